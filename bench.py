@@ -17,6 +17,15 @@ entries of include/libfiasco_amd.h.  Two timed loops over the same batch:
                pinned staging, host->HBM copy), the transfer of pass i+1 overlapping the
                kernel of pass i.
 
+A plain run times loop A only: set-up, --warmup passes, --steps timed passes, the outputs of the
+last pass if --dump-outputs is given, the result line.  Everything else -- loop B, the decoder
+pass, the 4K / colour / video / small-launch passes, the CPU baseline, the stream md5 against
+the reference's and the algorithmic bytes of speculating launches -- runs with --full only.
+
+--dump-outputs DIR writes the .fco streams of the last timed pass of rank 0: the length of
+every stream (stream_lengths.npy, float64) and the bytes of a fixed, seeded sample of the
+streams (stream_<frame>.npy, float32, 0..255), at most 64 MB in all.
+
 Multi-GPU: one process per GPU (torch.distributed, backend nccl == RCCL).  `--gpus N` without
 a torchrun environment starts the N ranks itself.  Frames are independent units (SURVEY.md
 §8e), so every rank encodes its own F frames (weak scaling) with no data-path collective; the
@@ -424,12 +433,32 @@ def _frame(args):
 
 def make_frames(w, h, seeds):
     import multiprocessing as mp
-    nproc = max(1, min(len(os.sched_getaffinity(0)), 32, len(seeds) // 4))
+    nproc = max(1, min(len(os.sched_getaffinity(0)), 16, len(seeds) // 4))
     work = [(w, h, s) for s in seeds]
     if nproc == 1:
         return [_frame(a) for a in work]
     with mp.get_context("fork").Pool(nproc) as pool:
         return pool.map(_frame, work, chunksize=4)
+
+
+DUMP_SAMPLE = 128                 # streams whose bytes --dump-outputs writes
+DUMP_BUDGET = 60 << 20            # bytes of .npy data in all, below the 64 MB limit
+
+
+def dump_outputs(d, streams):
+    """--dump-outputs: what the timed path returns -- one .fco byte string per frame -- as arrays
+    that two builds can be compared on.  The sample of frames depends only on the number of
+    frames (frame 0, the survey image, and a seeded draw of the others); a stream longer than its
+    share of the budget is cut, its full length is in stream_lengths.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    n = len(streams)
+    np.save(os.path.join(d, "stream_lengths.npy"), np.array([len(s) for s in streams], dtype=np.float64))
+    pick = [0] + sorted(np.random.default_rng(1234).choice(np.arange(1, n), min(n, DUMP_SAMPLE) - 1,
+                                                            replace=False).tolist())
+    cap = DUMP_BUDGET // (4 * len(pick))
+    for i in pick:
+        np.save(os.path.join(d, "stream_%05d.npy" % i), np.frombuffer(streams[i][:cap], dtype=np.uint8).astype(np.float32))
 
 
 def free_port():
@@ -465,13 +494,21 @@ def main():
     ap.add_argument("--no-k4-small", action="store_true", help="skip the 64- and 8-frame 4K launches (BASELINE config 4 as written)")
     ap.add_argument("--config5-frames", type=int, default=300,
                     help="frames of the extra 1280x720 colour video pass (BASELINE config 5 on one GPU; 0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: loop B, the decoder pass, the 4K / colour / "
+                         "video / small-launch passes, the CPU baseline and the parity check against the reference "
+                         "(the --no-* and --*-frames options above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the streams of the last timed pass of rank 0 as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # started without a launcher: become `python -m torch.distributed.run` with one rank per GPU
+        # started without a launcher: run `python -m torch.distributed.run` with one rank per GPU
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus),
                "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        sys.exit(subprocess.call(cmd))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -550,9 +587,9 @@ def main():
             out = batch.encode()
         # A launch this small runs several workgroups per frame; the coder's byte counters then cover
         # the chain workgroup only.  The algorithmic bytes of a frame do not depend on who computes
-        # them: taken from one pass with one workgroup per frame.
+        # them: taken from one pass with one workgroup per frame (--full; else not reported).
         alg_override = None
-        if lib.get_stats().spec_frames:
+        if a.full and lib.get_stats().spec_frames:
             os.environ["FIASCO_AMD_DEBUG"] = "1"; os.environ["FIASCO_AMD_SPEC"] = "0"
             b1 = fiasco_amd.Batch(lib, frames, 20.0, opt)
             lib.reset_stats(); b1.encode(); s1 = lib.get_stats(); b1.free()
@@ -571,11 +608,15 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
         st = lib.get_stats()
+        assert out is not None and all(o is not None for o in out), lib.error_message()
+        if rank == 0 and a.dump_outputs:
+            dump_outputs(a.dump_outputs, out)
         root = batch.stats(0)          # coder-side error of the survey frame
-        decoder = None
+        decoder = decoded_psnr = None
         try:                           # ... and its decoded PSNR (dfiasco -s 0 + pnmpsnr)
-            decoded_psnr = batch.decode_psnr(0)[0][0] if rank == 0 else None
-            if rank == 0 and not a.no_decoder:
+            if rank == 0 and a.full:
+                decoded_psnr = batch.decode_psnr(0)[0][0]
+            if rank == 0 and a.full and not a.no_decoder:
                 # all frames of the pass through the device decoder (one launch per level and
                 # frame, csrc/hip/frame_decoder.inc) + download + the host's pnmpsnr sum -- outside the timed region
                 lib.reset_stats()
@@ -596,9 +637,8 @@ def main():
         except Exception as e:
             decoded_psnr = None
             decoder = {"error": str(e)[:200]}
-        assert out is not None and all(o is not None for o in out), lib.error_message()
         # ---- loop B: the frames of every pass cross PCIe inside the timed region ----
-        if not a.no_pcie_loop:
+        if a.full and not a.no_pcie_loop:
             def rot(r):
                 r %= F
                 return frames[r:] + frames[:r]
@@ -624,15 +664,16 @@ def main():
                 "pipelined pass did not encode the uploaded frames"
         batch.free()
         small = k4 = c5 = c3 = k4s = None
-        if rank == 0 and world == 1 and a.k4_frames > 0 and (a.width, a.height) == (1920, 1080):
+        extras = a.full and rank == 0 and world == 1 and (a.width, a.height) == (1920, 1080)
+        if extras and a.k4_frames > 0:
             k4 = k4_pass(lib, a.k4_frames, rank)
-        if rank == 0 and world == 1 and not a.no_k4_small and (a.width, a.height) == (1920, 1080):
+        if extras and not a.no_k4_small:
             k4s = k4_small_pass(lib)
-        if rank == 0 and world == 1 and a.config3_frames > 0 and (a.width, a.height) == (1920, 1080):
+        if extras and a.config3_frames > 0:
             c3 = config3_pass(lib, a.config3_frames)
-        if rank == 0 and world == 1 and a.config5_frames > 0 and (a.width, a.height) == (1920, 1080):
+        if extras and a.config5_frames > 0:
             c5 = config5_pass(lib, a.config5_frames)
-        if rank == 0 and world == 1 and not a.no_small_launches and (a.width, a.height) == (1920, 1080):
+        if extras and not a.no_small_launches:
             small = small_launches(lib, opt, uniq, a.width, a.height)
 
     t = torch.tensor([dt, dt2], dtype=torch.float64, device=cdev)
@@ -655,7 +696,7 @@ def main():
     kernel_ms, alg_bytes, launches, nframes, kernel_ms2, nframes2 = [float(x) for x in agg.tolist()]
 
     if rank == 0:
-        md5_ref = REF_MD5_SEED1234.get((a.width, a.height))
+        md5_ref = REF_MD5_SEED1234.get((a.width, a.height)) if a.full else None
         if md5_ref and not dry:
             assert hashlib.md5(out[0]).hexdigest() == md5_ref, "parity lost: stream differs from the reference"
         total_frames = total_job * a.steps
@@ -663,8 +704,10 @@ def main():
         per_launch_bytes = alg_bytes / max(launches, 1)
         if not dry and alg_override is not None and world == 1:
             per_launch_bytes = alg_override
+        elif st is not None and st.spec_frames and world == 1:
+            per_launch_bytes = None                # chain workgroups' counters only: not the launch's bytes
         avg_kernel_s = (kernel_ms / 1e3) / max(launches, 1)
-        achieved = per_launch_bytes / avg_kernel_s / 1e9 if avg_kernel_s else None
+        achieved = per_launch_bytes / avg_kernel_s / 1e9 if avg_kernel_s and per_launch_bytes is not None else None
         res = {
             "metric": "grayscale frames/sec encoded",
             "value": value, "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -722,7 +765,7 @@ def main():
         }
         if dry:
             res["dry_run"] = True
-        if world == 1 and not a.no_cpu_baseline and not dry:
+        if a.full and world == 1 and not a.no_cpu_baseline and not dry:
             res["cpu_baseline"] = cpu_baseline(uniq[0], a.width, a.height)
         print(json.dumps(res), flush=True)
     if world > 1:

@@ -166,6 +166,7 @@ if [ -z "${FIASCO_SKIP_REF_BIG:-}" ] && { [ ! -x "$OUT/cfiasco_ref_big" ] || [ "
     TMPSRC=$(mktemp -d /tmp/fiasco_ref_big.XXXXXX)
     trap 'rm -rf "$TMPSRC"' EXIT
     cp -r "$REF/lib" "$REF/input" "$REF/output" "$REF/codec" "$REF/bin" "$REF/fiasco.h" "$TMPSRC/"
+    chmod -R u+w "$TMPSRC"         # the copy keeps the modes of read-only sources: sed -i and rm -rf need to write
     sed -i -e 's/^#define MAXSTATES 6000$/#define MAXSTATES 30000/' \
            -e 's/^#define MAXLEVEL  22 *$/#define MAXLEVEL  26/' "$TMPSRC/codec/wfa.h"
     sed -i -e 's/counts_1 \[level\];/counts_1 [level < 22 ? level : 21];/' \
