@@ -145,7 +145,7 @@ static bool needs_big_variant(const fa_cparams *cp, const fa_wfa *basis)
 }
 
 /* The 256-thread default build keeps a shorter stack and smaller snapshot pools in LDS than the
- * wide one (frame_coder.hip: FC_MAXDEPTH_NARROW, FC_SNAP16_NARROW, FC_SNAPTM_NARROW -- sized
+ * wide one (frame_coder.h: FC_MAXDEPTH_NARROW, FC_SNAP16_NARROW, FC_SNAPTM_NARROW -- sized
  * for what the stock reference accepts, level <= 22); a frame beyond them is given to the
  * wide build whatever the size of the launch. */
 static bool needs_wide_variant(const fa_cparams *cp)

@@ -139,24 +139,12 @@
 #ifndef FC_SPEC
 #define FC_SPEC 0
 #endif
-#ifndef SPEC_THR
 #define SPEC_THR 1.2f          /* FC_SPEC: see SpecLocal.mlc */
-#endif
-/* FC_SPINE: left-spine batching (mp_wave.inc) -- the linear-combination searches of a node and of its
- * chain of first children run at once, one per wave.  Bit-exact (the parked results are what the
- * searches would have found: same models, same dictionary), but it does not pay: a wave on its own
- * needs 3.4 x the time of the four waves together for one search, so a spine of three ranges costs what
- * three searches cost (519 .. 572 frames/s against 549 on the bench batch).
- * Kept as a build switch of the 256-thread default build for whoever wants to re-measure; off. */
 /* FC_D5T: the table of level-images_level dots is kept state-major, d5T[state][label][NA / 2] (address a ->
  * label a & 1, column a >> 1), so that the first pass of op_ipis reads four consecutive slots of one term with
- * ONE 16-byte load instead of four 4-byte gathers from four rows.  Same values, same sums. */
-#ifndef FC_D5T
+ * ONE 16-byte load instead of four 4-byte gathers from four rows.  Same values, same sums.  Not in the big
+ * build: it reads d5 rows as matching pursuit numerators. */
 #define FC_D5T (!FC_VARIANT_BIG)
-#endif
-#if FC_D5T && FC_VARIANT_BIG
-#error "FC_D5T: the big build reads d5 rows as matching pursuit numerators"
-#endif
 #if FC_D5T
 #define D5_AT(P, NA, a, s) ((unsigned) (s) * (unsigned) (NA) + (unsigned) ((a) & 1) * ((unsigned) (NA) >> 1) + ((unsigned) (a) >> 1))
 #else
@@ -164,38 +152,8 @@
 #endif
 /* FC_PRIO_ROTATE: rotating instruction priority of the frames that share a CU (kernel loop); the 256-thread default
  * build, whose launches put four workgroups on a CU */
-#ifndef FC_PRIO_ROTATE
 #define FC_PRIO_ROTATE (!FC_VARIANT_BIG && !FC_VARIANT_WIDE && !FC_SPEC)
-#endif
-#ifndef FC_PRIO_SHIFT
 #define FC_PRIO_SHIFT 20            /* 2^20 ticks of the 100 MHz wall clock: 10 ms per turn (82 us .. 42 ms measured: 580 .. 589 frames/s) */
-#endif
-#ifndef FC_SPINE
-#define FC_SPINE 0
-#endif
-#if FC_SPINE && (FC_VARIANT_BIG || FC_VARIANT_WIDE || FC_SPEC)
-#error "FC_SPINE is a variant of the 256-thread default build"
-#endif
-#define FC_SPINE_W 4            /* ranges of a spine searched at once: one per wave of the 256-thread build */
-/* FC_BLKEST: the sweep of a matching-pursuit pass prices whole 64-state blocks at once where the position
- * pricing is the same for every candidate of the block (mp_device.inc, stage1_block_price).  Exact as
- * well, and also no gain (520 against 549 frames/s): from the second pass on a fifth of the blocks hold a
- * breakpoint of the pricing and go the long way round anyway.  Off. */
-#ifndef FC_BLKEST
-#define FC_BLKEST 0
-#endif
-#if FC_BLKEST && (FC_VARIANT_BIG || FC_SPEC)
-#error "FC_BLKEST needs the default geometry without speculation (Sh::cum)"
-#endif
-/* FC_EST_RCP: the sweep's block minima are taken over a tight lower bound of the estimates
- * (reciprocal instead of division, stage1<.., LBQ> in mp_device.inc) */
-#ifndef FC_EST_RCP
-#define FC_EST_RCP 1
-#endif
-/* FC_MIN4: block minima of the register scan four slots at a time (interleaved DPP chains) */
-#ifndef FC_MIN4
-#define FC_MIN4 1
-#endif
 #define MAXED   FC_MAXED
 /* edges per label a state of this build can have (= max_elements the build accepts): the table
  * ops read and gather exactly that many term slots (+ the tree child), not the format's 5 */
@@ -317,9 +275,7 @@ struct __attribute__((aligned(16))) CoeffBuf {
  * after the combination): (depths + levels) x n16 uint4.  The 256-thread build is sized for the
  * frames the stock reference accepts (level <= 22) at the CLI's models; what needs more goes to
  * the 512-thread build (one frame per CU, LDS to spare) -- core_hip.cpp routes by these numbers. */
-#ifndef SNAP_POOL16
 #define SNAP_POOL16 (FC_VARIANT_WIDE ? FC_SNAP16_WIDE : FC_SNAP16_NARROW)
-#endif
 /* the default build never prices with the second tree model (prediction, big build only): a
  * snapshot holds the first one alone, 2 x MAXLEVEL words rounded to 16 bytes (21 depths x 13 uint4) */
 #define SNAP_TM_WORDS (FC_VARIANT_WIDE ? FC_SNAPTM_WIDE : FC_SNAPTM_NARROW)
@@ -391,31 +347,11 @@ struct Sh {
     float    Q0, Q1;
     float    tb[2];                /* default build: tree_bits (LEAF, CHILD) of the level being approximated (mp_tables) */
     MPState  mp;
-#if FC_SPINE
-    /* left-spine batching (mp_wave.inc): search state and result of the range w levels below the top node
-     * of the current spine, with the log2 table of its level's coefficient context and its tree prices;
-     * slot 0 is the top node itself.  spine_n ranges were searched when the node at stack depth spine_top
-     * was entered; spine_next is the depth of the next one the partition search may pick up; spine_use
-     * (lane 0, per OP_APPROX) is the slot of the node being approximated, 0 = search it now. */
-    struct SpineSlot { MPState mp; double lglv[16], lglv_m1; float tb[2]; } spine[FC_SPINE_W];
-    int      spine_top, spine_n, spine_next, spine_use;
-    /* ticks (100 MHz) and calls of OP_APPROX by kind: 0 a spine of K >= 2 ranges, 1 a parked result picked
-     * up, 2 one range searched by the whole workgroup; [3] = ranges searched in spines (DevFrame.dbg) */
-    unsigned long long spine_t[3];
-    unsigned spine_c[4];
-#endif
 #if FC_VARIANT_BIG
     MPState  mp_keep;              /* best result so far of a call with retries */
     int      apx_stage, apx_it, apx_more;   /* retry plan of approximate_range (lane 0) */
 #endif
     float    blockmin[NBLOCKMIN];
-#if FC_BLKEST
-    /* cum[b] = pool position of the first pool state with id >= 64 b (states enter the rle pool in id
-     * order, codec/domain-pool.c:832-852): the positions of block b are the run [cum[b], cum[b + 1]), the
-     * last block's ends at pool.n.  Written when state 64 b is stored (store_new_state); an entry is
-     * rewritten whenever that id is created again after a removal, so it always fits the dictionary. */
-    unsigned short cum[NBLOCKMIN + 2];
-#endif
     /* 16-byte aligned: op_d5 reads the block's pixels with 128-bit LDS loads (a member added in front of them in round 6
      * shifted them by four bytes: init_range +10 %) */
     __attribute__((aligned(16))) float pixels[FC_PIXELS];
@@ -425,10 +361,6 @@ struct Sh {
         unsigned long long bytes_mp, bytes_img, bytes_gram, n_mp, n_steps, n_blocks, n_appends,
                            n_fulleval, n_blockevals, t_mpA, t_mpB;
     } cnt;                         /* DevFrame counters of the same names */
-#ifdef FC_PM
-    unsigned long long pm[8], pm_t;
-    int pm_prev;
-#endif
 #ifdef FC_SERIAL_PROFILE
     unsigned long long tk_ph[8], ph_t0, tk_init[2], tk_apx[4];
     int      ph_prev;
@@ -2629,13 +2561,6 @@ __device__ __forceinline__ void snap_coop_after(Sh &sh, SFrame &fr, int depth)
 
 __device__ float tree_bits_dev(const Sh &sh, int ML, int child, int level, int which);
 
-#ifdef FC_PM
-#define PM0(sh) do { (sh).pm_t = wall_clock64(); } while (0)
-#define PM(sh, i, g) do { if (FC_PM == (g)) { unsigned long long t_ = wall_clock64(); (sh).pm[i] += t_ - (sh).pm_t; (sh).pm_t = t_; } } while (0)
-#else
-#define PM0(sh) do { } while (0)
-#define PM(sh, i, g) do { } while (0)
-#endif
 #include "mp_device.inc"
 
 /* ------------------------------------------------------------------ serial state machine */
@@ -2731,9 +2656,6 @@ __device__ void store_new_state(DevFrame &__restrict__ F, Sh &sh, SFrame &fr, in
     GLOBAL_AS float *const weight = (GLOBAL_AS float *) sh.par.at_weight, *const fin = (GLOBAL_AS float *) sh.par.at_final;
     GLOBAL_AS uint16_t *const xs = (GLOBAL_AS uint16_t *) sh.par.at_x, *const ys = (GLOBAL_AS uint16_t *) sh.par.at_y;
     short p = -1;
-#if FC_BLKEST
-    if ((s & 63) == 0 && (s >> 6) <= NBLOCKMIN) sh.cum[s >> 6] = sh.pool.n;
-#endif
     if (!aux && sh.pool.n < sh.pool.max_domains) {
         p = (short) sh.pool.n;
         pool[sh.pool.n++] = (short) s;
@@ -2900,10 +2822,6 @@ __device__ void push_root(DevFrame &__restrict__ F, Sh &__restrict__ sh, int y_s
     r.max_costs = MAXCOSTS;
     r.y_state = y_state;
     r.phase = PH_ENTER;
-#if FC_SPINE
-    sh.spine_n = 0; sh.spine_use = 0;
-    if (sh.band == 0) { for (int k = 0; k < 3; k++) sh.spine_t[k] = 0; for (int k = 0; k < 4; k++) sh.spine_c[k] = 0; }
-#endif
 #if FC_SPEC
     r.ckpt = 0;
 #endif
@@ -3082,53 +3000,6 @@ __device__ __forceinline__ int serial_step(DevFrame &__restrict__ F, Sh &__restr
             return 1;
         }
         SFrame &fr = sh.st[sp];
-#if defined(FC_PM) && FC_PM == 4
-        /* developer micro-benchmark of the serial lane under the live load of the CU: every 1024th
-         * transition, 64 dependent LDS reads / 64 dependent float adds / 64 independent LDS reads /
-         * 64 dependent int ops; ticks (100 MHz) in pm[0..3], samples in pm[7] */
-        if ((sh.pm_prev++ & 1023) == 0) {
-            volatile int *chain = (volatile int *) sh.pixels;      /* scratch area of the block, unused here */
-            int keep[8];
-            for (int k = 0; k < 8; k++) keep[k] = chain[k];
-            for (int k = 0; k < 8; k++) chain[k] = (k + 1) & 7;
-            unsigned long long t0 = wall_clock64();
-            int idx = 0;
-            for (int k = 0; k < 64; k++) idx = chain[idx];
-            unsigned long long t1 = wall_clock64();
-            float a = __int_as_float(idx + 0x3f800000);
-            for (int k = 0; k < 64; k++) a = a + 1.25f;
-            asm volatile("" : "+v"(a));
-            unsigned long long t2 = wall_clock64();
-            int sum = 0;
-#pragma unroll
-            for (int k = 0; k < 64; k++) sum += chain[k & 7];
-            asm volatile("" : "+v"(sum));
-            unsigned long long t3 = wall_clock64();
-            int x = sum;
-            for (int k = 0; k < 64; k++) x = x * 3 + 1;
-            asm volatile("" : "+v"(x));
-            unsigned long long t4 = wall_clock64();
-            {   /* dependent global loads: 32 lines of the Gram table far apart (cold: HBM or L2),
-                 * then the same 32 again (warm: L1/L2) */
-                const volatile float *g = F.gram;
-                const size_t stride = (size_t) F.P * 8 + 64;
-                unsigned long long u0 = wall_clock64();
-                size_t o = (size_t) (x & 1);
-                for (int k = 0; k < 32; k++) { float v = g[o]; o = (size_t) (k + 1) * stride + (size_t) (__float_as_int(v) & 1); }
-                unsigned long long u1 = wall_clock64();
-                o = (size_t) (o & 1);
-                for (int k = 0; k < 32; k++) { float v = g[o]; o = (size_t) (k + 1) * stride + (size_t) (__float_as_int(v) & 1); }
-                unsigned long long u2 = wall_clock64();
-                sh.pm[4] += u1 - u0; sh.pm[5] += u2 - u1; sh.pm[6] += o & 1;
-            }
-            for (int k = 0; k < 8; k++) chain[k] = keep[k];
-            sh.pm[0] += t1 - t0; sh.pm[1] += t2 - t1; sh.pm[2] += t3 - t2; sh.pm[3] += t4 - t3;
-            sh.pm[7] += 1; sh.pm[6] += (unsigned long long) ((x & 1) + (__float_as_int(a) & 1));
-        }
-#endif
-#if defined(FC_PM) && FC_PM == 3
-        { unsigned long long t_ = wall_clock64(); sh.pm[sh.pm_prev & 7] += t_ - sh.pm_t; sh.pm_t = t_; sh.pm_prev = phase; }
-#endif
 #ifdef FC_SERIAL_PROFILE
         {   /* developer profile: ticks per phase of the state machine (previous phase ends here) */
             unsigned long long t = wall_clock64();
@@ -3226,21 +3097,6 @@ __device__ __forceinline__ int serial_step(DevFrame &__restrict__ F, Sh &__restr
                 fr.lrange.nd_tree_bits = 0; fr.lrange.nd_weights_bits = 0; fr.lrange.prediction = 0;
                 fr.lrange.mv_tree_bits = fr.try_pred == 2 ? 1.0f : 0.0f;   /* mc allowed but not used */
                 fr.lrange.mv_coord_bits = 0;
-#endif
-#if FC_SPINE
-                {   /* Is this range the next one on the spine that was searched when its top node was entered
-                     * (mp_wave.inc)?  It is iff the search has descended from the last range picked up into
-                     * its FIRST child: models, dictionary and tree model are then what the spine's search saw
-                     * (codec/subdivide.c:226-237 restores them before :303-310 recurses).  Anything else
-                     * drops what is parked. */
-                    int use = 0;
-                    if (sh.spine_n) {
-                        if (sp == sh.spine_next && sp - sh.spine_top < sh.spine_n && sh.st[sp - 1].label == 0) {
-                            use = sp - sh.spine_top; sh.spine_next = sp + 1;
-                        } else sh.spine_n = 0;
-                    }
-                    sh.spine_use = use;
-                }
 #endif
                 sh.op = OP_APPROX;
                 return 0;
@@ -4151,9 +4007,6 @@ FC_KERNEL(DevFrame *frames, unsigned nlend, unsigned long long *ring, unsigned *
         for (int i = 0; i <= MAXED; i++) { m.count[i] = 1; m.total++; }
         m.n = 0; m.max_domains = (unsigned short) F.pool_max; m.y_index = 0;
         m.d0_index = 0; m.d0_yindex = 0; m.d0_n = 0;
-#if FC_BLKEST
-        sh.cum[0] = 0;
-#endif
 #if FC_GM
         /* alloc_domain_pool and the allocators behind it (codec/domain-pool.c:203-236) for the kinds of both sets */
         sh.gm.pk[0] = F.gm_pool[0]; sh.gm.pk[1] = F.pred_on ? F.gm_pool[1] : FC_PK_CONSTANT;
@@ -4287,9 +4140,6 @@ FC_KERNEL(DevFrame *frames, unsigned nlend, unsigned long long *ring, unsigned *
     if (tid == 0) for (int k = 0; k < 16; k++) tk[k] = 0;
 #ifdef FC_SERIAL_PROFILE
     if (tid == 0) { for (int k = 0; k < 8; k++) sh.tk_ph[k] = 0; sh.ph_prev = 0; sh.ph_t0 = 0; sh.tk_init[0] = sh.tk_init[1] = 0; for (int k = 0; k < 4; k++) sh.tk_apx[k] = 0; }
-#endif
-#ifdef FC_PM
-    if (tid == 0) for (int k = 0; k < 8; k++) sh.pm[k] = 0;
 #endif
     unsigned long long t_begin = wall_clock64();
     /* everything below is inlined into this one loop (a single call site per op keeps the
@@ -4623,13 +4473,7 @@ FC_KERNEL(DevFrame *frames, unsigned nlend, unsigned long long *ring, unsigned *
 #ifdef FC_SERIAL_PROFILE
             sh.ph_t0 = t1;
 #endif
-#if defined(FC_PM) && FC_PM == 3
-            sh.pm_t = wall_clock64(); sh.pm_prev = 7;
-#endif
             serial_advance(F, sh);
-#if defined(FC_PM) && FC_PM == 3
-            { unsigned long long t_ = wall_clock64(); sh.pm[sh.pm_prev & 7] += t_ - sh.pm_t; }
-#endif
 #ifdef FC_SERIAL_PROFILE
             { unsigned long long t = wall_clock64(); sh.tk_ph[sh.ph_prev] += t - sh.ph_t0; }
 #endif
@@ -4699,7 +4543,7 @@ FC_KERNEL(DevFrame *frames, unsigned nlend, unsigned long long *ring, unsigned *
         F.n_mp = sh.cnt.n_mp; F.n_steps = sh.cnt.n_steps; F.n_blocks = sh.cnt.n_blocks;
         F.n_appends = sh.cnt.n_appends; F.n_fulleval = sh.cnt.n_fulleval;
         F.n_blockevals = sh.cnt.n_blockevals; F.t_mpA = sh.cnt.t_mpA; F.t_mpB = sh.cnt.t_mpB;
-#if FC_VARIANT_BIG && !defined(FC_SERIAL_PROFILE) && !defined(FC_PM)
+#if FC_VARIANT_BIG && !defined(FC_SERIAL_PROFILE)
         /* the ops only this build has (ticks): chroma set-up, prediction set-up / finish, norms, motion search */
         F.dbg[2] = tk[OP_CHROMA]; F.dbg[3] = tk[OP_PRED_SETUP]; F.dbg[4] = tk[OP_PRED_FINISH];
         F.dbg[5] = tk[OP_NORMS]; F.dbg[6] = tk[OP_MC_SEARCH];
@@ -4711,18 +4555,7 @@ FC_KERNEL(DevFrame *frames, unsigned nlend, unsigned long long *ring, unsigned *
         F.dbg[3] = sh.tk_apx[0]; F.dbg[4] = sh.tk_apx[1]; F.dbg[5] = sh.tk_apx[2]; F.dbg[2] = sh.tk_apx[3];
 #endif
     }
-#ifdef FC_PM
-    if (tid == 0) for (int k = 0; k < 8; k++) F.dbg[k] = sh.pm[k];
-#elif FC_SPINE && !defined(FC_SERIAL_PROFILE) && !defined(FC_BLKEST_CHECK)
-    if (tid == 0) {
-        for (int k = 0; k < 3; k++) { F.dbg[2 * k] = sh.spine_t[k]; F.dbg[2 * k + 1] = sh.spine_c[k]; }
-        F.dbg[6] = sh.spine_c[3];
-        /* which SIMD runs wave 0 (the serial lane): histogram over the frames of a launch, 16 bits per SIMD
-         * (HW_REG_HW_ID, bits 5:4) */
-        F.dbg[7] = 1ull << (16 * ((__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 4) & 3));
-    }
-#endif
-#if FC_SPEC && !defined(FC_PM) && !defined(FC_SERIAL_PROFILE)
+#if FC_SPEC && !defined(FC_SERIAL_PROFILE)
     if (tid == 0) { F.dbg[0] = tk[OP_SPEC_CKPT]; F.dbg[1] = 0; }   /* ticks of the chain in checkpoints, verdicts and returns */
 #endif
     if (tid == 0) {

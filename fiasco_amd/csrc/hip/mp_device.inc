@@ -81,44 +81,6 @@ __device__ __forceinline__ void load_step_ctx(const MPState &mp, StepCtx &c)
  * is a LOWER bound of the estimate, tight to 5e-7 of the quotient.  For the block minima of the
  * sweep only: the rounds ask them which blocks they may skip, what a block holds is evaluated with
  * the exact estimate (LBQ = false) -- a lower bound in their place changes no result. */
-/* the position part of stage1()'s estimate once more, operation for operation: rle_bits of {kept vectors
- * + d} for a candidate that is neither position 0 nor the co-located luminance state.  `key` collects every data-dependent choice made on the
- * way (interval, the two code lengths): over a run of consecutive positions each of them is monotone, so
- * two positions with equal keys price every position between them exactly alike (stage1_block_price). */
-template <int MAXNP, int NP = -1>
-__device__ __forceinline__ float stage1_bits(const StepCtx &c, int d, unsigned &key)
-{
-    const int np = NP >= 0 ? NP : c.np;
-    float bits = c.pre[0];
-    int last = c.last[0], k = c.k[0], thr = c.thr[0], i = 0;
-    bool cd = c.cd & 1u;
-    int nextp = np > 0 ? c.p[0] : -1;
-#pragma unroll
-    for (int j = 0; j < MAXNP; j++)
-        if (j < np && d > c.p[j]) {
-            i = j + 1;
-            bits = c.pre[j + 1]; last = c.last[j + 1]; k = c.k[j + 1]; thr = c.thr[j + 1];
-            cd = (c.cd >> (j + 1)) & 1u;
-            nextp = (j + 1 < MAXED - 1 && j + 1 < np) ? c.p[(j + 1) % (MAXED - 1)] : -1;
-        }
-    key = (unsigned) i;
-    if (cd) {
-        const bool lt = d - last < thr;
-        bits += (float) (lt ? k : k + 1);
-        key |= lt ? 8u : 0u;
-    }
-    const unsigned mv = c.N - 2u - (unsigned) d;
-    if (nextp >= 0 && mv != 0) {
-        const unsigned code = bits_bin_code((unsigned) (nextp - d - 1), mv);
-        bits += (float) code;
-        key |= 16u | (code << 5);
-#pragma unroll
-        for (int j = 1; j < MAXNP; j++)
-            if (j > i && j < np && ((c.has >> j) & 1u)) bits += c.sfx[j];
-    }
-    return bits;
-}
-
 template <int MAXNP, int NP = -1, bool LBQ = false>
 __device__ __forceinline__ float stage1(const StepCtx &c, int d, int state, float num, float den)
 {
@@ -150,33 +112,6 @@ __device__ __forceinline__ float stage1(const StepCtx &c, int d, int state, floa
         return (bits + weights_bits + c.ab) * c.price + c.err
                - num * num * (__builtin_amdgcn_rcpf(den) * 1.00000047683715820312f);
     return (bits + weights_bits + c.ab) * c.price + c.err - num * num / den;
-}
-
-/* FC_BLKEST: the sweep prices whole 64-state blocks at once.  The estimate of a candidate is
- * fl(A - Q) with A = fl(fl((bits + wb + ab) * price) + err) and Q = fl(fl(num * num) / den); A depends on
- * the candidate's pool POSITION only (and on whether it is state 0 or the luminance state).  The
- * positions of the pool states of block b are the run [cum[b], cum[b + 1]) (Sh::cum: states enter the
- * pool in id order).  If the two ends of the run have equal keys (stage1_bits) every candidate of the
- * block has the same A, and since fl is monotone the block minimum of fl(A - Q') over an upper bound Q' of
- * Q is a lower bound of every estimate of the block -- all the ordered scan asks of a block minimum.
- * A candidate then costs the quotient and one subtraction instead of the whole position pricing; the
- * few blocks that a breakpoint of the pricing falls into (and block 0: state 0) are priced candidate
- * by candidate as before.  Returns A of the block whose positions run from plo to phi, pure = it may be used. */
-template <int MAXNP, int NP = -1>
-__device__ __forceinline__ float stage1_block_price(const StepCtx &c, int plo, int phi, bool &pure)
-{
-    unsigned klo, khi;
-    const float bits = stage1_bits<MAXNP, NP>(c, plo, klo);
-    (void) stage1_bits<MAXNP, NP>(c, phi, khi);
-    pure = klo == khi && plo > 0 && plo <= phi && (c.ypos < plo || c.ypos > phi);
-    /* a kept vector's own position prices like nothing else (its distance to "the next kept position"
-     * is -1): a block that holds one -- even as its first or last position, where the interval index
-     * does not change -- is priced candidate by candidate */
-    const int np = NP >= 0 ? NP : c.np;
-#pragma unroll
-    for (int j = 0; j < MAXNP; j++)
-        if (j < np && c.p[j] >= plo && c.p[j] <= phi) pure = false;
-    return (bits + c.wb_nd + c.ab) * c.price + c.err;
 }
 
 /* ---- coefficient prices that are the host's, bit for bit ----
@@ -247,8 +182,7 @@ __device__ __forceinline__ float btor_fast(int b, int mant, float range)
 
 /* full evaluation of the candidate (pool position d, state `state`) at step NN
  * (codec/approx.c:495-591; the self-feeding refresh :554-569 is omitted, SURVEY 7.3) */
-/* mp / lglv: the call's state and the log2 table of its level's coefficient context (sh.mp / sh.lglv, or
- * -- several ranges of a left spine searched at once, one per wave -- the wave's own, Sh::SpineSlot) */
+/* mp / lglv: the call's state and the log2 table of its level's coefficient context (sh.mp / sh.lglv) */
 template <int NN>
 __device__ __forceinline__ void full_eval_n(const DevFrame &F, const Sh &sh, const MPState &mp, const double *lglv,
                                             int d, int state,
@@ -582,7 +516,6 @@ __device__ void mp_step_prepare(const DevFrame &F, Sh &sh, MPState &mp, const do
             mp.psorted[j] = mp.indices[k];
         }
     mp.np = np;
-    PM(sh, 1, 1);
     {   /* uniform parts of the stage-1 position pricing, see StepCtx */
         const unsigned N = (unsigned) mp.N;
         const short *p = mp.psorted;
@@ -625,14 +558,12 @@ __device__ void mp_step_prepare(const DevFrame &F, Sh &sh, MPState &mp, const do
         for (int j = 0; j < np; j++) if (ev[j]) b += e[j];
         mp.s1_zy = b;
     }
-    PM(sh, 2, 1);
     {
         const int ctx = mp.level - sh.par.lc_min_opt;
         const int s_nd = sh.par.half_nd, s_dc = sh.par.half_dc;      /* rtob(0.5): constants of the model set (Sh::par) */
         mp.wb_nd = sub_log2(sh, wb, lglv[s_nd], sh.par.dcs + ctx * sh.par.sy + s_nd, ctx + 1);
         mp.wb_dc = sub_log2(sh, wb, sh.lgdc[s_dc], s_dc, 0);
     }
-    PM(sh, 3, 1);
 #if FC_GM
     {
         /* stage 1 prices {kept vectors with a non-zero weight (selection order), candidate} (codec/approx.c:433-458):
@@ -830,9 +761,6 @@ __device__ __forceinline__ void lds_barrier()
 }
 
 #include "mp_reg.inc"                 /* register-resident scan and the chroma list scan */
-#if FC_SPINE
-#include "mp_wave.inc"                /* several ranges of a left spine at once, one per wave */
-#endif
 
 /* general scan: per-candidate scratch in HBM (any number of states, up to MAXEDGES vectors).
  * Out of line on purpose: it is the cold variant (frames with more than KREG*B states or
@@ -1195,36 +1123,7 @@ __device__ __forceinline__ void op_approx(DevFrame &F, Sh &sh)
 #else
 #define APX_MARK(i) do { } while (0)
 #endif
-#if FC_SPINE
-    const unsigned long long t_op = tid == 0 ? wall_clock64() : 0ull;
-#endif
     if (fr.coop) snap_coop_before(sh, fr, sh.sp, sh.par.ML);
-#if FC_SPINE
-    /* left-spine batching (mp_wave.inc).  use > 0: this range was searched with the top node of its
-     * spine, the result waits in slot `use` -- only the accept test is left.  Otherwise, if the range
-     * can have children, it is the top node of a new spine of K ranges (itself + its chain of first
-     * children down to the smallest block level, at most one per wave). */
-    const int use = uni(sh.spine_use);
-    int K = 1;
-    if (!use && !sh.band && level > sh.lc_min && sh.states <= KREG * B && sh.states <= 64 * 64
-        && sh.par.max_elements <= FC_NIP + 1 && sh.par.sy <= 16 && sh.par.dcs <= 64) {
-        K = level - sh.lc_min + 1;
-        if (K > FC_SPINE_W) K = FC_SPINE_W;
-    }
-    const bool spine = use || K >= 2;                    /* uniform */
-    if (K >= 2) {
-        mp_tables_spine(F, sh, level, K, fr.lrange.image, fr.lrange.address, fr.price);
-        __syncthreads();
-        spine_search(F, sh, K);
-        if (tid == 0) { sh.spine_top = sh.sp; sh.spine_n = K; sh.spine_next = sh.sp + 1; }
-    }
-    MPState &fm = spine ? sh.spine[use].mp : sh.mp;      /* what the accept test looks at */
-    if (!spine) {
-#else
-    const bool spine = false;
-    MPState &fm = sh.mp;
-    {
-#endif
     mp_tables(F, sh, level, y);
     __syncthreads();
     APX_MARK(0);
@@ -1254,7 +1153,6 @@ __device__ __forceinline__ void op_approx(DevFrame &F, Sh &sh)
 #endif
     for (;;) {
     if (tid == 0) {
-        PM0(sh);
         mp.n = 0; mp.best_n = 0; mp.symp = SYMP_NONE;
         mp.D = D; mp.N = D;
         mp.y_state = y; mp.ypos = -1;
@@ -1315,7 +1213,6 @@ __device__ __forceinline__ void op_approx(DevFrame &F, Sh &sh)
 #endif
         mp.costs = (mp.matrix_bits + mp.weights_bits + mp.ab) * mp.price + mp.err;
         mp.index = -1;
-        PM(sh, 0, 1);
 #if FC_VARIANT_BIG
         mp_step_prepare(F, sh, mp, sh.lglv, sh.lglv_m1);
 #else
@@ -1329,7 +1226,6 @@ __device__ __forceinline__ void op_approx(DevFrame &F, Sh &sh)
             mp.min_costs = mp.costs;
         }
 #endif
-        PM(sh, 4, 1);
     }
     lds_barrier();                       /* the set-up lives in LDS; the scan's first reads stay in flight */
 
@@ -1419,17 +1315,8 @@ __device__ __forceinline__ void op_approx(DevFrame &F, Sh &sh)
 #endif
     }
 
-    }                                    /* !spine */
     if (tid == 0) {
-        PM0(sh);
-        MPState &mp = fm;
         Range &lr = fr.lrange;
-#if FC_SPINE
-        if (spine) {                         /* the tree prices of the range's level (mp_tables_spine) */
-            sh.tb[0] = sh.spine[use].tb[0]; sh.tb[1] = sh.spine[use].tb[1];
-            lr.tree_bits = sh.tb[0];
-        }
-#endif
         mp.indices[mp.best_n] = NOEDGE;
         float costs = (mp.matrix_bits + mp.weights_bits + mp.ab) * mp.price + mp.err;
         if (costs < fr.max_costs) {
@@ -1443,9 +1330,7 @@ __device__ __forceinline__ void op_approx(DevFrame &F, Sh &sh)
                     ni++;
                 }
             mp.indices[ni] = NOEDGE; mp.into[ni] = NOEDGE;
-            PM(sh, 0, 2);
             models_update(F, sh, mp.indices, mp.into, mp.weight, level, mp.y_state, sp);
-            PM(sh, 1, 2);
             int e = 0;
             for (; mp.indices[e] != NOEDGE; e++) { lr.into[e] = mp.into[e]; lr.weight[e] = mp.weight[e]; }
             lr.into[e] = NOEDGE;
@@ -1470,7 +1355,6 @@ __device__ __forceinline__ void op_approx(DevFrame &F, Sh &sh)
             } else sl.n_inline++;
         }
 #endif
-        PM(sh, 2, 2);
         if (sh.par.trace_on && F.trace_n < F.trace_cap) {
             FcTrace &t = F.trace[F.trace_n];
             t.seq = F.trace_n; t.level = level; t.image = mp.image; t.D = D; t.states = sh.states;
@@ -1485,23 +1369,11 @@ __device__ __forceinline__ void op_approx(DevFrame &F, Sh &sh)
         sh.cnt.bytes_mp += 4ull * D * (2 + mp.n) + 4ull * (1u << level);
         sh.cnt.n_mp++; sh.cnt.n_steps += mp.n;
 #endif
-        PM(sh, 3, 2);
-#if FC_SPINE
-        if (spine) {                         /* (lane 64 may be ahead of this wave's search: counted here) */
-            sh.cnt.bytes_mp += 4ull * D * (2 + fm.n) + 4ull * (1u << level);
-            sh.cnt.n_mp++; sh.cnt.n_steps += fm.n;
-        }
-        {
-            const int kind = use ? 1 : K >= 2 ? 0 : 2;
-            sh.spine_t[kind] += wall_clock64() - t_op; sh.spine_c[kind]++;
-            if (K >= 2) sh.spine_c[3] += K;
-        }
-#endif
     }
 #if !FC_VARIANT_BIG
-    else if (tid == 64 && !spine) {      /* the roofline counters, off the serial lane (mp.n is final) */
-        sh.cnt.bytes_mp += 4ull * D * (2 + fm.n) + 4ull * (1u << level);
-        sh.cnt.n_mp++; sh.cnt.n_steps += fm.n;
+    else if (tid == 64) {                /* the roofline counters, off the serial lane (mp.n is final) */
+        sh.cnt.bytes_mp += 4ull * D * (2 + mp.n) + 4ull * (1u << level);
+        sh.cnt.n_mp++; sh.cnt.n_steps += mp.n;
     }
 #endif
     if (fr.coop) {                       /* uniform */

@@ -208,79 +208,12 @@ __device__ __forceinline__ void mp_steps_reg(DevFrame &F, Sh &sh, int q, float s
         /* the estimates, one form per number of kept vectors (wave-uniform branch: the first
          * step of a call has none and prices a candidate without any interval select); lane 63
          * ends up with the block minimum and stores it */
-#if FC_BLKEST
-        /* Lane l prices the block of slot l as a whole (stage1_block_price, mp_device.inc): where every
-         * candidate of a block has the same position pricing -- all but the one or two blocks a breakpoint of
-         * the pricing falls into, and block 0 -- a candidate costs its quotient and one subtraction.  Bit l of
-         * pure_slots (wave uniform) says so, Ablk of lane l is the block's price.  First all slots that way
-         * (the pricing context is not touched: it need not be in registers), then the few others candidate by
-         * candidate as before. */
-        float Ablk;
-        unsigned pure_slots;
-        {
-            const int blk = NWAVES * lane + wave;
-            const int plo = blk < nblk ? (int) sh.cum[blk] : 1;
-            const int phi = (blk + 1 < nblk ? (int) sh.cum[blk + 1] : (int) ctx.N) - 1;
-            bool pure;
-            if (ctx.np == 0)      Ablk = stage1_block_price<NIP, 0>(ctx, plo, phi, pure);
-            else if (ctx.np == 1) Ablk = stage1_block_price<NIP, 1>(ctx, plo, phi, pure);
-            else                  Ablk = stage1_block_price<NIP, -1>(ctx, plo, phi, pure);
-            pure_slots = (unsigned) __ballot(pure && lane < KR && blk < nblk);
-        }
-#define EST_CHEAP(k, ek)                                                                         \
-        float ek = BIGF;                                                                         \
-        if ((k) < K && !((usmask >> (k)) & 1u) && ((pure_slots >> (k)) & 1u))                    \
-            ek = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Ablk), (k)))           \
-                 - num[k] * num[k] * (__builtin_amdgcn_rcpf(den[k]) * 1.00000047683715820312f);
-#pragma unroll
-        for (int k4 = 0; k4 + 4 <= KR; k4 += 4) {
-            if (k4 < K) {                                    /* uniform: skip unused groups */
-                EST_CHEAP(k4, e0) EST_CHEAP(k4 + 1, e1) EST_CHEAP(k4 + 2, e2) EST_CHEAP(k4 + 3, e3)
-                wave_min4_l63(e0, e1, e2, e3);
-                if (lane == 63) {
-                    sh.blockmin[NWAVES * k4 + wave] = e0;
-                    if (k4 + 1 < K) sh.blockmin[NWAVES * (k4 + 1) + wave] = e1;
-                    if (k4 + 2 < K) sh.blockmin[NWAVES * (k4 + 2) + wave] = e2;
-                    if (k4 + 3 < K) sh.blockmin[NWAVES * (k4 + 3) + wave] = e3;
-                }
-            }
-        }
-#pragma unroll
-        for (int k = KR / 4 * 4; k < KR; k++) {
-            if (k < K) {
-                EST_CHEAP(k, ek)
-                ek = wave_min_l63(ek);
-                if (lane == 63) sh.blockmin[NWAVES * k + wave] = ek;
-            }
-        }
-#undef EST_CHEAP
-        {
-            const unsigned imp = ~pure_slots & ((1u << K) - 1u);      /* wave uniform */
-#define EST_IMPURE(NPV)                                                                          \
-            _Pragma("unroll")                                                                    \
-            for (int k = 0; k < KR; k++)                                                       \
-                if ((imp >> k) & 1u) {                                                           \
-                    float ek = BIGF;                                                             \
-                    if (!((usmask >> k) & 1u))                                                   \
-                        ek = stage1<NIP, NPV, FC_EST_RCP != 0>(ctx, PS(k), k * B + tid, num[k], den[k]); \
-                    ek = wave_min_l63(ek);                                                       \
-                    if (lane == 63) sh.blockmin[NWAVES * k + wave] = ek;                         \
-                }
-            if (imp) {
-                if (ctx.np == 0)      { EST_IMPURE(0) }
-                else if (ctx.np == 1) { EST_IMPURE(1) }
-                else                  { EST_IMPURE(-1) }
-            }
-#undef EST_IMPURE
-        }
-#else
-#if FC_MIN4
         /* four slots at a time: the estimates of four blocks, then their minima with interleaved
          * DPP chains (wave_min4_l63) */
 #define EST_ONE(NPV, k, ek)                                                                      \
         float ek = BIGF;                                                                         \
         if ((k) < K && !((usmask >> (k)) & 1u))                                                  \
-            ek = stage1<NIP, NPV, FC_EST_RCP != 0>(ctx, PS(k), (k) * B + tid, num[k], den[k]);
+            ek = stage1<NIP, NPV, true>(ctx, PS(k), (k) * B + tid, num[k], den[k]);
 #define EST_PASS(NPV)                                                                            \
         _Pragma("unroll")                                                                        \
         for (int k4 = 0; k4 + 4 <= KR; k4 += 4) {                                              \
@@ -303,25 +236,11 @@ __device__ __forceinline__ void mp_steps_reg(DevFrame &F, Sh &sh, int q, float s
                 if (lane == 63) sh.blockmin[NWAVES * k + wave] = ek;                             \
             }                                                                                    \
         }
-#else
-#define EST_PASS(NPV)                                                                            \
-        _Pragma("unroll")                                                                        \
-        for (int k = 0; k < KR; k++) {                                                         \
-            if (k < K) {                                     /* uniform: skip unused slots */    \
-                float ek = BIGF;                                                                 \
-                if (!((usmask >> k) & 1u))                                                       \
-                    ek = stage1<NIP, NPV, FC_EST_RCP != 0>(ctx, PS(k), k * B + tid, num[k], den[k]); \
-                ek = wave_min_l63(ek);                                                           \
-                if (lane == 63) sh.blockmin[NWAVES * k + wave] = ek;                             \
-            }                                                                                    \
-        }
-#endif
         if (ctx.np == 0)      { EST_PASS(0) }
         else if (ctx.np == 1) { EST_PASS(1) }
         else                  { EST_PASS(-1) }
 #undef EST_PASS
 #undef EST_ONE
-#endif
         if (tid == 0) { rb.m2[1] = mp.min_costs; rb.state = -1; }   /* "round -1" */
         __syncthreads();
         if (tid == 0) { unsigned long long t = wall_clock64(); tA += t - tmark; tmark = t; }

@@ -7,7 +7,7 @@ name=$1; extra=${2:-}
 cd $R/fiasco_amd/csrc
 make -s >/dev/null
 B=build/var_$name; mkdir -p $B
-HF="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -mllvm -disable-machine-licm -I../../include -Ihost -Ihip -I../../experiments/r04_left_spine"
+HF="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -mllvm -disable-machine-licm -I../../include -Ihost -Ihip"
 /opt/rocm/bin/hipcc $HF ${NARROW_FLAGS--DFC_SERIAL_LOOP=1} $extra -c hip/frame_coder.hip -o $B/frame_coder.o &
 /opt/rocm/bin/hipcc $HF ${NARROW_FLAGS--DFC_SERIAL_LOOP=1} ${WIDE_FLAGS--DFC_WIDE_B=1024} $extra -DFC_VARIANT_WIDE=1 -c hip/frame_coder.hip -o $B/frame_coder_wide.o &
 /opt/rocm/bin/hipcc $HF ${NARROW_FLAGS--DFC_SERIAL_LOOP=1} ${WIDE_FLAGS--DFC_WIDE_B=1024} $extra -DFC_VARIANT_WIDE=1 -DFC_GRAM_TRI=1 -c hip/frame_coder.hip -o $B/frame_coder_wide_tri.o &

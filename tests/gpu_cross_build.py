@@ -1,6 +1,5 @@
-"""Developer helper (GPU box): n distinct frames through the 256-thread build (left-spine batching, block
-pricing) and through one wide workgroup per frame / several workgroups per frame (neither): every stream
-must be the same.  usage: gpu_cross_build.py W H n [reps]"""
+"""Developer helper (GPU box): n distinct frames through the 256-thread build and through one wide workgroup
+per frame / several workgroups per frame: every stream must be the same.  usage: gpu_cross_build.py W H n [reps]"""
 import hashlib
 import os
 os.environ.setdefault("FIASCO_AMD_DEBUG", "1")     # the library honours its developer switches only with this
