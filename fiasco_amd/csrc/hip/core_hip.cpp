@@ -127,7 +127,7 @@ static bool needs_big_variant(const fa_cparams *cp, const fa_wfa *basis)
     if (needs_hm_variant(cp)) return true;
     if (cp->prediction) return true;         /* second model set, residual search: big build only */
     if (long_basis(basis)) return true;
-    /* the default build reads 3 edge slots per label (frame_coder.hip FC_MAXE): a basis file
+    /* the default build reads 3 edge slots per label (fc_config.inc FC_MAXE): a basis file
      * whose states have more goes to the big build */
     if (basis)
         for (unsigned s = 0; s < basis->basis_states; s++)
@@ -138,7 +138,7 @@ static bool needs_big_variant(const fa_cparams *cp, const fa_wfa *basis)
     return cp->lc_min_level <= cp->images_level || cp->lc_max_level > 10 || cp->max_elements > 3
            || cp->second_domain_block || cp->check_for_underflow || cp->check_for_overflow || cp->full_search
            || (cp->lc_max_level - cp->lc_min_level + 1) * sy + dcs > FC_MAXCOEFF
-           /* aac snapshots beyond the default build's LDS pool (frame_coder.hip SNAP_POOL16; one per
+           /* aac snapshots beyond the default build's LDS pool (fc_lds.inc SNAP_POOL16; one per
             * depth + one per block level with children): the big build parks them in HBM */
            || (cp->level - cp->lc_min_level + 3 + cp->lc_max_level - cp->lc_min_level)
               * ((32 + 2 * ((cp->lc_max_level - cp->lc_min_level + 1) * sy + dcs) + 15) / 16) > FC_SNAP16_WIDE;
@@ -1460,7 +1460,7 @@ static void *core1_stage(unsigned n, fa_job *jobs)
             if (elig && S->lender0 < 0) {
                 S->lender0 = (int) k; S->lenders = 1;
                 S->qL = fs.L; S->qP = fs.P; S->qPA = fs.PA; S->qbig = fs.big; S->qtri = fs.tri;
-                /* workgroups the chip holds at once: frame_coder.hip FC_WG_PER_CU of the build the
+                /* workgroups the chip holds at once: fc_config.inc FC_WG_PER_CU of the build the
                  * launch will use (wide build for P > 3072: one per CU) */
                 S->lender_cap = (size_t) cus * frames_per_cu(fs.big, fs.P > 12 * 256 || fs.wide_only || fs.hm || fs.gm);
                 if (fa_knob("FIASCO_AMD_QUEUE_SLABS") && atoi(fa_knob("FIASCO_AMD_QUEUE_SLABS")) > 0)

@@ -119,7 +119,7 @@ typedef struct DevFrame {
                             * the kernel --, + one row of slack) */
     int      PA;           /* pitch / capacity of the automaton arrays (all states, PA >= P) */
     int      color;        /* 3 bands Y, Cb, Cr (codec/coder.c:775-800) */
-    int      chroma_sparse; /* chroma bands: <sub-block, state> entries only for the states somebody reads (frame_coder.hip,
+    int      chroma_sparse; /* chroma bands: <sub-block, state> entries only for the states somebody reads (fc_tables.inc,
                             * chroma_need_block); 0: the full tables (FIASCO_AMD_CHROMA_FULL, tests) */
     int      chroma_cl_cap; /* tests (FIASCO_AMD_CLMAX): a chroma block with more needed states than this takes the full tables, as
                             * one with more than the build's FC_CLMAX (the capacity of Sh::cl) does; 0 = FC_CLMAX */
@@ -285,7 +285,8 @@ typedef struct FcSpecCtl {
     unsigned slot_seq[FC_SPEC_W];   /* seq + 1 once the checkpoint of block `seq` is complete, 0 while written */
     unsigned verdict[FC_SPEC_W];    /* (seq + 1) << 11 | verifier (role - T - 1) << 8 | state ids the search used << 2 | code:
                                      * 1 the combination wins, 2 anything else, 3 the subdivision wins and the verifier's
-                                     * finished search waits in ITS result slot (frame_coder.hip, end of a verifier's task; spec_poll) */
+                                     * finished search waits in ITS result slot (frame_coder.hip, end of a verifier's task;
+                                     * fc_serial.inc, spec_poll) */
     /* statistics (chain) */
     unsigned long long n_tasks, n_confirmed, n_wrong, n_timeout, n_inline, t_wait;
     unsigned long long n_tab_used, n_tab_missed;      /* blocks whose tables came from a worker / were not there in time */
@@ -311,7 +312,7 @@ typedef struct FcSpecCtl {
      * each is a function of older rows, of the automaton rows of s and t and of the level-images_level images alone;
      * codec/ip.c:213-257 fixes the order of operations per ENTRY, not the order of entries -- and one CU's gather rate
      * bounds them.  app_H further workgroups of the frame (launched behind the chains / workers / verifiers of the
-     * launch, frame_coder.hip spec_append_helper) take the entries t with (t / B) mod (app_H + 1) == h + 1 of every
+     * launch, fc_spec.inc spec_append_helper) take the entries t with (t / B) mod (app_H + 1) == h + 1 of every
      * row the chain publishes: term lists of the new state -> release -> app_seq; helpers: acquire, build, release ->
      * app_done.  The chain builds its own share meanwhile and waits for app_seq * app_H arrivals -- bounded (app_wait): a
      * frame whose helpers do not answer fails with FC_ERR_COOP and is searched again without helpers (a helper that

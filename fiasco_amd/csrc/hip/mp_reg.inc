@@ -26,7 +26,7 @@
 struct Step0 { unsigned praw[KREG]; float draw[KREG], nraw[KREG]; };
 
 /* FC_SPEC, verifier: the candidates are the states below sh.gap_lo and those from sh.gap_hi on; the
- * ids in between are the chain's (frame_coder.hip, Sh).  Slots that lie inside the gap are not
+ * ids in between are the chain's (fc_lds.inc, Sh).  Slots that lie inside the gap are not
  * read at all, lanes inside it never become candidates. */
 #if FC_SPEC
 #define SPEC_DEADMASK(sh) const unsigned deadmask_ = (unsigned) __builtin_amdgcn_readfirstlane((int) (sh).deadmask);

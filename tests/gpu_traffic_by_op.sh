@@ -1,6 +1,6 @@
 #!/bin/bash
 # developer helper (GPU box, through gpurun): HBM traffic of the default kernel BY OPERATION.
-# The plain library and two builds that run one idempotent table operation twice (frame_coder.hip FC_DUP_OP;
+# The plain library and two builds that run one idempotent table operation twice (fc_config.inc FC_DUP_OP;
 # build them first:  tests/build_variant.sh dupinit "-DFC_DUP_OP=OP_INIT_RANGE";  tests/build_variant.sh dupappend
 # "-DFC_DUP_OP=OP_APPEND") run the 1024 x 1080p launch under rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes
 # (MI355X_MICROARCH.md, HBM section); the difference to the plain build is the operation's traffic.

@@ -4,10 +4,11 @@ tables: an inlined callee's instructions count for the callee), per assembly fun
 
 usage: tests/isa_lines.py [asm function substring] [extra hipcc flags ...]
 
-Compiles fiasco_amd/csrc/hip/frame_coder.hip with -gline-tables-only -save-temps into /tmp/fiasco_isa_lines, then walks
-the gfx950 assembly: every instruction belongs to the source line of the last `.loc`, a source line to the function
-whose definition starts last before it (definitions found by a regular expression: good enough for a budget).
-Output: per source function VALU / SALU / LDS / VMEM / waitcnt+barrier counts inside the chosen assembly function
+Compiles fiasco_amd/csrc/hip/frame_coder.hip (one translation unit with the fc_*.inc and mp_*.inc parts it includes)
+with -gline-tables-only -save-temps into /tmp/fiasco_isa_lines, then walks the gfx950 assembly: every instruction
+belongs to the source file and line of the last `.loc`, a source line to the function of that file whose definition
+starts last before it (definitions found by a regular expression: good enough for a budget).
+Output: per source file:function VALU / SALU / LDS / VMEM / waitcnt+barrier counts inside the chosen assembly function
 (default: the kernel itself, where the matching pursuit, its set-up and the partition search's callers are inlined).
 Used for profiles/r06_chain_budget.txt.
 """

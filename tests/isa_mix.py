@@ -3,10 +3,11 @@
 
 usage: tests/isa_mix.py [extra hipcc flags ...]      (default: the 256-thread default build's KFLAGS)
 
-Compiles fiasco_amd/csrc/hip/frame_coder.hip with -save-temps into /tmp/fiasco_isa_mix and counts, per
-function of the gfx950 assembly: VALU / SALU / LDS (ds_) / VMEM (global_, flat_, scratch_, buffer_)
-instructions, and the classes the round-3 verdict asked to budget: scratch_, flat_ vs global_, v_div_*,
-f64 arithmetic, 64-bit address arithmetic (v_lshlrev_b64, v_add_co / v_addc_co pairs, v_mad_u64_u32).
+Compiles fiasco_amd/csrc/hip/frame_coder.hip (one translation unit with the fc_*.inc and mp_*.inc parts it includes)
+with -save-temps into /tmp/fiasco_isa_mix and counts, per function of the gfx950 assembly: VALU / SALU / LDS (ds_)
+/ VMEM (global_, flat_, scratch_, buffer_) instructions, and the classes the round-3 verdict asked to budget: scratch_,
+flat_ vs global_, v_div_*, f64 arithmetic, 64-bit address arithmetic (v_lshlrev_b64, v_add_co / v_addc_co pairs,
+v_mad_u64_u32).
 The committed copy of its output is profiles/r04_isa_mix.txt.
 """
 import collections

@@ -111,7 +111,7 @@ def test_no_oracle_in_product():
             if f.endswith(".py") or f == "Makefile":       # build recipes and python plumbing
                 txt = open(os.path.join(dirpath, f), errors="ignore").read()
                 assert "oracle" not in txt, f
-            elif f.endswith((".c", ".cpp", ".hip")):        # sources: no include / link of it
+            elif f.endswith((".c", ".cpp", ".hip", ".inc")):  # sources: no include / link of it
                 txt = open(os.path.join(dirpath, f), errors="ignore").read()
                 assert "liboracle" not in txt and "oracle_core" not in txt, f
 
