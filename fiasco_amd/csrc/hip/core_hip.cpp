@@ -19,6 +19,7 @@
 #include <string.h>
 #include <stddef.h>
 #include <pthread.h>
+#include <algorithm>
 #include <utility>
 #include <vector>
 #include "fa_host.h"
@@ -34,6 +35,12 @@ extern "C" const char *fa_knob(const char *name)
 {
     const char *d = getenv("FIASCO_AMD_DEBUG");
     return d && *d && strcmp(d, "0") != 0 ? getenv(name) : nullptr;
+}
+/* a numeric switch: its value, or `d' when it is not set (callers check the range themselves) */
+static long long knob_int(const char *name, long long d)
+{
+    const char *e = fa_knob(name);
+    return e ? atoll(e) : d;
 }
 
 
@@ -61,34 +68,43 @@ static thread_local DevState *t_dev = &g_state0;
 #define g_l2     (t_dev->l2)
 #define g_l2_err (t_dev->l2_err)
 
-extern "C" void fc_launch(DevFrame *d_frames, unsigned n, unsigned nlend, unsigned long long *ring, unsigned *ctr,
+/* the kernel builds (frame_coder.hip, one object per build: Makefile FC_BUILDS) */
+typedef void launch_fn(DevFrame *d_frames, unsigned n, unsigned nlend, unsigned long long *ring, unsigned *ctr,
                        const unsigned *ptrmask, unsigned long long queue_wait_ticks, unsigned coopW, hipStream_t stream);
-extern "C" void fc_launch_big(DevFrame *d_frames, unsigned n, unsigned nlend, unsigned long long *ring, unsigned *ctr,
-                       const unsigned *ptrmask, unsigned long long queue_wait_ticks, unsigned coopW, hipStream_t stream);
-extern "C" void fc_launch_wide(DevFrame *d_frames, unsigned n, unsigned nlend, unsigned long long *ring, unsigned *ctr,
-                       const unsigned *ptrmask, unsigned long long queue_wait_ticks, unsigned coopW, hipStream_t stream);
-extern "C" void fc_launch_wide_tri(DevFrame *d_frames, unsigned n, unsigned nlend, unsigned long long *ring, unsigned *ctr,
-                       const unsigned *ptrmask, unsigned long long queue_wait_ticks, unsigned coopW, hipStream_t stream);
-extern "C" void fc_launch_big_wide(DevFrame *d_frames, unsigned n, unsigned nlend, unsigned long long *ring, unsigned *ctr,
-                       const unsigned *ptrmask, unsigned long long queue_wait_ticks, unsigned coopW, hipStream_t stream);
-/* the 512-thread big build with coefficient models of up to 512 symbols per context (frame_coder.h FC_HM) */
-extern "C" void fc_launch_big_hm(DevFrame *d_frames, unsigned n, unsigned nlend, unsigned long long *ring, unsigned *ctr,
-                       const unsigned *ptrmask, unsigned long long queue_wait_ticks, unsigned coopW, hipStream_t stream);
-/* ... and with the other models of the reference's registries (frame_coder.h FC_GM) */
-extern "C" void fc_launch_big_gm(DevFrame *d_frames, unsigned n, unsigned nlend, unsigned long long *ring, unsigned *ctr,
-                       const unsigned *ptrmask, unsigned long long queue_wait_ticks, unsigned coopW, hipStream_t stream);
+/* block-level speculation (frame_coder.h, FcSpecCtl): n frames with G workgroups and H append helpers each */
+typedef void spec_launch_fn(DevFrame *d_frames, DevFrame *d_vframes, unsigned n, unsigned G, unsigned H, hipStream_t stream);
+extern "C" launch_fn fc_launch, fc_launch_wide, fc_launch_big, fc_launch_big_wide, fc_launch_wide_tri, fc_launch_big_hm,
+                     fc_launch_big_gm;
+extern "C" spec_launch_fn fc_launch_spec, fc_launch_spec_wide;
+extern "C" unsigned fc_spec_slot_bytes(void), fc_spec_slot_bytes_wide(void), fc_spec_ctl_bytes(void);
+/* workgroups (= frames) of a kernel build that one CU holds at once, as the runtime computes it
+ * from the build's registers and LDS (frame_coder.hip FC_OCCUPANCY) */
+extern "C" int fc_occupancy(void), fc_occupancy_wide(void), fc_occupancy_big(void), fc_occupancy_big_wide(void),
+               fc_occupancy_spec(void);
 
-/* block-level speculation (frame_coder.h, FcSpecCtl): n frames with G workgroups each */
-extern "C" void fc_launch_spec(DevFrame *d_frames, DevFrame *d_vframes, unsigned n, unsigned G, unsigned H, hipStream_t stream);
-extern "C" unsigned fc_spec_slot_bytes(void);
-extern "C" unsigned fc_spec_ctl_bytes(void);
-extern "C" int fc_occupancy_spec(void);
-extern "C" void fc_launch_spec_wide(DevFrame *d_frames, DevFrame *d_vframes, unsigned n, unsigned G, unsigned H, hipStream_t stream);
-extern "C" unsigned fc_spec_slot_bytes_wide(void);
+/* The nine kernel builds in the order a launch orders its frames and starts them.  wide: 1024 threads per
+ * workgroup (default geometry) or 512 (big); tri: triangular Gram tables; hm, gm: the big build with larger
+ * coefficient models / the other model registries; spec: several workgroups per frame.  Only the builds up to
+ * B_WIDE_TRI take frames that borrow a slab (queue_eligible). */
+enum Build { B_DEFAULT, B_WIDE, B_BIG, B_BIG_WIDE, B_WIDE_TRI, B_BIG_HM, B_BIG_GM, B_SPEC, B_SPEC_WIDE, N_BUILDS };
+struct BuildInfo {
+    launch_fn      *launch;         /* one workgroup per frame, or the frame queue */
+    spec_launch_fn *spec_launch;    /* the speculating builds instead */
+    int             stats_slot;     /* fiasco_amd_stats.frames_by_build[]; -1: counted in spec_frames */
+    int           (*occupancy)(void);   /* what frames_per_cu() answers for frames of the build */
+};
+static const BuildInfo k_build[N_BUILDS] = {
+    { fc_launch,          nullptr,              0, fc_occupancy },
+    { fc_launch_wide,     nullptr,              1, fc_occupancy_wide },
+    { fc_launch_big,      nullptr,              2, fc_occupancy_big },
+    { fc_launch_big_wide, nullptr,              3, fc_occupancy_big_wide },
+    { fc_launch_wide_tri, nullptr,              4, fc_occupancy_wide },
+    { fc_launch_big_hm,   nullptr,              3, fc_occupancy_big_wide },
+    { fc_launch_big_gm,   nullptr,              3, fc_occupancy_big_wide },
+    { nullptr,            fc_launch_spec,      -1, fc_occupancy },
+    { nullptr,            fc_launch_spec_wide, -1, fc_occupancy_wide },
+};
 
-/* which of the two kernel builds (frame_coder.hip) encodes a job: the default build covers
- * the CLI's -z 0 geometry, the big one block levels 4..12, up to 5 vectors and the
- * second-domain retry */
 /* A basis the rows inside DevFrame cannot hold: more than FC_MAXBASIS states, or a label with more than
  * MAXEDGES edges (data/medium.fco, large.fco: the reference's append_edge runs on into the next row,
  * fa_wfa_append_edge).  It travels as the memory image of its rows (DevFrame.bx); big kernel builds only. */
@@ -122,6 +138,8 @@ static bool needs_gm_variant(const fa_job *job)
            || (delta_used && (cp->d_pool_kind != FA_POOL_RLE || cp->d_coeff_kind != FA_COEFF_ADAPTIVE));
 }
 
+/* the default builds cover the CLI's -z 0 geometry, the big ones block levels 4..12, up to 5 vectors and the
+ * second-domain retry */
 static bool needs_big_variant(const fa_cparams *cp, const fa_wfa *basis)
 {
     if (needs_hm_variant(cp)) return true;
@@ -227,26 +245,22 @@ extern "C" int fiasco_amd_spec_workgroups(unsigned frames, int cus, int big_fram
 }
 extern "C" const char *fa_core_name(void) { return "hip-gfx950"; }
 
-/* workgroups (= frames) of a kernel build that one CU holds at once, as the runtime computes it
- * from the build's registers and LDS (frame_coder.hip FC_OCCUPANCY) */
-extern "C" int fc_occupancy(void);
-extern "C" int fc_occupancy_wide(void);
-extern "C" int fc_occupancy_big(void);
-extern "C" int fc_occupancy_big_wide(void);
-static size_t frames_per_cu(bool big, bool wide)
-{
-    static int cache[4] = { 0, 0, 0, 0 };
-    const int i = (big ? 2 : 0) + (wide ? 1 : 0);
-    if (!cache[i]) {
-        cache[i] = i == 0 ? fc_occupancy() : i == 1 ? fc_occupancy_wide() : i == 2 ? fc_occupancy_big() : fc_occupancy_big_wide();
-        if (cache[i] < 1) cache[i] = 1;
-    }
-    return (size_t) cache[i];
-}
-
 extern "C" void fiasco_amd_release_memory(void);
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+/* a device buffer (or pinned host buffer) of at least `need' elements: kept while it is large enough, else
+ * allocated afresh; false, with the buffer empty, when there is no room (each caller decides what that means) */
+template <typename T> static bool grow_buffer(T *&p, size_t &n, size_t need, bool pinned = false)
+{
+    if (need <= n) return true;
+    if (p) (void) (pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr; n = 0;
+    if ((pinned ? hipHostMalloc((void **) &p, need * sizeof(T), hipHostMallocDefault) : hipMalloc((void **) &p, need * sizeof(T)))
+        != hipSuccess) { p = nullptr; (void) hipGetLastError(); return false; }
+    n = need;
+    return true;
+}
 
 /* ------------------------------------------------------------------ log2 self test
  *
@@ -259,7 +273,6 @@ static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
  * exponent range and compares the doubles bit for bit with glibc's on the host. */
 #include <fcntl.h>
 #include <math.h>
-#include <pthread.h>
 #include <sys/stat.h>
 #include <sys/types.h>
 #include <unistd.h>
@@ -752,9 +765,6 @@ struct FrameSlot {
     const fa_image *src = nullptr;
 };
 
-struct Staged;
-static inline const fa_image *slot_image(const Staged *S, const FrameSlot &fs);
-
 struct Staged {
     unsigned n = 0;
     fa_job  *jobs = nullptr;
@@ -824,6 +834,48 @@ struct Staged {
     size_t    spec_first[2] = { 0, 0 }, spec_n[2] = { 0, 0 };    /* ... per workgroup width (256, 1024 threads) */
 };
 
+/* The kernel build of a frame in the next launch.  The wide builds take launches with no more frames than CUs
+ * (`few': the chip cannot be filled with frames anyway, give each frame more lanes) and frames beyond the
+ * 256-thread build's register-resident scan (more than 3072 states: 4K) or its LDS pools. */
+static Build build_of(const Staged *S, const FrameSlot &fs, bool few)
+{
+    const bool wide_only = fs.P > 12 * 256 || fs.wide_only;
+    if (fs.spec && S->specG >= 2 && !fs.borrow && !fs.tri && !fs.big && fs.P <= 12 * 1024)
+        return wide_only ? B_SPEC_WIDE : B_SPEC;
+    if (fs.gm) return B_BIG_GM;
+    if (fs.hm) return B_BIG_HM;
+    if (fs.tri) return B_WIDE_TRI;
+    return (Build) ((fs.big ? B_BIG : B_DEFAULT) + (few || wide_only ? 1 : 0));
+}
+
+/* workgroups (= frames) that one CU holds at once of the build of a frame's geometry and width -- what sizes the
+ * slabs and the frame queue at staging, before a launch knows its batch: a speculating or triangular-table frame
+ * counts as the plain build of its width */
+static size_t frames_per_cu(const FrameSlot &fs)
+{
+    static int cache[N_BUILDS];
+    const Build b = fs.gm ? B_BIG_GM : fs.hm ? B_BIG_HM
+                  : (Build) ((fs.big ? B_BIG : B_DEFAULT) + (fs.P > 12 * 256 || fs.wide_only ? 1 : 0));
+    if (!cache[b]) {
+        cache[b] = k_build[b].occupancy();
+        if (cache[b] < 1) cache[b] = 1;
+    }
+    return (size_t) cache[b];
+}
+
+static inline const fa_image *slot_image(const Staged *S, const FrameSlot &fs)
+{
+    return fs.src ? fs.src : S->jobs[fs.job].image;
+}
+
+/* blocks of the largest block level that cover the frame */
+static size_t top_blocks(const fa_job *job)
+{
+    const fa_cparams *cp = &job->cp;
+    const unsigned bw = fa_width_of_level(cp->lc_max_level), bh = fa_height_of_level(cp->lc_max_level);
+    return (size_t) ((job->image->width + bw - 1) / bw) * ((job->image->height + bh - 1) / bh);
+}
+
 /* A launch that leaves workgroup slots of the chip free gives its frames several workgroups each
  * (frame_coder.h, FcSpecCtl).  Which frames: gray intra frames of the default geometry whose state
  * capacity -- with room for the verifiers' id ranges -- still fits the 256-thread build.
@@ -831,8 +883,8 @@ struct Staged {
 /* of the G workgroups of a frame: the chain, T table workers, G - 1 - T verifiers */
 static int spec_workers(int G)
 {
-    const char *e = fa_knob("FIASCO_AMD_SPEC_T");           /* experiments */
-    if (e && atoi(e) >= 0 && atoi(e) < G - 1) return atoi(e);
+    const long long t = knob_int("FIASCO_AMD_SPEC_T", -1);          /* experiments */
+    if (t >= 0 && t < G - 1) return (int) t;
     return G >= 6 ? 2 : G >= 4 ? 1 : 0;
 }
 
@@ -858,22 +910,23 @@ static void spec_block_list(const DevFrame &F, std::vector<uint16_t> &out)
     }
 }
 
-static int spec_policy(size_t frames, int cus, bool big_frames, bool narrow_only, int occ);
-
 /* Append helpers per frame (frame_coder.h FcSpecCtl.app_*): further workgroups of a speculating frame that build their
  * shares of every Gram row the chain appends.  For the 1024-thread speculating build (frames beyond 3072 states: 4K),
  * whose launches give a frame a CU per workgroup and leave the rest of the chip empty -- BASELINE config 4 as written
  * puts 8 frames on a GPU: 8 x 8 workgroups on 256 CUs -- and whose rows are long (up to 10 passes of the 1024 lanes).
  * Three where the chip has CUs left for them; fewer than 2 are not worth the hand-off.  A function of its arguments
- * alone (fiasco_amd_spec_append_helpers); FIASCO_AMD_SPEC_APP=<H> (tests, experiments) asks for H. */
+ * alone (fiasco_amd_spec_append_helpers); FIASCO_AMD_SPEC_APP=<H> (tests, experiments) asks for H at the launch
+ * (spec_helpers). */
+static size_t spec_app_room(size_t frames, int cus, int G, int occ)
+{
+    if (occ < 1) occ = 1;
+    const size_t room = (size_t) cus * (size_t) occ / frames;       /* workgroups per frame that can be resident */
+    return room > (size_t) G ? room - (size_t) G : 0;
+}
 static int spec_app_policy(size_t frames, int cus, int G, bool wide_build, int occ)
 {
     if (!frames || G < 2 || cus < 1) return 0;
-    if (occ < 1) occ = 1;
-    const size_t room = (size_t) cus * (size_t) occ / frames;       /* workgroups per frame that can be resident */
-    size_t H = room > (size_t) G ? room - (size_t) G : 0;
-    const char *e = fa_knob("FIASCO_AMD_SPEC_APP");
-    if (e) { const size_t want = (size_t) (atoi(e) > 0 ? atoi(e) : 0); return (int) (want < H ? want : H); }
+    size_t H = spec_app_room(frames, cus, G, occ);
     if (!wide_build) {
         /* the 256-thread build (rows of up to 3072 entries, 12 passes of the lanes): three helpers while the launch
          * stays below 1.5 workgroups per CU -- 1080p: 1 frame 0.367 -> 0.343 s, 16 frames 39.4 -> 42.7, 32 frames 75 -> 80
@@ -943,11 +996,6 @@ static int spec_policy(size_t frames, int cus, bool big_frames, bool narrow_only
     return G >= 3 ? (int) G : 0;
 }
 
-static inline const fa_image *slot_image(const Staged *S, const FrameSlot &fs)
-{
-    return fs.src ? fs.src : S->jobs[fs.job].image;
-}
-
 static void fill_frame(FrameSlot &fs, const fa_job *job)
 {
     const fa_cparams *cp = &job->cp;
@@ -979,7 +1027,7 @@ static void fill_frame(FrameSlot &fs, const fa_job *job)
     F.gram_ls = fs.tri ? (unsigned) ((size_t) fs.P * (fs.P + 1) / 2 + fs.P) : (unsigned) fs.P * (unsigned) fs.P;
     F.color = job->image->color ? 1 : 0;
     /* pools whose chroma list is not cut down (uniform, rle-no-chroma ...: FC_GM build) search every state: full tables */
-    F.chroma_cl_cap = fa_knob("FIASCO_AMD_CLMAX") ? atoi(fa_knob("FIASCO_AMD_CLMAX")) : 0;     /* tests: the overflow path of Sh::cl */
+    F.chroma_cl_cap = (int) knob_int("FIASCO_AMD_CLMAX", 0);     /* tests: the overflow path of Sh::cl */
     F.chroma_sparse = !fa_knob("FIASCO_AMD_CHROMA_FULL") && (cp->pool_kind == FA_POOL_RLE || cp->pool_kind == FA_POOL_ADAPTIVE || cp->pool_kind == FA_POOL_BASIS);
     F.chroma_max = (int) cp->chroma_max_states;
     F.chroma_decrease = cp->chroma_decrease;
@@ -1061,7 +1109,7 @@ static void fill_frame(FrameSlot &fs, const fa_job *job)
     F.slab_base = base; F.slab_bytes = L.total;
 }
 
-/* allocate the slab of one frame for capacity fs.P and upload its pixel plane */
+/* the slab layout of one frame for capacity fs.P */
 static void slot_layout(Staged *S, FrameSlot &fs)
 {
     const fa_job *job = &S->jobs[fs.job];
@@ -1074,8 +1122,10 @@ static void slot_layout(Staged *S, FrameSlot &fs)
     int NI = (int) fa_size_of_tree(cp->images_level);
     size_t npix = (size_t) job->image->width * job->image->height;
     const int bands = job->image->color ? 3 : 1;
+    /* states a prediction attempt can displace: the nodes of a subtree from the largest
+     * predicted level down to the smallest block level */
     int max_save = 0;
-    const int inter = job->frame_type;
+    const int inter = job->frame_type;                 /* 0 I, 1 P, 2 B */
     if (cp->prediction || inter) {
         int span = (int) cp->p_max_level - (int) cp->lc_min_level + 1;
         max_save = 1 << (span < 1 ? 1 : span > 9 ? 9 : span);
@@ -1101,8 +1151,6 @@ static bool queue_layout(const Staged *S, const FrameSlot &fs)
     return fs.P == S->qP && fs.PA == S->qPA && fs.big == S->qbig && fs.tri == S->qtri
            && memcmp(&fs.L, &S->qL, sizeof(Layout)) == 0;
 }
-
-static void fill_frame(FrameSlot &fs, const fa_job *job);
 
 /* a frame without a slab: descriptor laid out for the slab of the queue's first frame (the
  * workgroup that takes it re-bases the pointers), pixel planes in the queue's pixel buffer */
@@ -1138,38 +1186,45 @@ static int stage_borrower(Staged *S, FrameSlot &fs, size_t frames_left)
     return 1;
 }
 
+/* the planes of a reference frame into the slab at `off': from the copy the device decoder left on this device
+ * (fa_image.dev, frame_decoder.inc), else from the host planes */
+static bool upload_reference(Staged *S, const FrameSlot &fs, const fa_image *ref, size_t off, int here)
+{
+    const fa_job *job = &S->jobs[fs.job];
+    const size_t npix = (size_t) job->image->width * job->image->height;
+    const int bands = job->image->color ? 3 : 1;
+    for (int b = 0; b < bands; b++)
+        if ((ref->dev && ref->dev_id == here
+             ? hipMemcpyAsync(fs.base + off + (size_t) b * npix * 2, (const int16_t *) ref->dev + (size_t) b * npix, npix * 2,
+                              hipMemcpyDeviceToDevice, S->stream)
+             : hipMemcpyAsync(fs.base + off + (size_t) b * npix * 2, ref->pixels[b], npix * 2,
+                              hipMemcpyHostToDevice, S->stream)) != hipSuccess)
+            return false;
+    return true;
+}
+
+/* allocate the slab of one frame for capacity fs.P and upload its inputs */
 static int stage_slot(Staged *S, FrameSlot &fs)
 {
     fa_job *job = &S->jobs[fs.job];
     const fa_cparams *cp = &job->cp;
-    int il = (int) cp->images_level;
-    int low = cp->lc_min_level < cp->images_level;
-    int NL = (int) (cp->lc_max_level - (low ? cp->lc_min_level : cp->images_level) + 1);
-    int NS = (int) fa_size_of_tree(cp->products_level);
-    int NA = 1 << (cp->lc_max_level - cp->images_level);
-    int NI = (int) fa_size_of_tree(cp->images_level);
-    size_t npix = (size_t) job->image->width * job->image->height;
+    const size_t npix = (size_t) job->image->width * job->image->height;
     const int bands = job->image->color ? 3 : 1;
-    /* states a prediction attempt can displace: the nodes of a subtree from the largest
-     * predicted level down to the smallest block level */
-    int max_save = 0;
-    const int inter = job->frame_type;                 /* 0 I, 1 P, 2 B */
-    if (cp->prediction || inter) {
-        int span = (int) cp->p_max_level - (int) cp->lc_min_level + 1;
-        max_save = 1 << (span < 1 ? 1 : span > 9 ? 9 : span);
-    }
-    fs.L = make_layout(fs.P, fs.PA, NL, NS, NA, NI, il, low, npix * bands, max_save, inter,
-                       (int) cp->p_max_level - (int) cp->p_min_level + 1, job->image->color ? 1 : 0, fs.tri, fs.hm || fs.gm,
-                       fs.gm ? (int) cp->limit_states : 0);
+    slot_layout(S, fs);
     fs.base = slab_acquire(fs.L.total, &fs.bytes);
     /* developer aid: FIASCO_AMD_POISON=<byte> fills the slab first -- the kernel must write every
      * cell before it reads it, whatever an earlier frame left there */
     if (fs.base && fa_knob("FIASCO_AMD_POISON"))
-        (void) hipMemsetAsync(fs.base, atoi(fa_knob("FIASCO_AMD_POISON")), fs.L.total, S->stream);
+        (void) hipMemsetAsync(fs.base, (int) knob_int("FIASCO_AMD_POISON", 0), fs.L.total, S->stream);
     if (!fs.base) {
         snprintf(job->errmsg, sizeof job->errmsg, "out of HBM: frame needs %.2f GiB", fs.L.total / 1073741824.0);
         return 0;
     }
+    auto give_up = [&](const char *msg) {
+        snprintf(job->errmsg, sizeof job->errmsg, "%s", msg);
+        slab_release(fs.base, fs.bytes); fs.base = nullptr;
+        return 0;
+    };
     fill_frame(fs, job);
     const bool hmx = fs.hm || fs.gm;              /* the FC_GM build has the FC_HM build's model sizes */
     const int maxsym = hmx ? FC_MAXSYM_HM : FC_MAXSYM_STD;
@@ -1185,58 +1240,28 @@ static int stage_slot(Staged *S, FrameSlot &fs)
     if (fs.ext_pix) fs.F.pix16 = fs.ext_pix;       /* the planes live outside the slab already */
     for (int b = 0; b < bands && !fs.ext_pix; b++)
         if (hipMemcpyAsync(fs.base + fs.L.pix16 + (size_t) b * npix * 2, slot_image(S, fs)->pixels[b], npix * 2,
-                           hipMemcpyHostToDevice, S->stream) != hipSuccess) {
-            snprintf(job->errmsg, sizeof job->errmsg, "HIP error: pixel upload failed");
-            slab_release(fs.base, fs.bytes); fs.base = nullptr;
-            return 0;
-        }
-    /* reference frames the device decoder left on this device (fa_image.dev, frame_decoder.inc) are taken from
-     * there; anything else comes from the host planes */
+                           hipMemcpyHostToDevice, S->stream) != hipSuccess)
+            return give_up("HIP error: pixel upload failed");
     int here = -1;
     if (hipGetDevice(&here) != hipSuccess) { (void) hipGetLastError(); here = -1; }
-    if (job->frame_type != FA_I_FRAME && job->past)
-        for (int b = 0; b < bands; b++)
-            if ((job->past->dev && job->past->dev_id == here
-                 ? hipMemcpyAsync(fs.base + fs.L.past + (size_t) b * npix * 2, (const int16_t *) job->past->dev + (size_t) b * npix, npix * 2,
-                                  hipMemcpyDeviceToDevice, S->stream)
-                 : hipMemcpyAsync(fs.base + fs.L.past + (size_t) b * npix * 2, job->past->pixels[b], npix * 2,
-                                  hipMemcpyHostToDevice, S->stream)) != hipSuccess) {
-                snprintf(job->errmsg, sizeof job->errmsg, "HIP error: reference frame upload failed");
-                slab_release(fs.base, fs.bytes); fs.base = nullptr;
-                return 0;
-            }
-    if (job->frame_type == FA_B_FRAME && job->future)
-        for (int b = 0; b < bands; b++)
-            if ((job->future->dev && job->future->dev_id == here
-                 ? hipMemcpyAsync(fs.base + fs.L.future + (size_t) b * npix * 2, (const int16_t *) job->future->dev + (size_t) b * npix, npix * 2,
-                                  hipMemcpyDeviceToDevice, S->stream)
-                 : hipMemcpyAsync(fs.base + fs.L.future + (size_t) b * npix * 2, job->future->pixels[b], npix * 2,
-                                  hipMemcpyHostToDevice, S->stream)) != hipSuccess) {
-                snprintf(job->errmsg, sizeof job->errmsg, "HIP error: reference frame upload failed");
-                slab_release(fs.base, fs.bytes); fs.base = nullptr;
-                return 0;
-            }
+    if ((job->frame_type != FA_I_FRAME && job->past && !upload_reference(S, fs, job->past, fs.L.past, here))
+        || (job->frame_type == FA_B_FRAME && job->future && !upload_reference(S, fs, job->future, fs.L.future, here)))
+        return give_up("HIP error: reference frame upload failed");
     if (job->ycol_carry) {                 /* [cap][2] on the host, [2][PA] on the device */
         const fa_wfa *w = job->wfa;
         fs.ycol_host.assign((size_t) 2 * fs.PA, 0);
         for (unsigned s = 0; s < w->cap && s < (unsigned) fs.PA; s++)
             for (int l = 0; l < 2; l++) fs.ycol_host[(size_t) l * fs.PA + s] = w->y_column[s * 2 + l];
         if (hipMemcpyAsync(fs.base + fs.L.ycol0, fs.ycol_host.data(), fs.ycol_host.size(),
-                           hipMemcpyHostToDevice, S->stream) != hipSuccess) {
-            snprintf(job->errmsg, sizeof job->errmsg, "HIP error: y_column upload failed");
-            slab_release(fs.base, fs.bytes); fs.base = nullptr;
-            return 0;
-        }
+                           hipMemcpyHostToDevice, S->stream) != hipSuccess)
+            return give_up("HIP error: y_column upload failed");
     }
     if (fs.F.lginv) {                      /* log2 (1.0 / n) as THIS host's libm gives it: uniform_bits, codec/domain-pool.c:592-615 */
         const unsigned nmax = cp->limit_states + 1;
         fs.lginv_host.assign(nmax + 1, 0.0);
         for (unsigned k = 1; k <= nmax; k++) fs.lginv_host[k] = log2(1.0 / k);
-        if (hipMemcpyAsync(fs.base + fs.L.lginv, fs.lginv_host.data(), fs.lginv_host.size() * 8, hipMemcpyHostToDevice, S->stream) != hipSuccess) {
-            snprintf(job->errmsg, sizeof job->errmsg, "HIP error: table upload failed");
-            slab_release(fs.base, fs.bytes); fs.base = nullptr;
-            return 0;
-        }
+        if (hipMemcpyAsync(fs.base + fs.L.lginv, fs.lginv_host.data(), fs.lginv_host.size() * 8, hipMemcpyHostToDevice, S->stream) != hipSuccess)
+            return give_up("HIP error: table upload failed");
     }
     if (fs.F.bx) {                         /* the rows of a long basis, as they lie in the host's memory (DevFrame.bx) */
         const fa_wfa *w = job->wfa;
@@ -1249,11 +1274,8 @@ static int stage_slot(Staged *S, FrameSlot &fs)
         float *bw = (float *) (b + 4 + 2 * nb);
         int16_t *bi = (int16_t *) (b + 4 + 2 * nb + nr);
         for (unsigned k = 0; k < nr; k++) { bi[k] = k < 12 * nb ? w->into[k] : (int16_t) FA_NO_EDGE; bw[k] = k < 12 * nb ? w->weight[k] : 0.0f; }
-        if (hipMemcpyAsync(fs.base + fs.L.bx, b, fs.bx_host.size() * 4, hipMemcpyHostToDevice, S->stream) != hipSuccess) {
-            snprintf(job->errmsg, sizeof job->errmsg, "HIP error: basis upload failed");
-            slab_release(fs.base, fs.bytes); fs.base = nullptr;
-            return 0;
-        }
+        if (hipMemcpyAsync(fs.base + fs.L.bx, b, fs.bx_host.size() * 4, hipMemcpyHostToDevice, S->stream) != hipSuccess)
+            return give_up("HIP error: basis upload failed");
     }
     fs.staged = true;
     return 1;
@@ -1269,13 +1291,8 @@ static void core1_unstage(void *h)
     }
     for (size_t k = 0; k < S->slots.size(); k++)
         if (S->slots[k].base) slab_release(S->slots[k].base, S->slots[k].bytes);
-    if (S->d_frames) (void) hipFree(S->d_frames);
-    if (S->qpix) (void) hipFree(S->qpix);
-    if (S->d_ring) (void) hipFree(S->d_ring);
-    if (S->d_queue) (void) hipFree(S->d_queue);
-    if (S->d_ptrmask) (void) hipFree(S->d_ptrmask);
-    if (S->d_vframes) (void) hipFree(S->d_vframes);
-    if (S->d_spec) (void) hipFree(S->d_spec);
+    for (void *p : std::initializer_list<void *>{ S->d_frames, S->qpix, S->d_ring, S->d_queue, S->d_ptrmask, S->d_vframes, S->d_spec })
+        if (p) (void) hipFree(p);
     if (S->cstream) { (void) hipStreamSynchronize(S->cstream); (void) hipStreamDestroy(S->cstream); }
     for (int i = 0; i < 2; i++) if (S->d_pack[i]) (void) hipFree(S->d_pack[i]);
     if (S->pinned) (void) hipHostFree(S->pinned);
@@ -1287,6 +1304,146 @@ static void core1_unstage(void *h)
     if (S->ev1) (void) hipEventDestroy(S->ev1);
     if (S->stream) (void) hipStreamDestroy(S->stream);
     delete S;
+}
+
+/* the slot of job i: its kernel build's geometry and the first guess of its state capacity */
+static FrameSlot first_guess(const Staged *S, unsigned i)
+{
+    const fa_job *job = &S->jobs[i];
+    const fa_cparams *cp = &job->cp;
+    /* one state per bintree node above the largest block level (2 x #blocks) ... measured need at -q 20 is
+     * ~1.3 x #blocks */
+    const size_t blocks = top_blocks(job);
+    size_t guess = blocks + blocks * 3 / 8 + 64;
+    /* predicted frames: the residual of a predicted block subdivides where the block itself would not --
+     * 720p colour P frames with --prediction end with 2.0 .. 2.3 table states per block (config 5) */
+    if (job->frame_type != FA_I_FRAME) guess = blocks * 5 / 2 + 64;
+    /* tests / experiments: FIASCO_AMD_CAP_GUESS=<states> forces the first guess (a frame that
+     * outgrows it is encoded again with 1.5 x the capacity, frame_outcome) */
+    const long long forced = knob_int("FIASCO_AMD_CAP_GUESS", 0);
+    if (forced > 0) guess = (size_t) forced;
+    /* what frames of this kind needed before (cap_hint_put): 1/16 on top, frames of a sequence drift */
+    int hintP = 0, hintPA = 0;
+    if (forced <= 0 && !fa_knob("FIASCO_AMD_NO_CAP_HINT")) cap_hint_get(job, &hintP, &hintPA);
+    if ((size_t) hintP + hintP / 16 + 32 > guess) guess = (size_t) hintP + hintP / 16 + 32;
+    if (guess > cp->limit_states) guess = cp->limit_states;
+    FrameSlot fs;
+    fs.job = (int) i;
+    fs.P = (int) align_up(guess, 64);
+    fs.big = needs_big_variant(cp, job->wfa) || job->frame_type != FA_I_FRAME
+             /* a chroma dictionary of more than 63 states: the list scan of the big builds (mp_steps_list_global) */
+             || (job->image->color && cp->chroma_max_states > 63);
+    fs.hm = needs_hm_variant(cp);
+    fs.gm = needs_gm_variant(job) || fa_knob("FIASCO_AMD_FORCE_GM") != nullptr;     /* (tests: every frame through the FC_GM build) */
+    if (fs.gm) fs.big = true;
+    fs.wide_only = !fs.big && needs_wide_variant(cp);
+    if (S->specG && !fs.big) {
+        /* the 256-thread build up to 3072 states, the 1024-thread one (4K; frames beyond the narrow
+         * build's LDS pools) up to 12288 */
+        const size_t withids = align_up(guess + (size_t) (S->specG - 1 - spec_workers(S->specG)) * FC_SPEC_TEMPS, 64);
+        if (withids <= 12 * 1024 && withids <= align_up(cp->limit_states, 64)) { fs.spec = true; fs.P = (int) withids; }
+    }
+    /* tests: the triangular layout (chosen by fit_hbm for HBM-bound batches) for every default-geometry frame */
+    if (!fs.big && fa_knob("FIASCO_AMD_FORCE_TRI")) fs.tri = true;
+    /* colour: the two chroma bands add auxiliary states (no tables) */
+    const size_t cap = align_up(cp->limit_states, 64);
+    fs.PA = job->image->color ? (int) (3 * (size_t) fs.P > cap ? cap : 3 * (size_t) fs.P) : fs.P;
+    if ((size_t) hintPA + hintPA / 16 + 32 > (size_t) fs.PA) {
+        const size_t want = align_up((size_t) hintPA + hintPA / 16 + 32, 64);
+        fs.PA = (int) (want > cap ? cap : want);
+    }
+    if (fs.PA < fs.P) fs.PA = fs.P;
+    if (hintP) { fs.floorP = hintP + hintP / 16 + 32; fs.floorPA = hintPA + hintPA / 16 + 32; }
+    return fs;
+}
+
+/* HBM-bound batches (4K: a slab is 3 GB, 97 % of it the Gram tables, quadratic in the state capacity): when the
+ * slabs the chip could keep busy do not fit, the frames take the triangular Gram tables, then the capacity guess
+ * drops from 1.375 to 1.15 states per block of the largest block level -- a third more frames in flight; a frame
+ * that outgrows it is encoded again with 1.5 x the capacity (frame_outcome).  A batch that will queue for slabs
+ * gets the pixel buffer of the queue's frames first. */
+static void fit_hbm(Staged *S)
+{
+    FrameSlot probe = S->slots[0];
+    slot_layout(S, probe);
+    size_t free_b = 0, total_b = 0, pooled = 0;
+    for (size_t i = 0; i < g_free.size(); i++) pooled += g_free[i].bytes;
+    size_t want = S->slots.size();
+    const size_t resident = (size_t) S->ncu * frames_per_cu(probe);
+    if (want > resident) want = resident;
+    const bool hbm_bound = hipMemGetInfo(&free_b, &total_b) == hipSuccess && probe.L.total * want > free_b + pooled;
+    if ((hbm_bound || S->slots.size() > resident) && queue_eligible(S, probe)) {
+        /* the pixel planes of the frames that will queue for a slab: set aside before the slabs
+         * take what HBM has (when HBM is the limit nobody knows yet how many slabs will fit) */
+        const fa_image *im = S->jobs[probe.job].image;
+        const size_t need = align_up((size_t) im->width * im->height * (im->color ? 3 : 1) * 2, 256);
+        const size_t frames = hbm_bound ? S->slots.size() : S->slots.size() - resident;
+        if (hipMalloc((void **) &S->qpix, need * frames) == hipSuccess) { S->qpix_bytes = need * frames; S->qpix_used = 0; }
+        else { S->qpix = nullptr; (void) hipGetLastError(); }
+    }
+    if (!hbm_bound) return;
+    /* first remedy: the triangular Gram tables -- half the slab; the kernel build that reads them exists for the
+     * default geometry at the wide workgroup (frames with more than 3072 states: 4K), where memory is what keeps
+     * CUs idle */
+    for (size_t k = 0; k < S->slots.size(); k++) {
+        FrameSlot &fs = S->slots[k];
+        if (!fs.big && fs.P > 12 * 256) fs.tri = true;
+    }
+    FrameSlot probe2 = S->slots[0];
+    slot_layout(S, probe2);
+    if (probe2.L.total * want <= free_b + pooled) return;
+    /* then the tight capacity */
+    for (size_t k = 0; k < S->slots.size(); k++) {
+        FrameSlot &fs = S->slots[k];
+        const fa_job *job = &S->jobs[fs.job];
+        const fa_cparams *cp = &job->cp;
+        const size_t blocks = top_blocks(job);
+        size_t tight = align_up(blocks + blocks * 3 / 20 + 64, 64);
+        if ((size_t) fs.floorP > tight) tight = align_up((size_t) fs.floorP, 64);   /* never below a known need */
+        if (tight > cp->limit_states) tight = align_up(cp->limit_states, 64);
+        if ((size_t) fs.P <= tight || fs.spec) continue;
+        const size_t cap = align_up(cp->limit_states, 64);
+        fs.P = (int) tight;
+        fs.PA = job->image->color ? (int) (3 * tight > cap ? cap : 3 * tight) : fs.P;
+        if ((size_t) fs.floorPA > (size_t) fs.PA) fs.PA = (int) (align_up((size_t) fs.floorPA, 64) > cap ? cap : align_up((size_t) fs.floorPA, 64));
+        if (fs.PA < fs.P) fs.PA = fs.P;
+    }
+}
+
+/* Stage the frames.  Every frame gets a slab of its own until the device is full -- as many frames of one layout
+ * as the chip runs workgroups at once, or as HBM holds; the frames after that join the FRAME QUEUE of that layout
+ * (no slab: whichever workgroup finishes its frame takes the next one into its slab).  What can neither have a
+ * slab nor join the queue is staged by core1_finish2() as slabs free up. */
+static void stage_frames(Staged *S)
+{
+    for (size_t k = 0; k < S->slots.size(); k++) {
+        FrameSlot &fs = S->slots[k];
+        const bool elig = queue_eligible(S, fs);
+        slot_layout(S, fs);
+        if (elig && queue_layout(S, fs) && S->lenders >= S->lender_cap
+            && stage_borrower(S, fs, S->slots.size() - k))
+            continue;
+        if (stage_slot(S, fs)) {
+            if (elig && S->lender0 < 0) {
+                S->lender0 = (int) k; S->lenders = 1;
+                S->qL = fs.L; S->qP = fs.P; S->qPA = fs.PA; S->qbig = fs.big; S->qtri = fs.tri;
+                /* workgroups the chip holds at once: fc_config.inc FC_WG_PER_CU of the build the
+                 * launch will use (wide build for P > 3072: one per CU) */
+                S->lender_cap = (size_t) S->ncu * frames_per_cu(fs);
+                const long long slabs = knob_int("FIASCO_AMD_QUEUE_SLABS", 0);     /* tests: a short queue on small batches */
+                if (slabs > 0) S->lender_cap = (size_t) slabs;
+            } else if (elig && queue_layout(S, fs)) S->lenders++;
+            continue;
+        }
+        if (fs.rejected) continue;         /* outside the device scope: message recorded */
+        if (elig && queue_layout(S, fs) && S->lenders >= 1) {     /* HBM is full: queue */
+            S->jobs[fs.job].errmsg[0] = 0;
+            if (stage_borrower(S, fs, S->slots.size() - k)) { S->lender_cap = S->lenders; continue; }
+        }
+        if (k == 0) continue;              /* does not fit even alone: error already recorded */
+        S->jobs[fs.job].errmsg[0] = 0;     /* later wave */
+        break;
+    }
 }
 
 static void *core1_stage(unsigned n, fa_job *jobs)
@@ -1309,7 +1466,6 @@ static void *core1_stage(unsigned n, fa_job *jobs)
                      "(FIASCO_AMD_NO_LOG2_TABLE=1 encodes without it): %s", g_l2_err);
         return S;                             /* S->ok stays false: nothing of this batch runs */
     }
-    int specG = 0;
     {
         int dev = 0, ncu = 0;
         if (hipGetDevice(&dev) != hipSuccess) dev = 0;
@@ -1317,14 +1473,12 @@ static void *core1_stage(unsigned n, fa_job *jobs)
         /* every frame for the 256-thread build of the speculating kernel?  (several of its workgroups fit a CU) */
         bool narrow_only = n > 0;
         for (unsigned i = 0; i < n && narrow_only; i++) {
-            const fa_cparams *cp = &jobs[i].cp;
             if (!jobs[i].image) { narrow_only = false; break; }
-            const unsigned bw = fa_width_of_level(cp->lc_max_level), bh = fa_height_of_level(cp->lc_max_level);
-            const size_t blocks = (size_t) ((jobs[i].image->width + bw - 1) / bw) * ((jobs[i].image->height + bh - 1) / bh);
-            if (needs_wide_variant(cp) || blocks + blocks * 3 / 8 + 64 + FC_SPEC_MAXG * FC_SPEC_TEMPS > 3072) narrow_only = false;
+            const size_t blocks = top_blocks(&jobs[i]);
+            if (needs_wide_variant(&jobs[i].cp) || blocks + blocks * 3 / 8 + 64 + FC_SPEC_MAXG * FC_SPEC_TEMPS > 3072) narrow_only = false;
         }
-        specG = spec_groups(n, ncu, n > 0 && jobs[0].image && (jobs[0].image->width > 2048 || jobs[0].image->height > 2048), narrow_only);
-        S->specG = specG; S->ncu = ncu;
+        S->specG = spec_groups(n, ncu, n > 0 && jobs[0].image && (jobs[0].image->width > 2048 || jobs[0].image->height > 2048), narrow_only);
+        S->ncu = ncu;
     }
     if (hipStreamCreate(&S->stream) != hipSuccess || hipEventCreate(&S->ev0) != hipSuccess
         || hipEventCreate(&S->ev1) != hipSuccess
@@ -1333,150 +1487,10 @@ static void *core1_stage(unsigned n, fa_job *jobs)
             snprintf(jobs[i].errmsg, sizeof jobs[i].errmsg, "HIP error: cannot create stream/events");
         return S;
     }
-    for (unsigned i = 0; i < n; i++) {
-        if (!device_supported(&jobs[i], jobs[i].errmsg, sizeof jobs[i].errmsg)) continue;
-        /* first guess of the state capacity: one state per bintree node above the largest
-         * block level (2 x #blocks) ... measured need at -q 20 is ~1.3 x #blocks */
-        const fa_cparams *cp = &jobs[i].cp;
-        unsigned bw = fa_width_of_level(cp->lc_max_level), bh = fa_height_of_level(cp->lc_max_level);
-        size_t blocks = (size_t) ((jobs[i].image->width + bw - 1) / bw) * ((jobs[i].image->height + bh - 1) / bh);
-        size_t guess = blocks + blocks * 3 / 8 + 64;
-        /* predicted frames: the residual of a predicted block subdivides where the block itself would not --
-         * 720p colour P frames with --prediction end with 2.0 .. 2.3 table states per block (config 5) */
-        if (jobs[i].frame_type != FA_I_FRAME) guess = blocks * 5 / 2 + 64;
-        /* tests / experiments: FIASCO_AMD_CAP_GUESS=<states> forces the first guess (a frame that
-         * outgrows it is encoded again with 1.5 x the capacity, complete_wave) */
-        if (fa_knob("FIASCO_AMD_CAP_GUESS") && atoi(fa_knob("FIASCO_AMD_CAP_GUESS")) > 0)
-            guess = (size_t) atoi(fa_knob("FIASCO_AMD_CAP_GUESS"));
-        /* what frames of this kind needed before (cap_hint_put): 1/16 on top, frames of a sequence drift */
-        int hintP = 0, hintPA = 0;
-        const bool forced = fa_knob("FIASCO_AMD_CAP_GUESS") && atoi(fa_knob("FIASCO_AMD_CAP_GUESS")) > 0;
-        if (!forced && !fa_knob("FIASCO_AMD_NO_CAP_HINT")) cap_hint_get(&jobs[i], &hintP, &hintPA);
-        if ((size_t) hintP + hintP / 16 + 32 > guess) guess = (size_t) hintP + hintP / 16 + 32;
-        if (guess > cp->limit_states) guess = cp->limit_states;
-        FrameSlot fs;
-        fs.job = (int) i;
-        fs.P = (int) align_up(guess, 64);
-        fs.big = needs_big_variant(cp, jobs[i].wfa) || jobs[i].frame_type != FA_I_FRAME
-                 /* a chroma dictionary of more than 63 states: the list scan of the big builds (mp_steps_list_global) */
-                 || (jobs[i].image->color && cp->chroma_max_states > 63);
-        fs.hm = needs_hm_variant(cp);
-        fs.gm = needs_gm_variant(&jobs[i]) || fa_knob("FIASCO_AMD_FORCE_GM") != nullptr;     /* (tests: every frame through the FC_GM build) */
-        if (fs.gm) fs.big = true;
-        fs.wide_only = !fs.big && needs_wide_variant(cp);
-                /* (experiments: FIASCO_AMD_SPEC_BUILD1 runs the speculating kernel build with ONE workgroup per frame) */
-        const bool build1 = !specG && fa_knob("FIASCO_AMD_SPEC_BUILD1") != nullptr;
-        if ((specG || build1) && !fs.big) {
-            /* the 256-thread build up to 3072 states, the 1024-thread one (4K; frames beyond the narrow
-             * build's LDS pools) up to 12288 */
-            const size_t withids = align_up(guess + (build1 ? 0 : (size_t) (specG - 1 - spec_workers(specG)) * FC_SPEC_TEMPS), 64);
-            if (withids <= 12 * 1024 && withids <= align_up(cp->limit_states, 64)) { fs.spec = true; fs.P = (int) withids; }
-        }
-        /* tests: the triangular layout (chosen below for HBM-bound batches) for every default-geometry frame */
-        if (!fs.big && fa_knob("FIASCO_AMD_FORCE_TRI")) fs.tri = true;
-        /* colour: the two chroma bands add auxiliary states (no tables) */
-        size_t cap = align_up(cp->limit_states, 64);
-        fs.PA = jobs[i].image->color ? (int) (3 * (size_t) fs.P > cap ? cap : 3 * (size_t) fs.P) : fs.P;
-        if ((size_t) hintPA + hintPA / 16 + 32 > (size_t) fs.PA) {
-            const size_t want = align_up((size_t) hintPA + hintPA / 16 + 32, 64);
-            fs.PA = (int) (want > cap ? cap : want);
-        }
-        if (fs.PA < fs.P) fs.PA = fs.P;
-        if (hintP) { fs.floorP = hintP + hintP / 16 + 32; fs.floorPA = hintPA + hintPA / 16 + 32; }
-        S->slots.push_back(fs);
-    }
-    /* Stage the frames.  Every frame gets a slab of its own until the device is full -- as many
-     * frames of one layout as the chip runs workgroups at once, or as HBM holds; the frames
-     * after that join the FRAME QUEUE of that layout (no slab: whichever workgroup finishes its
-     * frame takes the next one into its slab).  What can neither have a slab nor join the queue
-     * is staged by run() as slabs free up. */
-    int cus = 0;
-    {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    }
-    if (!S->slots.empty() && !fa_knob("FIASCO_AMD_NO_TIGHT")) {
-        /* HBM-bound batches (4K: a slab is 3 GB, 97 % of it the Gram tables, quadratic in the state
-         * capacity): when the slabs the chip could keep busy do not fit, the capacity guess drops
-         * from 1.375 to 1.15 states per block of the largest block level -- a third more frames in
-         * flight; a frame that outgrows it is encoded again with 1.5 x the capacity (complete_wave) */
-        FrameSlot probe = S->slots[0];
-        slot_layout(S, probe);
-        size_t free_b = 0, total_b = 0, pooled = 0;
-        for (size_t i = 0; i < g_free.size(); i++) pooled += g_free[i].bytes;
-        size_t want = S->slots.size();
-        const size_t resident = (size_t) cus * frames_per_cu(probe.big, probe.P > 12 * 256 || probe.wide_only || probe.hm || probe.gm);
-        if (want > resident) want = resident;
-        const bool hbm_bound = hipMemGetInfo(&free_b, &total_b) == hipSuccess && probe.L.total * want > free_b + pooled;
-        if ((hbm_bound || S->slots.size() > resident) && queue_eligible(S, probe)) {
-            /* the pixel planes of the frames that will queue for a slab: set aside before the slabs
-             * take what HBM has (when HBM is the limit nobody knows yet how many slabs will fit) */
-            const fa_image *im = jobs[probe.job].image;
-            const size_t need = align_up((size_t) im->width * im->height * (im->color ? 3 : 1) * 2, 256);
-            const size_t frames = hbm_bound ? S->slots.size() : S->slots.size() - resident;
-            if (hipMalloc((void **) &S->qpix, need * frames) == hipSuccess) { S->qpix_bytes = need * frames; S->qpix_used = 0; }
-            else { S->qpix = nullptr; (void) hipGetLastError(); }
-        }
-        bool still_bound = hbm_bound;
-        if (hbm_bound) {
-            /* first remedy: the triangular Gram tables -- half the slab; the kernel build that reads
-             * them exists for the default geometry at the wide workgroup (frames with more than 3072
-             * states: 4K), where memory is what keeps CUs idle.  FIASCO_AMD_NO_TRI keeps the full tables. */
-            for (size_t k = 0; k < S->slots.size(); k++) {
-                FrameSlot &fs = S->slots[k];
-                if (!fs.big && fs.P > 12 * 256 && !fa_knob("FIASCO_AMD_NO_TRI")) fs.tri = true;
-            }
-            FrameSlot probe2 = S->slots[0];
-            slot_layout(S, probe2);
-            still_bound = probe2.L.total * want > free_b + pooled;
-        }
-        if (still_bound)
-            for (size_t k = 0; k < S->slots.size(); k++) {
-                FrameSlot &fs = S->slots[k];
-                const fa_job *job = &jobs[fs.job];
-                const fa_cparams *cp = &job->cp;
-                unsigned bw = fa_width_of_level(cp->lc_max_level), bh = fa_height_of_level(cp->lc_max_level);
-                size_t blocks = (size_t) ((job->image->width + bw - 1) / bw) * ((job->image->height + bh - 1) / bh);
-                size_t tight = align_up(blocks + blocks * 3 / 20 + 64, 64);
-                if ((size_t) fs.floorP > tight) tight = align_up((size_t) fs.floorP, 64);   /* never below a known need */
-                if (tight > cp->limit_states) tight = align_up(cp->limit_states, 64);
-                if ((size_t) fs.P <= tight || fs.spec) continue;
-                const size_t cap = align_up(cp->limit_states, 64);
-                fs.P = (int) tight;
-                fs.PA = job->image->color ? (int) (3 * tight > cap ? cap : 3 * tight) : fs.P;
-                if ((size_t) fs.floorPA > (size_t) fs.PA) fs.PA = (int) (align_up((size_t) fs.floorPA, 64) > cap ? cap : align_up((size_t) fs.floorPA, 64));
-                if (fs.PA < fs.P) fs.PA = fs.P;
-            }
-    }
-    for (size_t k = 0; k < S->slots.size(); k++) {
-        FrameSlot &fs = S->slots[k];
-        const bool elig = queue_eligible(S, fs);
-        slot_layout(S, fs);
-        if (elig && queue_layout(S, fs) && S->lenders >= S->lender_cap
-            && stage_borrower(S, fs, S->slots.size() - k))
-            continue;
-        if (stage_slot(S, fs)) {
-            if (elig && S->lender0 < 0) {
-                S->lender0 = (int) k; S->lenders = 1;
-                S->qL = fs.L; S->qP = fs.P; S->qPA = fs.PA; S->qbig = fs.big; S->qtri = fs.tri;
-                /* workgroups the chip holds at once: fc_config.inc FC_WG_PER_CU of the build the
-                 * launch will use (wide build for P > 3072: one per CU) */
-                S->lender_cap = (size_t) cus * frames_per_cu(fs.big, fs.P > 12 * 256 || fs.wide_only || fs.hm || fs.gm);
-                if (fa_knob("FIASCO_AMD_QUEUE_SLABS") && atoi(fa_knob("FIASCO_AMD_QUEUE_SLABS")) > 0)
-                    S->lender_cap = (size_t) atoi(fa_knob("FIASCO_AMD_QUEUE_SLABS"));     /* tests: a short queue on small batches */
-            } else if (elig && queue_layout(S, fs)) S->lenders++;
-            continue;
-        }
-        if (fs.rejected) continue;         /* outside the device scope: message recorded */
-        if (elig && queue_layout(S, fs) && S->lenders >= 1) {     /* HBM is full: queue */
-            S->jobs[fs.job].errmsg[0] = 0;
-            if (stage_borrower(S, fs, S->slots.size() - k)) { S->lender_cap = S->lenders; continue; }
-        }
-        if (k == 0) continue;              /* does not fit even alone: error already recorded */
-        S->jobs[fs.job].errmsg[0] = 0;     /* later wave */
-        break;
-    }
+    for (unsigned i = 0; i < n; i++)
+        if (device_supported(&jobs[i], jobs[i].errmsg, sizeof jobs[i].errmsg)) S->slots.push_back(first_guess(S, i));
+    if (!S->slots.empty()) fit_hbm(S);
+    stage_frames(S);
     (void) hipStreamSynchronize(S->stream);
     S->ok = true;
     return S;
@@ -1490,17 +1504,8 @@ static int16_t *core1_upload_buffer(void *h, size_t bytes)
     if (!S || !S->ok || !bytes) return nullptr;
     /* the previous upload has left this memory long ago (a whole pass lies in between) */
     if (S->ustream) (void) hipStreamSynchronize(S->ustream);
-    if (bytes > S->up_host_bytes || S->up_host_shared) {
-        if (S->up_host && !S->up_host_shared) (void) hipHostFree(S->up_host);
-        S->up_host_shared = false;
-        S->up_host = nullptr; S->up_host_bytes = 0;
-        if (hipHostMalloc((void **) &S->up_host, bytes, hipHostMallocDefault) != hipSuccess) {
-            S->up_host = nullptr; (void) hipGetLastError();
-            return nullptr;
-        }
-        S->up_host_bytes = bytes;
-    }
-    return (int16_t *) S->up_host;
+    if (S->up_host_shared) { S->up_host = nullptr; S->up_host_bytes = 0; S->up_host_shared = false; }   /* not ours to free */
+    return grow_buffer(S->up_host, S->up_host_bytes, bytes, true) ? (int16_t *) S->up_host : nullptr;
 }
 
 static int core1_upload_commit(void *h)
@@ -1528,15 +1533,9 @@ static int core1_upload_commit(void *h)
         need += align_up(npix * 2, 256);
     }
     if (!need) return 1;                         /* nothing the device can encode */
-    if (need > S->up_dev_bytes[p]) {
-        if (S->up_dev[p]) (void) hipFree(S->up_dev[p]);
-        S->up_dev[p] = nullptr; S->up_dev_bytes[p] = 0;
-        if (hipMalloc((void **) &S->up_dev[p], need) != hipSuccess) {
-            S->up_dev[p] = nullptr; (void) hipGetLastError();
-            fa_set_error("out of HBM: no room for %.1f MiB of replacement frames", need / 1048576.0);
-            return 0;
-        }
-        S->up_dev_bytes[p] = need;
+    if (!grow_buffer(S->up_dev[p], S->up_dev_bytes[p], need)) {
+        fa_set_error("out of HBM: no room for %.1f MiB of replacement frames", need / 1048576.0);
+        return 0;
     }
     {
         size_t at = 0;
@@ -1578,17 +1577,17 @@ static int collect(Staged *S, FrameSlot &fs, const char *pinned)
         }
         pinned = own.data();
     }
-    struct { const char *p; const char *data() const { return p; } } host = { pinned };
-    const int16_t *tree = (const int16_t *) (host.data());
-    const int16_t *into = (const int16_t *) (host.data() + (L.into - L.tree));
-    const float *weight = (const float *) (host.data() + (L.weight - L.tree));
-    const float *fin = (const float *) (host.data() + (L.final_d - L.tree));
-    const uint8_t *los = (const uint8_t *) (host.data() + (L.level_of_state - L.tree));
-    const uint8_t *dt = (const uint8_t *) (host.data() + (L.domain_type - L.tree));
-    const uint16_t *xs = (const uint16_t *) (host.data() + (L.x - L.tree));
-    const uint16_t *ys = (const uint16_t *) (host.data() + (L.y - L.tree));
-    const uint8_t *ycol = (const uint8_t *) (host.data() + (L.ycol - L.tree));
-    const int16_t *mv = (const int16_t *) (host.data() + (L.mv - L.tree));
+    const char *const host = pinned;
+    const int16_t *tree = (const int16_t *) host;
+    const int16_t *into = (const int16_t *) (host + (L.into - L.tree));
+    const float *weight = (const float *) (host + (L.weight - L.tree));
+    const float *fin = (const float *) (host + (L.final_d - L.tree));
+    const uint8_t *los = (const uint8_t *) (host + (L.level_of_state - L.tree));
+    const uint8_t *dt = (const uint8_t *) (host + (L.domain_type - L.tree));
+    const uint16_t *xs = (const uint16_t *) (host + (L.x - L.tree));
+    const uint16_t *ys = (const uint16_t *) (host + (L.y - L.tree));
+    const uint8_t *ycol = (const uint8_t *) (host + (L.ycol - L.tree));
+    const int16_t *mv = (const int16_t *) (host + (L.mv - L.tree));
     const bool inter = job->frame_type != FA_I_FRAME;
     for (unsigned s = 0; s < w->basis_states; s++) w->level_of_state[s] = 0xff;   /* codec/control.c:133-173 */
     fa_wfa_remove_states(w, w->basis_states);
@@ -1679,13 +1678,9 @@ static int collect(Staged *S, FrameSlot &fs, const char *pinned)
  * when the same frame is laid out for two different slabs, plus pack_src */
 static bool queue_resources(Staged *S, size_t frames)
 {
-    if (5 * frames > S->ring_n) {
-        if (S->d_ring) (void) hipFree(S->d_ring);
-        S->d_ring = nullptr; S->ring_n = 0;
-        if (hipMalloc((void **) &S->d_ring, sizeof(unsigned long long) * 5 * frames) != hipSuccess) { (void) hipGetLastError(); return false; }
-        S->ring_n = 5 * frames;
-    }
-    if (!S->d_queue && hipMalloc((void **) &S->d_queue, 10 * sizeof(unsigned)) != hipSuccess) {
+    /* a ring per build that can hold a queue (B_DEFAULT .. B_WIDE_TRI), indexed by the build */
+    if (!grow_buffer(S->d_ring, S->ring_n, 5 * frames)) return false;
+    if (!S->d_queue && hipMalloc((void **) &S->d_queue, 2 * 5 * sizeof(unsigned)) != hipSuccess) {
         S->d_queue = nullptr; (void) hipGetLastError(); return false;
     }
     if (!S->ptrmask_ready) {
@@ -1709,308 +1704,295 @@ static bool queue_resources(Staged *S, size_t frames)
     return true;
 }
 
-/* build the next launch from the frames that are staged and not yet encoded, upload their
- * descriptors and start the kernel(s); nothing is waited for.  Returns false when there is
- * nothing to launch. */
-static bool launch_wave(Staged *S)
+/* frames of a launch per kernel build: all, the frame queue's lenders (with a slab) and its borrowers */
+struct WaveGroups { size_t n[N_BUILDS], lend[N_BUILDS], borrow[N_BUILDS]; };
+
+/* the launch's frames (S->batch), ordered by build, then the queue's lenders, then its borrowers, then the rest,
+ * each part in slot order; counts them per build.  False when nothing is left to launch. */
+static bool order_batch(Staged *S, WaveGroups &g)
 {
     std::vector<size_t> &batch = S->batch;
     batch.clear();
     for (size_t k = 0; k < S->slots.size(); k++)
         if (S->slots[k].staged && !S->slots[k].done) batch.push_back(k);
     if (batch.empty()) return false;
-    /* one launch per kernel build (frame_coder.hip): geometry {default, big} x workgroup width
-     * {256, 512 or 1024 threads}.  The wide builds take launches with no more frames than CUs (the
-     * chip cannot be filled with frames anyway: give each frame twice the lanes) and frames
-     * whose state capacity exceeds the 256-thread build's register-resident scan (4K). */
-    size_t group_n[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, group_lend[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, group_borrow[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-    {
-        int cus = 0, dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-        const bool few = batch.size() <= (size_t) cus && !fa_knob("FIASCO_AMD_NO_WIDE");
-        /* per build: first the frames of the queue's layout -- those with a slab (the queue's
-         * workgroups), then those without --, then every other frame (one workgroup each) */
-        std::vector<size_t> ordered;
-        for (int g = 0; g < 9; g++)
-            for (int part = 0; part < 3; part++)
-                for (size_t b = 0; b < batch.size(); b++) {
-                    const FrameSlot &fs = S->slots[batch[b]];
-                    const bool wide = few || fs.P > 12 * 256 || fs.wide_only;
-                    /* group 5: the FC_HM build, 6: the FC_GM build; groups 7, 8: several workgroups per frame (FC_SPEC builds, 256 / 1024 threads) */
-                    const bool spec = fs.spec && (S->specG >= 2 || fa_knob("FIASCO_AMD_SPEC_BUILD1")) && !fs.borrow && !fs.tri && !fs.big && fs.P <= 12 * 1024;
-                    /* (FIASCO_AMD_SPEC_WIDE=0 / 1: experiments with the width of the workgroups) */
-                    const char *sw = fa_knob("FIASCO_AMD_SPEC_WIDE");
-                    const bool spec_wide = spec && (fs.P > 12 * 256 || fs.wide_only || (sw && atoi(sw) == 1));
-                    if ((spec ? (spec_wide ? 8 : 7) : fs.gm ? 6 : fs.hm ? 5 : fs.tri ? 4 : (int) fs.big * 2 + (int) wide) != g) continue;
-                    const bool q = S->borrowers && queue_eligible(S, fs) && queue_layout(S, fs);
-                    const int where = fs.borrow ? 1 : q ? 0 : 2;
-                    if (where != part) continue;
-                    ordered.push_back(batch[b]);
-                    group_n[g]++;
-                    if (g < 5) g_stats.frames_by_build[g]++; else if (g <= 6) g_stats.frames_by_build[3]++; else g_stats.spec_frames++;
-                    if (part == 0) group_lend[g]++; else if (part == 1) group_borrow[g]++;
-                }
-        batch.swap(ordered);
+    memset(&g, 0, sizeof g);
+    const bool few = batch.size() <= (size_t) S->ncu && !fa_knob("FIASCO_AMD_NO_WIDE");
+    std::vector<int> key(S->slots.size());
+    for (size_t k : batch) {
+        const FrameSlot &fs = S->slots[k];
+        const Build b = build_of(S, fs, few);
+        const int part = fs.borrow ? 1 : S->borrowers && queue_eligible(S, fs) && queue_layout(S, fs) ? 0 : 2;
+        key[k] = 3 * b + part;
+        g.n[b]++;
+        if (part == 0) g.lend[b]++; else if (part == 1) g.borrow[b]++;
+        if (k_build[b].stats_slot >= 0) g_stats.frames_by_build[k_build[b].stats_slot]++; else g_stats.spec_frames++;
     }
+    std::stable_sort(batch.begin(), batch.end(), [&](size_t a, size_t b) { return key[a] < key[b]; });
+    return true;
+}
+
+/* the launch's descriptors (S->hf) and where every frame packs its finished automaton: one buffer per launch,
+ * double buffered -- launch i + 1 writes the other one while the copy of launch i is on its way to the host */
+static void place_packs(Staged *S)
+{
+    const std::vector<size_t> &batch = S->batch;
     std::vector<DevFrame> &hf = S->hf;
     hf.resize(batch.size());
-    S->d_trace = nullptr;
-    const char *trace_path = fa_knob("FIASCO_AMD_TRACE");
-    const int trace_cap = 400000;
-    for (size_t b = 0; b < batch.size(); b++) hf[b] = S->slots[batch[b]].F;
-    {   /* where every frame packs its finished automaton */
-        S->parity ^= 1;
-        char *&pack = S->d_pack[S->parity];
-        S->pack_off.assign(batch.size(), 0);
-        size_t need = 0;
-        for (size_t b = 0; b < batch.size(); b++) {
-            const Layout &L = S->slots[batch[b]].L;
-            S->pack_off[b] = need;
-            need += align_up(L.pool_states - L.tree, 256);
-        }
-        S->pack_need = need;
-        if (need > S->d_pack_bytes[S->parity]) {
-            if (pack) (void) hipFree(pack);
-            pack = nullptr; S->d_pack_bytes[S->parity] = 0;
-            if (hipMalloc((void **) &pack, need) == hipSuccess) S->d_pack_bytes[S->parity] = need;
-            else { pack = nullptr; (void) hipGetLastError(); }
-        }
-        if (!S->cstream && hipStreamCreateWithFlags(&S->cstream, hipStreamNonBlocking) != hipSuccess) {
-            S->cstream = nullptr; (void) hipGetLastError();
-        }
-        S->packed = pack != nullptr && S->cstream != nullptr;
-        for (size_t b = 0; b < batch.size(); b++) {
-            const FrameSlot &fs = S->slots[batch[b]];
-            hf[b].pack_src = fs.F.slab_base + fs.L.tree;     /* a borrower's is re-based by the kernel */
-            hf[b].pack_bytes = (unsigned) (fs.L.pool_states - fs.L.tree);
-            hf[b].pack_dst = S->packed ? pack + S->pack_off[b] : nullptr;
-        }
+    S->pack_off.assign(batch.size(), 0);
+    size_t need = 0;
+    for (size_t b = 0; b < batch.size(); b++) {
+        const FrameSlot &fs = S->slots[batch[b]];
+        hf[b] = fs.F;
+        hf[b].pack_src = fs.F.slab_base + fs.L.tree;     /* a borrower's is re-based by the kernel */
+        hf[b].pack_bytes = (unsigned) (fs.L.pool_states - fs.L.tree);
+        S->pack_off[b] = need;
+        need += align_up(fs.L.pool_states - fs.L.tree, 256);
     }
-    if (trace_path && hipMalloc((void **) &S->d_trace, sizeof(FcTrace) * trace_cap) == hipSuccess) {
-        hf[0].trace = S->d_trace; hf[0].trace_cap = trace_cap;
+    S->pack_need = need;
+    S->parity ^= 1;
+    char *&pack = S->d_pack[S->parity];
+    (void) grow_buffer(pack, S->d_pack_bytes[S->parity], need);      /* without it: one copy per frame */
+    if (!S->cstream && hipStreamCreateWithFlags(&S->cstream, hipStreamNonBlocking) != hipSuccess) {
+        S->cstream = nullptr; (void) hipGetLastError();
     }
-    bool fail = false;
+    S->packed = pack != nullptr && S->cstream != nullptr;
+    for (size_t b = 0; b < batch.size(); b++) hf[b].pack_dst = S->packed ? pack + S->pack_off[b] : nullptr;
+}
+
+/* append helpers per frame of the speculating frames, per width: only for a launch of ONE width (the residency
+ * sum is per build); FIASCO_AMD_SPEC_APP=<H> asks for H, as many as the chip holds beside the frames */
+static void spec_helpers(Staged *S, const WaveGroups &g, int G)
+{
+    S->specH[0] = S->specH[1] = 0;
+    if (S->no_app || (g.n[B_SPEC] && g.n[B_SPEC_WIDE])) return;
+    const int wk = g.n[B_SPEC_WIDE] ? 1 : 0;
+    const size_t frames = g.n[B_SPEC + wk];
+    const int occ = wk ? 1 : fc_occupancy_spec();
+    const char *e = fa_knob("FIASCO_AMD_SPEC_APP");
+    if (!e) { S->specH[wk] = spec_app_policy(frames, S->ncu, G, wk != 0, occ); return; }
+    const size_t room = spec_app_room(frames, S->ncu, G, occ), want = (size_t) (atoi(e) > 0 ? atoi(e) : 0);
+    S->specH[wk] = (int) (want < room ? want : room);
+}
+
+/* the descriptors of the verifier workgroups (table workers share the chain's; verifier v of a frame owns the
+ * state ids [P - 16 v, P - 16 (v - 1)) and its private tables behind the frames' control blocks) */
+static std::vector<DevFrame> spec_descriptors(Staged *S, size_t first_all, size_t nall, int G, int T, size_t span,
+                                              const std::vector<size_t> &priv)
+{
+    const int NV = G - 1 - T;
+    std::vector<DevFrame> vf(nall * (size_t) (G - 1));
+    size_t o = span * nall;
+    for (size_t i = 0; i < nall; i++) {
+        DevFrame &C = S->hf[first_all + i];
+        C.spec = (FcSpecCtl *) (S->d_spec + span * i);
+        C.spec_role = 0; C.spec_G = G; C.spec_T = T;
+        C.spec_cap = C.P - NV * FC_SPEC_TEMPS;
+        C.spec_tb = C.P;
+        for (int r = 1; r < G; r++) {
+            DevFrame &V = vf[i * (size_t) (G - 1) + (size_t) (r - 1)];
+            V = C;
+            V.spec_role = r; V.trace = nullptr; V.trace_cap = 0; V.pack_dst = nullptr;
+            if (r <= T) continue;                        /* a table worker: the chain's descriptor */
+            V.spec_tb = C.P - (r - T) * FC_SPEC_TEMPS;
+            const size_t P = (size_t) C.P;
+            char *q = S->d_spec + o;
+            V.ipis = (float *) q;  q += align_up((size_t) C.NS * P * 4, 256);
+            V.d5 = (float *) q;    q += align_up((size_t) C.NA * P * 4, 256);
+            V.num = (float *) q;   q += align_up(P * 4, 256);
+            V.den = (float *) q;   q += align_up(P * 4, 256);
+            V.est = (float *) q;   q += align_up(P * 4, 256);
+            V.ipdo = (float *) q;  q += align_up((size_t) FC_MAXED * P * 4, 256);
+            V.used = (uint8_t *) q; q += align_up(P, 256);
+            V.pool_states = (int16_t *) q; q += align_up((P + 8) * 2, 256);
+            V.hits = (int *) q;
+            o += priv[i];
+        }
+        S->spec_frames.push_back(first_all + i);
+    }
+    return vf;
+}
+
+/* Block-level speculation for the launch's speculating frames (the last of the batch, 256-thread build first):
+ * per frame one span of control block + checkpoint slots + block list + table ring, then per verifier its
+ * private <sub-block, state> tables, scan scratch and pool list.  Without memory for them: one workgroup per
+ * frame.  False when a HIP call failed. */
+static bool setup_spec(Staged *S, const WaveGroups &g)
+{
     S->spec_frames.clear();
     S->spec_first[0] = S->spec_first[1] = 0; S->spec_n[0] = S->spec_n[1] = 0;
-    if (group_n[7] + group_n[8] && S->specG < 2) {       /* FIASCO_AMD_SPEC_BUILD1: the build alone */
-        const size_t nall = group_n[7] + group_n[8], first_all = batch.size() - nall;
-        S->spec_first[0] = first_all; S->spec_n[0] = group_n[7];
-        S->spec_first[1] = first_all + group_n[7]; S->spec_n[1] = group_n[8];
-        for (size_t i = 0; i < nall; i++) hf[first_all + i].spec = nullptr;
-    } else if (group_n[7] + group_n[8]) {
-        /* the speculating frames (groups 5 and 6: 256 / 1024 threads per workgroup; they are the last of
-         * the batch): control block + checkpoint slots + block list + table ring per frame, then per
-         * verifier workgroup its private <sub-block, state> tables, scan scratch and pool list; verifier
-         * v of a frame owns the state ids [P - 16 v, P - 16 (v - 1)) */
-        const int G = S->specG;
-        const int T = spec_workers(G), NV = G - 1 - T;           /* table workers, verifiers */
-        const size_t nall = group_n[7] + group_n[8], first_all = batch.size() - nall;
-        /* append helpers: only a launch of ONE width (the residency sum below is per build) */
-        S->specH[0] = S->specH[1] = 0;
-        if (!S->no_app) {
-            if (group_n[8] && !group_n[7]) S->specH[1] = spec_app_policy(group_n[8], S->ncu, G, true, 1);
-            else if (group_n[7] && !group_n[8]) S->specH[0] = spec_app_policy(group_n[7], S->ncu, G, false, fc_occupancy_spec());
-        }
-        S->spec_first[0] = first_all; S->spec_n[0] = group_n[7];
-        S->spec_first[1] = first_all + group_n[7]; S->spec_n[1] = group_n[8];
-        /* one span for every frame of the launch (sized for the largest) */
-        size_t max_blocks = 0, max_tab = 0, max_slot = 0;
-        std::vector<std::vector<uint16_t>> lists(nall);
-        for (size_t i = 0; i < nall; i++) {
-            const DevFrame &F = hf[first_all + i];
-            spec_block_list(F, lists[i]);
-            if (lists[i].size() / 2 > max_blocks) max_blocks = lists[i].size() / 2;
-            const size_t tab = align_up(((size_t) F.NS + (size_t) F.NA) * (size_t) F.P * 4, 256);
-            if (tab > max_tab) max_tab = tab;
-            const size_t slot = i < group_n[7] ? fc_spec_slot_bytes() : fc_spec_slot_bytes_wide();
-            if (slot > max_slot) max_slot = slot;
-        }
-        const size_t off_blocks = align_up((size_t) fc_spec_ctl_bytes() + (size_t) 2 * FC_SPEC_W * max_slot, 256);      /* checkpoint + result slots */
-        const size_t off_tabs = align_up(off_blocks + max_blocks * 4, 256);
-        const size_t span = align_up(off_tabs + (size_t) FC_SPEC_R * max_tab, 256);
-        std::vector<size_t> priv(nall);
-        size_t need = span * nall;
-        for (size_t i = 0; i < nall; i++) {
-            const DevFrame &F = hf[first_all + i];
-            const size_t P = (size_t) F.P;
-            priv[i] = align_up((size_t) F.NS * P * 4, 256)
-                      + align_up((size_t) F.NA * P * 4, 256) + 3 * align_up(P * 4, 256) + align_up((size_t) FC_MAXED * P * 4, 256)
-                      + align_up(P, 256) + align_up((P + 8) * 2, 256) + align_up(((size_t) F.PA + 8) * 4, 256);
-            need += priv[i] * (size_t) NV;
-        }
-        if (need > S->d_spec_bytes) {
-            if (S->d_spec) (void) hipFree(S->d_spec);
-            S->d_spec = nullptr; S->d_spec_bytes = 0;
-            if (hipMalloc((void **) &S->d_spec, need) == hipSuccess) S->d_spec_bytes = need; else (void) hipGetLastError();
-        }
-        if (nall * (size_t) (G - 1) > S->vframes_n) {
-            if (S->d_vframes) (void) hipFree(S->d_vframes);
-            S->d_vframes = nullptr; S->vframes_n = 0;
-            if (hipMalloc((void **) &S->d_vframes, sizeof(DevFrame) * nall * (size_t) (G - 1)) == hipSuccess) S->vframes_n = nall * (size_t) (G - 1);
-            else (void) hipGetLastError();
-        }
-        S->spec_ctl_span = span;
-        if (S->d_spec && S->d_vframes) {
-            std::vector<DevFrame> vf(nall * (size_t) (G - 1));
-            size_t o = span * nall;
-            for (size_t i = 0; i < nall; i++) {
-                DevFrame &C = hf[first_all + i];
-                C.spec = (FcSpecCtl *) (S->d_spec + span * i);
-                C.spec_role = 0; C.spec_G = G; C.spec_T = T;
-                C.spec_cap = C.P - NV * FC_SPEC_TEMPS;
-                C.spec_tb = C.P;
-                for (int r = 1; r <= T; r++) {                   /* table workers: the chain's descriptor */
-                    DevFrame &V = vf[i * (size_t) (G - 1) + (size_t) (r - 1)];
-                    V = C;
-                    V.spec_role = r; V.trace = nullptr; V.trace_cap = 0; V.pack_dst = nullptr;
-                }
-                for (int r = T + 1; r < G; r++) {
-                    DevFrame &V = vf[i * (size_t) (G - 1) + (size_t) (r - 1)];
-                    V = C;
-                    V.spec_role = r; V.spec_tb = C.P - (r - T) * FC_SPEC_TEMPS;
-                    const size_t P = (size_t) C.P;
-                    char *q = S->d_spec + o;
-                    V.ipis = (float *) q;  q += align_up((size_t) C.NS * P * 4, 256);
-                    V.d5 = (float *) q;    q += align_up((size_t) C.NA * P * 4, 256);
-                    V.num = (float *) q;   q += align_up(P * 4, 256);
-                    V.den = (float *) q;   q += align_up(P * 4, 256);
-                    V.est = (float *) q;   q += align_up(P * 4, 256);
-                    V.ipdo = (float *) q;  q += align_up((size_t) FC_MAXED * P * 4, 256);
-                    V.used = (uint8_t *) q; q += align_up(P, 256);
-                    V.pool_states = (int16_t *) q; q += align_up((P + 8) * 2, 256);
-                    V.hits = (int *) q;    q += align_up(((size_t) C.PA + 8) * 4, 256);
-                    V.trace = nullptr; V.trace_cap = 0; V.pack_dst = nullptr;
-                    o += priv[i];
-                }
-                S->spec_frames.push_back(first_all + i);
-            }
-            /* control blocks: zero, then what the host knows (sizes, offsets, the block list) */
-            for (size_t i = 0; i < nall && !fail; i++)
-                fail = hipMemsetAsync(S->d_spec + span * i, 0, off_tabs, S->stream) != hipSuccess;
-            fail = fail || hipStreamSynchronize(S->stream) != hipSuccess;
-            for (size_t i = 0; i < nall && !fail; i++) {
-                FcSpecCtl h;
-                memset(&h, 0, sizeof h);
-                h.slot_bytes = (unsigned) max_slot;
-                /* a colour frame: the chroma bands' tables too, from every workgroup but the chain (even
-                 * without table workers for the luminance band) */
-                h.n_blocks = (unsigned) (lists[i].size() / 2);
-                h.n_tabs = hf[first_all + i].color ? 3u * h.n_blocks : (T ? h.n_blocks : 0u);
-                h.tab_stride = (unsigned) max_tab;
-                /* 120 us: about what the chain needs to build the tables itself (tests: FIASCO_AMD_SPEC_TABWAIT=0
-                 * makes it take the worker's tables only when they are there already) */
-                h.tab_wait = fa_knob("FIASCO_AMD_SPEC_TABWAIT") ? (unsigned) atoi(fa_knob("FIASCO_AMD_SPEC_TABWAIT")) : 12000u;
-                h.off_blocks = off_blocks; h.off_tabs = off_tabs;
-                {   /* append helpers of the frame's width group (frames of the 256-thread build come first) */
-                    const int wk = i < group_n[7] ? 0 : 1;
-                    h.app_H = (unsigned) S->specH[wk];
-                    h.app_min = wk ? 2048u : 512u;               /* two passes of the workgroup's lanes */
-                    if (fa_knob("FIASCO_AMD_SPEC_APPMIN")) h.app_min = (unsigned) atoi(fa_knob("FIASCO_AMD_SPEC_APPMIN"));
-                    h.app_dbg = fa_knob("FIASCO_AMD_SPEC_APPDBG") ? (unsigned) atoi(fa_knob("FIASCO_AMD_SPEC_APPDBG")) : 0u;
-                    h.app_wait = fa_knob("FIASCO_AMD_SPEC_APPWAIT_MS") ? 100000u * (unsigned) atoi(fa_knob("FIASCO_AMD_SPEC_APPWAIT_MS")) : 200000000u;   /* 2 s */
-                }
-                fail = hipMemcpy(S->d_spec + span * i, &h, sizeof h, hipMemcpyHostToDevice) != hipSuccess;
-                if (!fail && !lists[i].empty())
-                    fail = hipMemcpy(S->d_spec + span * i + off_blocks, lists[i].data(), lists[i].size() * 2, hipMemcpyHostToDevice) != hipSuccess;
-            }
-            fail = fail || hipMemcpy(S->d_vframes, vf.data(), sizeof(DevFrame) * vf.size(), hipMemcpyHostToDevice) != hipSuccess;
-        } else
-            for (size_t i = 0; i < nall; i++) hf[first_all + i].spec = nullptr;      /* no memory: one workgroup per frame */
+    const size_t nall = g.n[B_SPEC] + g.n[B_SPEC_WIDE], first_all = S->batch.size() - nall;
+    if (!nall) return true;
+    std::vector<DevFrame> &hf = S->hf;
+    const int G = S->specG;
+    const int T = spec_workers(G), NV = G - 1 - T;           /* table workers, verifiers */
+    spec_helpers(S, g, G);
+    S->spec_first[0] = first_all; S->spec_n[0] = g.n[B_SPEC];
+    S->spec_first[1] = first_all + g.n[B_SPEC]; S->spec_n[1] = g.n[B_SPEC_WIDE];
+    /* one span for every frame of the launch (sized for the largest) */
+    size_t max_blocks = 0, max_tab = 0, max_slot = 0;
+    std::vector<std::vector<uint16_t>> lists(nall);
+    for (size_t i = 0; i < nall; i++) {
+        const DevFrame &F = hf[first_all + i];
+        spec_block_list(F, lists[i]);
+        if (lists[i].size() / 2 > max_blocks) max_blocks = lists[i].size() / 2;
+        const size_t tab = align_up(((size_t) F.NS + (size_t) F.NA) * (size_t) F.P * 4, 256);
+        if (tab > max_tab) max_tab = tab;
+        const size_t slot = i < g.n[B_SPEC] ? fc_spec_slot_bytes() : fc_spec_slot_bytes_wide();
+        if (slot > max_slot) max_slot = slot;
     }
-    fail = fail || hipMemcpyAsync(S->d_frames, hf.data(), sizeof(DevFrame) * batch.size(),
-                               hipMemcpyHostToDevice, S->stream) != hipSuccess;
-    /* ---- one persistent launch per kernel build: one workgroup per frame ---- */
+    const size_t off_blocks = align_up((size_t) fc_spec_ctl_bytes() + (size_t) 2 * FC_SPEC_W * max_slot, 256);      /* checkpoint + result slots */
+    const size_t off_tabs = align_up(off_blocks + max_blocks * 4, 256);
+    const size_t span = align_up(off_tabs + (size_t) FC_SPEC_R * max_tab, 256);
+    std::vector<size_t> priv(nall);
+    size_t need = span * nall;
+    for (size_t i = 0; i < nall; i++) {
+        const DevFrame &F = hf[first_all + i];
+        const size_t P = (size_t) F.P;
+        priv[i] = align_up((size_t) F.NS * P * 4, 256)
+                  + align_up((size_t) F.NA * P * 4, 256) + 3 * align_up(P * 4, 256) + align_up((size_t) FC_MAXED * P * 4, 256)
+                  + align_up(P, 256) + align_up((P + 8) * 2, 256) + align_up(((size_t) F.PA + 8) * 4, 256);
+        need += priv[i] * (size_t) NV;
+    }
+    (void) grow_buffer(S->d_spec, S->d_spec_bytes, need);
+    (void) grow_buffer(S->d_vframes, S->vframes_n, nall * (size_t) (G - 1));
+    S->spec_ctl_span = span;
+    if (!S->d_spec || !S->d_vframes) {
+        for (size_t i = 0; i < nall; i++) hf[first_all + i].spec = nullptr;      /* no memory: one workgroup per frame */
+        return true;
+    }
+    const std::vector<DevFrame> vf = spec_descriptors(S, first_all, nall, G, T, span, priv);
+    /* control blocks: zero, then what the host knows (sizes, offsets, the block list) */
+    bool fail = false;
+    for (size_t i = 0; i < nall && !fail; i++)
+        fail = hipMemsetAsync(S->d_spec + span * i, 0, off_tabs, S->stream) != hipSuccess;
+    fail = fail || hipStreamSynchronize(S->stream) != hipSuccess;
+    for (size_t i = 0; i < nall && !fail; i++) {
+        FcSpecCtl h;
+        memset(&h, 0, sizeof h);
+        h.slot_bytes = (unsigned) max_slot;
+        /* a colour frame: the chroma bands' tables too, from every workgroup but the chain (even
+         * without table workers for the luminance band) */
+        h.n_blocks = (unsigned) (lists[i].size() / 2);
+        h.n_tabs = hf[first_all + i].color ? 3u * h.n_blocks : (T ? h.n_blocks : 0u);
+        h.tab_stride = (unsigned) max_tab;
+        /* 120 us: about what the chain needs to build the tables itself (tests: FIASCO_AMD_SPEC_TABWAIT=0
+         * makes it take the worker's tables only when they are there already) */
+        h.tab_wait = (unsigned) knob_int("FIASCO_AMD_SPEC_TABWAIT", 12000);
+        h.off_blocks = off_blocks; h.off_tabs = off_tabs;
+        /* append helpers of the frame's width group */
+        const int wk = i < g.n[B_SPEC] ? 0 : 1;
+        h.app_H = (unsigned) S->specH[wk];
+        h.app_min = wk ? 2048u : 512u;               /* two passes of the workgroup's lanes */
+        h.app_dbg = (unsigned) knob_int("FIASCO_AMD_SPEC_APPDBG", 0);
+        h.app_wait = 100000u * (unsigned) knob_int("FIASCO_AMD_SPEC_APPWAIT_MS", 2000);      /* 100 MHz ticks */
+        fail = hipMemcpy(S->d_spec + span * i, &h, sizeof h, hipMemcpyHostToDevice) != hipSuccess;
+        if (!fail && !lists[i].empty())
+            fail = hipMemcpy(S->d_spec + span * i + off_blocks, lists[i].data(), lists[i].size() * 2, hipMemcpyHostToDevice) != hipSuccess;
+    }
+    fail = fail || hipMemcpy(S->d_vframes, vf.data(), sizeof(DevFrame) * vf.size(), hipMemcpyHostToDevice) != hipSuccess;
+    return !fail;
+}
+
+/* Big frames that leave the chip empty (a step of a video: 30 GOPs): W workgroups build the tables of a frame
+ * (frame_coder.h FcCoop), one of 512 threads per CU, all resident: W x frames <= CUs, nothing else beside them.
+ * Returns W (1: off) for the `plain' frames of build b at batch position `at' and writes their control blocks. */
+static unsigned setup_coop(Staged *S, Build b, size_t at, size_t plain, bool &fail)
+{
+    const std::vector<DevFrame> &hf = S->hf;
+    unsigned W = 1;
+    bool any_bx = false;                /* a long basis: its table rows are built by the frame's own workgroup */
+    for (size_t i = at; i < at + plain; i++) any_bx = any_bx || hf[i].bx != nullptr;
+    if (b == B_BIG_WIDE && S->batch.size() == plain && !S->no_coop && !any_bx) W = coop_policy(plain, S->ncu);
+    if (S->no_coop) S->no_coop_done = true;
+    if (W == 1) return W;
+    FcCoop &hdr = S->coop_hdr;
+    memset(&hdr, 0, sizeof hdr);
+    for (hdr.depth = 1; (1u << hdr.depth) < W; hdr.depth++) {}
+    /* tests: FIASCO_AMD_COOP_WAIT_MS shortens the frame's wait, FIASCO_AMD_COOP_DEAF=1 sends the helpers
+     * home at once (the frame then fails with FC_ERR_COOP and is searched again by one workgroup) */
+    hdr.done_ticks = 100000ull * (unsigned long long) knob_int("FIASCO_AMD_COOP_WAIT_MS", FC_COOP_DONE_TICKS / 100000);
+    hdr.quit = fa_knob("FIASCO_AMD_COOP_DEAF") ? 1u : 0u;
+    hdr.minsub = 1;
+    for (size_t i = at; i < at + plain && !fail; i++)
+        fail = hipMemcpyAsync(hf[i].coop, &hdr, sizeof(FcCoop), hipMemcpyHostToDevice, S->stream) != hipSuccess;
+    g_stats.coop_frames += plain; g_stats.coop_workgroups = W;
+    return W;
+}
+
+/* one persistent launch per kernel build, speculating builds first; the queue's frames with their ring */
+static bool start_launches(Staged *S, const WaveGroups &g, bool fail)
+{
+    std::vector<DevFrame> &hf = S->hf;
+    const size_t frames = S->batch.size();
+    /* bound of a queued frame's wait for a slab (frame_coder.hip); tests shorten it */
+    const unsigned long long qwait = 100000ull * (unsigned long long) knob_int("FIASCO_AMD_QUEUE_WAIT_MS", FC_QUEUE_WAIT_TICKS / 100000);
+    for (int k = 0; k < 2 && !fail; k++) {
+        if (!S->spec_n[k]) continue;
+        /* without the verifiers' buffers: G = 1, the chain alone */
+        const bool on = S->d_spec && S->d_vframes && !S->spec_frames.empty();
+        DevFrame *vfr = S->d_vframes ? S->d_vframes + (S->spec_first[k] - S->spec_first[0]) * (size_t) (S->specG - 1) : nullptr;
+        k_build[B_SPEC + k].spec_launch(S->d_frames + S->spec_first[k], vfr, (unsigned) S->spec_n[k],
+                                        on ? (unsigned) S->specG : 1u, on ? (unsigned) S->specH[k] : 0u, S->stream);
+    }
+    size_t first = 0;
+    for (int b = 0; b < B_SPEC && !fail; b++) {
+        launch_fn *const launch = k_build[b].launch;
+        size_t plain = g.n[b], at = first;
+        if (g.borrow[b]) {
+            /* the queue: g.lend[b] frames with slabs first, then the frames that borrow one */
+            const size_t nq = g.lend[b] + g.borrow[b];
+            if (!g.lend[b] || !S->packed || !queue_resources(S, frames)) {
+                for (size_t i = at + g.lend[b]; i < at + nq; i++) hf[i].status = FC_ERR_INTERNAL;
+                fail = fail || hipMemcpyAsync(S->d_frames + at, hf.data() + at, sizeof(DevFrame) * nq,
+                                              hipMemcpyHostToDevice, S->stream) != hipSuccess;
+                if (g.lend[b])
+                    launch(S->d_frames + at, (unsigned) g.lend[b], (unsigned) g.lend[b], nullptr, nullptr, nullptr, qwait, 1u, S->stream);
+            } else {
+                unsigned long long *ring = S->d_ring + (size_t) b * frames;
+                fail = fail || hipMemsetAsync(S->d_queue + 2 * b, 0, 2 * sizeof(unsigned), S->stream) != hipSuccess;
+                fail = fail || hipMemsetAsync(ring, 0, nq * sizeof(unsigned long long), S->stream) != hipSuccess;
+                launch(S->d_frames + at, (unsigned) nq, (unsigned) g.lend[b], ring, S->d_queue + 2 * b,
+                       S->d_ptrmask, qwait, 1u, S->stream);
+            }
+            at += nq; plain -= nq;
+        }
+        if (plain) {
+            const unsigned W = setup_coop(S, (Build) b, at, plain, fail);
+            launch(S->d_frames + at, (unsigned) plain, (unsigned) plain, nullptr, nullptr, nullptr, qwait, W, S->stream);
+        }
+        first += g.n[b];
+    }
+    return fail;
+}
+
+/* build the next launch, upload its descriptors and start the kernel(s); nothing is waited for.  Returns false
+ * when there is nothing to launch. */
+static bool launch_wave(Staged *S)
+{
+    WaveGroups g;
+    if (!order_batch(S, g)) return false;
+    place_packs(S);
+    S->d_trace = nullptr;
+    const int trace_cap = 400000;
+    if (fa_knob("FIASCO_AMD_TRACE") && hipMalloc((void **) &S->d_trace, sizeof(FcTrace) * trace_cap) == hipSuccess) {
+        S->hf[0].trace = S->d_trace; S->hf[0].trace_cap = trace_cap;
+    }
+    bool fail = !setup_spec(S, g);
+    fail = fail || hipMemcpyAsync(S->d_frames, S->hf.data(), sizeof(DevFrame) * S->batch.size(),
+                                  hipMemcpyHostToDevice, S->stream) != hipSuccess;
     fail = fail || hipEventRecord(S->ev0, S->stream) != hipSuccess;
-    {
-        typedef void (*launch_fn)(DevFrame *, unsigned, unsigned, unsigned long long *, unsigned *, const unsigned *,
-                                  unsigned long long, unsigned, hipStream_t);
-        /* bound of a queued frame's wait for a slab (frame_coder.hip); tests shorten it */
-        unsigned long long qwait = FC_QUEUE_WAIT_TICKS;
-        if (fa_knob("FIASCO_AMD_QUEUE_WAIT_MS")) qwait = 100000ull * (unsigned long long) atoll(fa_knob("FIASCO_AMD_QUEUE_WAIT_MS"));
-        static const launch_fn launch[7] = { fc_launch, fc_launch_wide, fc_launch_big, fc_launch_big_wide, fc_launch_wide_tri, fc_launch_big_hm, fc_launch_big_gm };
-        size_t first = 0;
-        for (int k = 0; k < 2 && !fail; k++) {
-            if (!S->spec_n[k]) continue;
-            /* without the verifiers' buffers: G = 1, the chain alone */
-            const bool on = S->d_spec && S->d_vframes && !S->spec_frames.empty();
-            const size_t all_first = S->spec_first[0];
-            DevFrame *vfr = S->d_vframes ? S->d_vframes + (S->spec_first[k] - all_first) * (size_t) (S->specG - 1) : nullptr;
-            (k ? fc_launch_spec_wide : fc_launch_spec)(S->d_frames + S->spec_first[k], vfr, (unsigned) S->spec_n[k],
-                                                       on ? (unsigned) S->specG : 1u, on ? (unsigned) S->specH[k] : 0u, S->stream);
-        }
-        for (int g = 0; g < 7 && !fail; g++) {
-            size_t plain = group_n[g], at = first;
-            if (group_borrow[g]) {
-                /* the queue: group_lend[g] frames with slabs first, then the frames that borrow one */
-                const size_t nq = group_lend[g] + group_borrow[g];
-                if (!group_lend[g] || !S->packed || !queue_resources(S, batch.size())) {
-                    for (size_t b = at + group_lend[g]; b < at + nq; b++) hf[b].status = FC_ERR_INTERNAL;
-                    fail = fail || hipMemcpyAsync(S->d_frames + at, hf.data() + at, sizeof(DevFrame) * nq,
-                                                  hipMemcpyHostToDevice, S->stream) != hipSuccess;
-                    if (group_lend[g])
-                        launch[g](S->d_frames + at, (unsigned) group_lend[g], (unsigned) group_lend[g], nullptr, nullptr, nullptr, qwait, 1u, S->stream);
-                } else {
-                    unsigned long long *ring = S->d_ring + (size_t) g * batch.size();
-                    fail = fail || hipMemsetAsync(S->d_queue + 2 * g, 0, 2 * sizeof(unsigned), S->stream) != hipSuccess;
-                    fail = fail || hipMemsetAsync(ring, 0, nq * sizeof(unsigned long long), S->stream) != hipSuccess;
-                    launch[g](S->d_frames + at, (unsigned) nq, (unsigned) group_lend[g], ring, S->d_queue + 2 * g,
-                              S->d_ptrmask, qwait, 1u, S->stream);
-                }
-                at += nq; plain -= nq;
-            }
-            if (plain) {
-                /* big frames that leave the chip empty (a step of a video: 30 GOPs): several workgroups build the
-                 * tables of a frame (frame_coder.h FcCoop).  One workgroup of 512 threads per CU; every workgroup
-                 * of the launch must be resident: W x frames <= CUs, and nothing else launched beside it */
-                unsigned W = 1;
-                bool any_bx = false;                /* a long basis: its table rows are built by the frame's own workgroup */
-                for (size_t b = at; b < at + plain; b++) any_bx = any_bx || hf[b].bx != nullptr;
-                if (g == 3 && batch.size() == plain && !S->no_coop && !any_bx) {
-                    W = coop_policy(plain, S->ncu ? S->ncu : 256);
-                    if (fa_knob("FIASCO_AMD_COOP") && atoi(fa_knob("FIASCO_AMD_COOP")) >= 1) {
-                        W = (unsigned) atoi(fa_knob("FIASCO_AMD_COOP"));
-                        if (W > 8) W = 8;
-                        if ((size_t) W * ((plain + 7) / 8 * 8) > (size_t) (S->ncu ? S->ncu : 256)) W = 1;
-                    }
-                }
-                if (S->no_coop) S->no_coop_done = true;
-                if (W > 1) {
-                    unsigned D = 1;
-                    while ((1u << D) < W) D++;
-                    if (fa_knob("FIASCO_AMD_COOP_DEPTH") && atoi(fa_knob("FIASCO_AMD_COOP_DEPTH")) >= 1 && atoi(fa_knob("FIASCO_AMD_COOP_DEPTH")) <= 3
-                        && (1 << atoi(fa_knob("FIASCO_AMD_COOP_DEPTH"))) >= (int) W)
-                        D = (unsigned) atoi(fa_knob("FIASCO_AMD_COOP_DEPTH"));
-                    FcCoop &hdr = S->coop_hdr;
-                    memset(&hdr, 0, sizeof hdr);
-                    hdr.depth = D;
-                    /* tests: FIASCO_AMD_COOP_WAIT_MS shortens the frame's wait, FIASCO_AMD_COOP_DEAF=1 sends the helpers
-                     * home at once (the frame then fails with FC_ERR_COOP and is searched again by one workgroup) */
-                    hdr.done_ticks = fa_knob("FIASCO_AMD_COOP_WAIT_MS") ? 100000ull * (unsigned long long) atoll(fa_knob("FIASCO_AMD_COOP_WAIT_MS"))
-                                                                            : FC_COOP_DONE_TICKS;
-                    hdr.quit = fa_knob("FIASCO_AMD_COOP_DEAF") ? 1u : 0u;
-                    hdr.minsub = fa_knob("FIASCO_AMD_COOP_MINSUB") ? atoi(fa_knob("FIASCO_AMD_COOP_MINSUB")) : 1;
-                    for (size_t b = at; b < at + plain && !fail; b++)
-                        fail = hipMemcpyAsync(hf[b].coop, &hdr, sizeof(FcCoop), hipMemcpyHostToDevice, S->stream) != hipSuccess;
-                    g_stats.coop_frames += plain; g_stats.coop_workgroups = W;
-                }
-                launch[g](S->d_frames + at, (unsigned) plain, (unsigned) plain, nullptr, nullptr, nullptr, qwait, W, S->stream);
-            }
-            first += group_n[g];
-        }
-    }
+    fail = start_launches(S, g, fail);
     fail = fail || hipGetLastError() != hipSuccess;
     fail = fail || hipEventRecord(S->ev1, S->stream) != hipSuccess;
     S->launch_failed = fail;
     return true;
 }
 
-/* wait for the launch, download the descriptors, collect every finished frame; a frame whose
- * capacity guess was too small gets a bigger slab and stays "not done" for the next launch */
-static void complete_wave(Staged *S)
+/* wait for the launch, download the descriptors (S->hf) and the counters of speculation, write the trace.  False
+ * when the launch or the download failed. */
+static bool download_wave(Staged *S)
 {
-    std::vector<size_t> &batch = S->batch;
     std::vector<DevFrame> &hf = S->hf;
     bool fail = S->launch_failed;
     fail = fail || hipStreamSynchronize(S->stream) != hipSuccess;
@@ -2020,7 +2002,7 @@ static void complete_wave(Staged *S)
             g_stats.kernel_ms += ms;
             g_stats.launches += 1;
         }
-        fail = hipMemcpy(hf.data(), S->d_frames, sizeof(DevFrame) * batch.size(),
+        fail = hipMemcpy(hf.data(), S->d_frames, sizeof(DevFrame) * S->batch.size(),
                          hipMemcpyDeviceToHost) != hipSuccess;
     }
     if (!fail && !S->spec_frames.empty() && S->d_spec) {
@@ -2046,127 +2028,141 @@ static void complete_wave(Staged *S)
         }
     }
     if (S->d_trace) { (void) hipFree(S->d_trace); S->d_trace = nullptr; }
-    if (fail) {
-        const char *why = hipGetErrorString(hipGetLastError());   /* reading it clears it: once */
-        for (size_t b = 0; b < batch.size(); b++) {
-            FrameSlot &fs = S->slots[batch[b]];
-            snprintf(S->jobs[fs.job].errmsg, sizeof S->jobs[fs.job].errmsg, "HIP error: %s", why);
-            fs.done = true;
-        }
-        S->broken = true;
-        return;
-    }
-    /* all automata of the launch come down into one pinned buffer: one copy of the packed
-     * buffer on the copy stream (not waited for here: the next launch may start first), or --
-     * without a packed buffer -- one async copy per frame */
+    return !fail;
+}
+
+/* All automata of the launch come down into one pinned buffer: one copy of the packed buffer on the copy stream
+ * (not waited for here: the next launch may start first), or -- without a packed buffer -- one async copy per
+ * frame.  Returns every frame's offset in S->pinned ((size_t) -1: not there, collect() copies it itself). */
+static std::vector<size_t> fetch_automata(Staged *S)
+{
+    const std::vector<size_t> &batch = S->batch;
+    const std::vector<DevFrame> &hf = S->hf;
     std::vector<size_t> off(batch.size(), (size_t) -1);
-    {
-        size_t need = 0;
-        if (S->packed) {
-            need = S->pack_need;
-            for (size_t b = 0; b < batch.size(); b++) if (hf[b].status == FC_OK) off[b] = S->pack_off[b];
-        } else
+    size_t need = 0;
+    if (S->packed) {
+        need = S->pack_need;
+        for (size_t b = 0; b < batch.size(); b++) if (hf[b].status == FC_OK) off[b] = S->pack_off[b];
+    } else
         for (size_t b = 0; b < batch.size(); b++)
             if (hf[b].status == FC_OK) {
                 const Layout &L = S->slots[batch[b]].L;
                 off[b] = need;
                 need += align_up(L.pool_states - L.tree, 256);
             }
-        if (S->copy_pending) { (void) hipStreamSynchronize(S->cstream); S->copy_pending = false; }
-        if (need > S->pinned_bytes) {
-            if (S->pinned) (void) hipHostFree(S->pinned);
-            S->pinned = nullptr; S->pinned_bytes = 0;
-            if (hipHostMalloc((void **) &S->pinned, need, hipHostMallocDefault) == hipSuccess) S->pinned_bytes = need;
-            else { S->pinned = nullptr; (void) hipGetLastError(); }
+    if (S->copy_pending) { (void) hipStreamSynchronize(S->cstream); S->copy_pending = false; }
+    (void) grow_buffer(S->pinned, S->pinned_bytes, need, true);
+    if (S->pinned && S->packed) {
+        if (hipMemcpyAsync(S->pinned, S->d_pack[S->parity], need, hipMemcpyDeviceToHost, S->cstream) == hipSuccess)
+            S->copy_pending = true;
+        else {
+            (void) hipGetLastError();
+            off.assign(batch.size(), (size_t) -1);
         }
-        if (S->pinned && S->packed) {
-            if (hipMemcpyAsync(S->pinned, S->d_pack[S->parity], need, hipMemcpyDeviceToHost, S->cstream) == hipSuccess)
-                S->copy_pending = true;
-            else {
-                (void) hipGetLastError();
-                for (size_t b = 0; b < batch.size(); b++) off[b] = (size_t) -1;
+    } else if (S->pinned) {
+        for (size_t b = 0; b < batch.size(); b++)
+            if (off[b] != (size_t) -1) {
+                const FrameSlot &fs = S->slots[batch[b]];
+                if (hipMemcpyAsync(S->pinned + off[b], fs.base + fs.L.tree, fs.L.pool_states - fs.L.tree,
+                                   hipMemcpyDeviceToHost, S->stream) != hipSuccess)
+                    off[b] = (size_t) -1;
             }
-        } else if (S->pinned) {
-            for (size_t b = 0; b < batch.size(); b++)
-                if (off[b] != (size_t) -1) {
-                    const FrameSlot &fs = S->slots[batch[b]];
-                    if (hipMemcpyAsync(S->pinned + off[b], fs.base + fs.L.tree, fs.L.pool_states - fs.L.tree,
-                                       hipMemcpyDeviceToHost, S->stream) != hipSuccess)
-                        off[b] = (size_t) -1;
-                }
-            (void) hipStreamSynchronize(S->stream);
-        }
+        (void) hipStreamSynchronize(S->stream);
     }
-    for (size_t b = 0; b < batch.size(); b++) {
-        FrameSlot &fs = S->slots[batch[b]];
-        fa_job *job = &S->jobs[fs.job];
-        int st = hf[b].status;
-        void *tr_keep = fs.F.trace;
-        fs.F = hf[b];
-        fs.F.trace = (FcTrace *) tr_keep; fs.F.trace_cap = 0;
-        if (fs.ext_pix) fs.F.pix16 = fs.ext_pix;
-        size_t cap = align_up(job->cp.limit_states, 64);
-        /* (a frame that shares its slab with verifiers has less than fs.P for itself -- their private
-         * state ids lie at the top of the capacity --: at the state limit it is encoded once more by one
-         * workgroup with all of it, like the reference would, before "Maximum number of states" is said) */
-        if (st == FC_ERR_CAPACITY && ((size_t) fs.P < cap || (size_t) fs.PA < cap || fs.spec)) {
-            /* capacity guess too small: bigger slab, same inputs, encode again */
-            g_stats.reencodes += 1;
-            size_t np = align_up((size_t) fs.P + (size_t) fs.P / 2, 64);
-            size_t npa = align_up((size_t) fs.PA + (size_t) fs.PA / 2, 64);
-            if ((size_t) fs.P >= cap || np >= cap) fs.spec = false;
-            /* a frame of a launch with more workgroups than CUs that outgrows the 256-thread build would come
-             * back in the 1024-thread speculating build, one workgroup per CU: its verifiers might not be
-             * resident (the chain's waits are bounded, but slow) -- one workgroup for such a frame */
-            if (np > 3072 && S->specG > 1 && (size_t) S->specG * S->n > (size_t) S->ncu) fs.spec = false;
-            if (fs.base) slab_release(fs.base, fs.bytes);
-            /* a borrower gets a slab of its own; its pixel planes stay where they are (the queue's
-             * pixel buffer or an upload buffer): the host copy may belong to the next pass by now */
-            if (fs.borrow) { fs.borrow = false; S->borrowers--; }
-            fs.base = nullptr; fs.staged = false;
-            fs.P = (int) (np > cap ? cap : np);
-            fs.PA = (int) (npa > cap ? cap : npa);
-            if (fs.PA < fs.P) fs.PA = fs.P;
-            if (fs.P > 12 * 1024) fs.spec = false;     /* beyond the speculating builds: one (wide) workgroup */
-            if (!stage_slot(S, fs)) fs.done = true;
-            continue;
-        }
-        if (st == FC_ERR_COOP && fs.spec && !S->no_app) {
-            /* the append helpers of a speculating frame did not answer in time: again without helpers */
-            S->no_app = true;
-            continue;
-        }
-        if (st == FC_ERR_COOP && !S->no_coop_done) {
-            /* the helper workgroups of the frame were not there in time (not resident: masked CUs, a busy device):
-             * the frame keeps its slab and is searched again by one workgroup -- a retry instead of a failure */
-            S->no_coop = true;
-            continue;
-        }
-        if (st == FC_ERR_QUEUE && fs.borrow) {
-            /* the frame never got a slab from the queue (bounded wait in the kernel): a slab of its
-             * own in the next launch; its pixel planes stay where they are */
-            fs.borrow = false; S->borrowers--;
-            fs.base = nullptr; fs.staged = false;
-            if (!stage_slot(S, fs)) fs.done = true;
-            continue;
-        }
-        fs.done = true;
-        if (st == FC_OK) {
-            /* unpacking into the job's fa_wfa is host work on host memory: deferred so that
-             * a following submit can start the device first (flush_unpack) */
-            if (S->pinned && off[b] != (size_t) -1) S->to_unpack.push_back(std::make_pair(batch[b], off[b]));
-            else S->good += collect(S, fs, nullptr);
-        } else {
-            const char *msg = "device coder failed";
-            if (st == FC_ERR_STATES || st == FC_ERR_CAPACITY) msg = "Maximum number of states reached!";
-            else if (st == FC_ERR_NOROOT) msg = "No root state generated!";
-            else if (st == FC_ERR_QUEUE) msg = "device coder: frame queue gave no slab";
-            else if (st == FC_ERR_COOP) msg = "device coder: the helper workgroups of the frame did not answer";
-            else if (st == FC_ERR_INTERNAL) msg = "device coder: frame exceeds a built-in capacity (recursion depth, snapshot stack or 16384 states)";
-            if (st > FC_ERR_QUEUE) snprintf(job->errmsg, sizeof job->errmsg, "%s (status %d)", msg, st);
-            else snprintf(job->errmsg, sizeof job->errmsg, "%s", msg);
-        }
+    return off;
+}
+
+/* What becomes of the frame at batch position b, by its status, in this order: a capacity guess that was too small
+ * (a bigger slab, encoded again), append helpers that did not answer (again without helpers), table helpers that
+ * did not answer (again by one workgroup), a queued frame that got no slab (a slab of its own), else done: collected
+ * (`off': its automaton in S->pinned) or failed with a message. */
+static void frame_outcome(Staged *S, size_t b, size_t off)
+{
+    FrameSlot &fs = S->slots[S->batch[b]];
+    fa_job *job = &S->jobs[fs.job];
+    const int st = S->hf[b].status;
+    void *tr_keep = fs.F.trace;
+    fs.F = S->hf[b];
+    fs.F.trace = (FcTrace *) tr_keep; fs.F.trace_cap = 0;
+    if (fs.ext_pix) fs.F.pix16 = fs.ext_pix;
+    const size_t cap = align_up(job->cp.limit_states, 64);
+    /* (a frame that shares its slab with verifiers has less than fs.P for itself -- their private
+     * state ids lie at the top of the capacity --: at the state limit it is encoded once more by one
+     * workgroup with all of it, like the reference would, before "Maximum number of states" is said) */
+    if (st == FC_ERR_CAPACITY && ((size_t) fs.P < cap || (size_t) fs.PA < cap || fs.spec)) {
+        /* capacity guess too small: bigger slab, same inputs, encode again */
+        g_stats.reencodes += 1;
+        size_t np = align_up((size_t) fs.P + (size_t) fs.P / 2, 64);
+        size_t npa = align_up((size_t) fs.PA + (size_t) fs.PA / 2, 64);
+        if ((size_t) fs.P >= cap || np >= cap) fs.spec = false;
+        /* a frame of a launch with more workgroups than CUs that outgrows the 256-thread build would come
+         * back in the 1024-thread speculating build, one workgroup per CU: its verifiers might not be
+         * resident (the chain's waits are bounded, but slow) -- one workgroup for such a frame */
+        if (np > 3072 && S->specG > 1 && (size_t) S->specG * S->n > (size_t) S->ncu) fs.spec = false;
+        if (fs.base) slab_release(fs.base, fs.bytes);
+        /* a borrower gets a slab of its own; its pixel planes stay where they are (the queue's
+         * pixel buffer or an upload buffer): the host copy may belong to the next pass by now */
+        if (fs.borrow) { fs.borrow = false; S->borrowers--; }
+        fs.base = nullptr; fs.staged = false;
+        fs.P = (int) (np > cap ? cap : np);
+        fs.PA = (int) (npa > cap ? cap : npa);
+        if (fs.PA < fs.P) fs.PA = fs.P;
+        if (fs.P > 12 * 1024) fs.spec = false;     /* beyond the speculating builds: one (wide) workgroup */
+        if (!stage_slot(S, fs)) fs.done = true;
+        return;
     }
+    if (st == FC_ERR_COOP && fs.spec && !S->no_app) {
+        /* the append helpers of a speculating frame did not answer in time: again without helpers */
+        S->no_app = true;
+        return;
+    }
+    if (st == FC_ERR_COOP && !S->no_coop_done) {
+        /* the helper workgroups of the frame were not there in time (not resident: masked CUs, a busy device):
+         * the frame keeps its slab and is searched again by one workgroup -- a retry instead of a failure */
+        S->no_coop = true;
+        return;
+    }
+    if (st == FC_ERR_QUEUE && fs.borrow) {
+        /* the frame never got a slab from the queue (bounded wait in the kernel): a slab of its
+         * own in the next launch; its pixel planes stay where they are */
+        fs.borrow = false; S->borrowers--;
+        fs.base = nullptr; fs.staged = false;
+        if (!stage_slot(S, fs)) fs.done = true;
+        return;
+    }
+    fs.done = true;
+    if (st == FC_OK) {
+        /* unpacking into the job's fa_wfa is host work on host memory: deferred so that
+         * a following submit can start the device first (flush_unpack) */
+        if (S->pinned && off != (size_t) -1) S->to_unpack.push_back(std::make_pair(S->batch[b], off));
+        else S->good += collect(S, fs, nullptr);
+        return;
+    }
+    const char *msg = "device coder failed";
+    if (st == FC_ERR_STATES || st == FC_ERR_CAPACITY) msg = "Maximum number of states reached!";
+    else if (st == FC_ERR_NOROOT) msg = "No root state generated!";
+    else if (st == FC_ERR_QUEUE) msg = "device coder: frame queue gave no slab";
+    else if (st == FC_ERR_COOP) msg = "device coder: the helper workgroups of the frame did not answer";
+    else if (st == FC_ERR_INTERNAL) msg = "device coder: frame exceeds a built-in capacity (recursion depth, snapshot stack or 16384 states)";
+    if (st > FC_ERR_QUEUE) snprintf(job->errmsg, sizeof job->errmsg, "%s (status %d)", msg, st);
+    else snprintf(job->errmsg, sizeof job->errmsg, "%s", msg);
+}
+
+/* wait for the launch and settle every frame of it (frame_outcome) */
+static void complete_wave(Staged *S)
+{
+    if (!download_wave(S)) {
+        const char *why = hipGetErrorString(hipGetLastError());   /* reading it clears it: once */
+        for (size_t b = 0; b < S->batch.size(); b++) {
+            FrameSlot &fs = S->slots[S->batch[b]];
+            snprintf(S->jobs[fs.job].errmsg, sizeof S->jobs[fs.job].errmsg, "HIP error: %s", why);
+            fs.done = true;
+        }
+        S->broken = true;
+        return;
+    }
+    const std::vector<size_t> off = fetch_automata(S);
+    for (size_t b = 0; b < S->batch.size(); b++) frame_outcome(S, b, off[b]);
     (void) hipStreamSynchronize(S->stream);
 }
 

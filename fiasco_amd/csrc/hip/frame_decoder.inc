@@ -27,7 +27,7 @@
  *  HBM-bound integer adds: one 2-byte read per (pixel, term), coalesced along the pixels of an image.
  *
  *  The decoded planes stay on the device (fa_image.dev): the next P/B frame of the sequence takes its
- *  reference frames with a device-to-device copy (stage_slot); the host copy serves every other caller.
+ *  reference frames with a device-to-device copy (upload_reference); the host copy serves every other caller.
  */
 struct DecEdge { int16_t dom, val; };
 struct DecNode { int32_t tree, n; DecEdge e[6]; };                    /* 32 bytes per (state, label) */
