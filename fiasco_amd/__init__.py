@@ -44,7 +44,17 @@ EXPORTED_SYMBOLS = [
     "fiasco_amd_seq_gop_of", "fiasco_amd_seq_ycol_size", "fiasco_amd_seq_initial_level",
     "fiasco_amd_seq_search", "fiasco_amd_seq_gop_result", "fiasco_amd_seq_ycol", "fiasco_amd_seq_write",
     "fiasco_amd_seq_probe",
+    "fiasco_amd_batch_stage_device", "fiasco_amd_batch_upload_device", "fiasco_amd_batch_input_planes",
 ]
+
+# pixel layouts of a frame in device memory (include/libfiasco_amd_hip.h)
+FIASCO_AMD_GRAY8, FIASCO_AMD_RGB8_INTERLEAVED, FIASCO_AMD_RGB8_PLANAR = 0, 1, 2
+
+
+class DeviceFrame(ctypes.Structure):
+    """struct fiasco_amd_device_frame (include/libfiasco_amd_hip.h)."""
+    _fields_ = [("data", ctypes.c_void_p), ("pitch", ctypes.c_size_t), ("plane_stride", ctypes.c_size_t),
+                ("width", ctypes.c_uint), ("height", ctypes.c_uint), ("layout", ctypes.c_int)]
 
 
 class Stats(ctypes.Structure):
@@ -228,9 +238,9 @@ class Batch:
     """Staged batch (fiasco_amd_batch_stage / _encode / _free): inputs stay resident in HBM
     between encode() calls."""
 
-    def __init__(self, lib, pnm_list, quality=20.0, options=None):
+    @staticmethod
+    def _bind(L):
         c = ctypes
-        L = lib.L
         L.fiasco_amd_batch_stage.argtypes = [c.c_uint, c.POINTER(c.c_char_p), c.POINTER(c.c_size_t),
                                              c.c_float, c.c_void_p]
         L.fiasco_amd_batch_stage.restype = c.c_void_p
@@ -241,7 +251,13 @@ class Batch:
         L.fiasco_amd_batch_submit.restype = c.c_int
         L.fiasco_amd_batch_collect.argtypes = [c.c_void_p, c.POINTER(c.c_void_p), c.POINTER(c.c_size_t), c.c_int]
         L.fiasco_amd_batch_collect.restype = c.c_int
+
+    def __init__(self, lib, pnm_list, quality=20.0, options=None):
+        c = ctypes
+        L = lib.L
+        self._bind(L)
         self.lib = lib
+        self._keep = None
         self.n = len(pnm_list)
         bufs = (c.c_char_p * self.n)(*pnm_list)
         lens = (c.c_size_t * self.n)(*[len(b) for b in pnm_list])
@@ -249,6 +265,60 @@ class Batch:
                                                options.handle if options else None)
         if not self.handle:
             raise FiascoError(lib.error_message())
+        self._geom = [_pnm_geometry(p) for p in pnm_list]
+
+    @classmethod
+    def from_device(cls, lib, frames, quality=20.0, options=None, stream=None):
+        """fiasco_amd_batch_stage_device: a batch of frames that already live in device memory.  A frame is a
+        torch uint8 tensor on the GPU or any object with __cuda_array_interface__: H x W is gray, H x W x 3
+        interleaved R, G, B, 3 x H x W planar; pitch and plane stride come from the strides (a slice of a larger
+        tensor is read in place, a stride pattern the C struct cannot express raises FiascoError).  `stream`: the
+        hipStream_t (integer) on which the pixels become ready; None = torch's current stream for torch tensors,
+        else the default stream.  The objects are kept alive until the next upload or free()."""
+        c = ctypes
+        self = cls.__new__(cls)
+        self.lib = lib
+        frames = list(frames)
+        self.n = len(frames)
+        arr = _device_frames(frames)
+        f = lib.L.fiasco_amd_batch_stage_device
+        f.argtypes = [c.c_uint, c.POINTER(DeviceFrame), c.c_void_p, c.c_float, c.c_void_p]
+        f.restype = c.c_void_p
+        cls._bind(lib.L)
+        self.handle = f(self.n, arr, _stream_of(frames, stream), c.c_float(quality), options.handle if options else None)
+        if not self.handle:
+            raise FiascoError(lib.error_message())
+        self._keep = frames
+        self._geom = [(a.width, a.height, 1 if a.layout == FIASCO_AMD_GRAY8 else 3) for a in arr]
+        return self
+
+    def upload_device(self, frames, stream=None):
+        """fiasco_amd_batch_upload_device: new frames for every slot, converted on the device from where they lie
+        (see from_device); not waited for, the next submit / collect(resubmit=True) encodes them."""
+        c = ctypes
+        frames = list(frames)
+        if len(frames) != self.n:
+            raise FiascoError("upload_device: %d frames for a batch of %d" % (len(frames), self.n))
+        arr = _device_frames(frames)
+        f = self.lib.L.fiasco_amd_batch_upload_device
+        f.argtypes = [c.c_void_p, c.POINTER(DeviceFrame), c.c_void_p]
+        f.restype = c.c_int
+        if not f(self.handle, arr, _stream_of(frames, stream)):
+            raise FiascoError(self.lib.error_message())
+        self._keep = frames
+
+    def input_planes(self, i):
+        """fiasco_amd_batch_input_planes: the planes the coder sees for frame i, int16 [bands, h, w] (12.4 fixed point)."""
+        import numpy
+        c = ctypes
+        f = self.lib.L.fiasco_amd_batch_input_planes
+        f.argtypes = [c.c_void_p, c.c_uint, c.c_void_p]
+        f.restype = c.c_int
+        w, h, bands = self._geom[i]          # replacement frames keep the size and colour model of the batch
+        out = numpy.empty((bands, h, w), dtype=numpy.int16)
+        if not f(self.handle, i, out.ctypes.data):
+            raise FiascoError(self.lib.error_message())
+        return out
 
     def upload(self, pnm_list):
         """fiasco_amd_batch_upload: new frames for every slot (host PNM buffers -> pinned ->
@@ -341,6 +411,76 @@ class Batch:
         if self.handle:
             self.lib.L.fiasco_amd_batch_free(self.handle)
             self.handle = None
+        self._keep = None
+
+
+def _pnm_geometry(buf):
+    """(width, height, bands) of raw PGM / PPM bytes (what the C reader finds; a broken header never gets here)."""
+    import re
+    m = re.match(rb"P([56])(?:\s|#[^\n]*\n)*(\d+)(?:\s|#[^\n]*\n)+(\d+)", buf[:4096])
+    return (int(m.group(2)), int(m.group(3)), 1 if m.group(1) == b"5" else 3) if m else None
+
+
+def _device_frames(frames):
+    """The fiasco_amd_device_frame array of a list of GPU arrays (torch tensors, anything with
+    __cuda_array_interface__): layout from the shape, pitch and plane stride from the strides."""
+    arr = (DeviceFrame * max(len(frames), 1))()
+    for i, fr in enumerate(frames):
+        cai = getattr(fr, "__cuda_array_interface__", None)
+        if cai is None:
+            raise FiascoError("frame %d is not in device memory (no __cuda_array_interface__)" % i)
+        if cai["typestr"] not in ("|u1", "<u1", ">u1", "=u1"):
+            raise FiascoError("frame %d: 8-bit unsigned pixels expected, not %s" % (i, cai["typestr"]))
+        shape = tuple(int(v) for v in cai["shape"])
+        strides = cai.get("strides")
+        if strides is None:
+            strides = tuple(_packed_strides(shape))
+        strides = tuple(int(v) for v in strides)
+        d = arr[i]
+        d.data = int(cai["data"][0])
+        bad = None
+        if len(shape) == 2:
+            d.layout, (d.height, d.width) = FIASCO_AMD_GRAY8, shape
+            if strides[1] != 1:
+                bad = "pixels of a row must be adjacent"
+            d.pitch, d.plane_stride = strides[0], 0
+        elif len(shape) == 3 and shape[2] == 3:
+            d.layout, (d.height, d.width) = FIASCO_AMD_RGB8_INTERLEAVED, shape[:2]
+            if strides[2] != 1 or strides[1] != 3:
+                bad = "R, G, B of a pixel and the pixels of a row must be adjacent"
+            d.pitch, d.plane_stride = strides[0], 0
+        elif len(shape) == 3 and shape[0] == 3:
+            d.layout, (d.height, d.width) = FIASCO_AMD_RGB8_PLANAR, shape[1:]
+            if strides[2] != 1:
+                bad = "pixels of a row must be adjacent"
+            d.pitch, d.plane_stride = strides[1], strides[0]
+        else:
+            raise FiascoError("frame %d: shape %s is neither H x W, H x W x 3 nor 3 x H x W" % (i, shape))
+        if bad is None and (min(strides) <= 0):
+            bad = "strides must be positive"
+        if bad:
+            raise FiascoError("frame %d: strides %s cannot be described by pitch and plane stride (%s)" % (i, strides, bad))
+    return arr
+
+
+def _packed_strides(shape):
+    out, n = [], 1
+    for v in reversed(shape):
+        out.append(n)
+        n *= v
+    return reversed(out)
+
+
+def _stream_of(frames, stream):
+    """The hipStream_t to order against: the caller's, else torch's current stream when the frames are torch
+    tensors (torch is looked up, never imported, here), else the default stream."""
+    import sys
+    if stream is not None:
+        return ctypes.c_void_p(int(getattr(stream, "cuda_stream", stream)))
+    torch = sys.modules.get("torch")
+    if torch is not None and frames and isinstance(frames[0], torch.Tensor):
+        return ctypes.c_void_p(torch.cuda.current_stream(frames[0].device).cuda_stream)
+    return None
 
 
 class Sequence:

@@ -804,6 +804,14 @@ struct Staged {
     bool   up_pending = false;
     hipStream_t ustream = nullptr;
     hipEvent_t  ev_up = nullptr;
+    /* frames handed over in device memory (input_convert.inc): the descriptor table of the conversion kernel, pinned
+     * on the host and on the device, the event after its copy, and the staging buffer for sources of another device */
+    struct IcFrame *ic_tab = nullptr, *d_ic = nullptr;
+    size_t ic_cap = 0;
+    hipEvent_t  ev_ic = nullptr;
+    char  *peer_buf = nullptr;
+    size_t peer_bytes = 0;
+    char   ic_failed[200] = "";      /* why the frames of a device-fed batch could not be converted at staging */
     /* frame queue (frame_coder.hip, FC_KERNEL): frames beyond the number of resident workgroups
      * (or beyond what HBM holds in slabs) borrow the slab of whichever workgroup takes them */
     int       lender0 = -1;        /* first slot with a slab of the queue's layout */
@@ -1161,16 +1169,22 @@ static int stage_borrower(Staged *S, FrameSlot &fs, size_t frames_left)
     const size_t npix = (size_t) job->image->width * job->image->height;
     const int bands = job->image->color ? 3 : 1;
     const size_t need = align_up(npix * bands * 2, 256);
-    if (!S->qpix) {
+    if (!S->qpix && !fs.ext_pix) {
         size_t bytes = need * frames_left;
         if (hipMalloc((void **) &S->qpix, bytes) != hipSuccess) { S->qpix = nullptr; (void) hipGetLastError(); return 0; }
         S->qpix_bytes = bytes; S->qpix_used = 0;
     }
-    if (S->qpix_used + need > S->qpix_bytes) return 0;
+    if (!fs.ext_pix && S->qpix_used + need > S->qpix_bytes) return 0;
     fs.base = ref.base;                       /* the layout reference, not an owned slab */
     fill_frame(fs, job);
     fs.base = nullptr; fs.bytes = 0;
     fs.borrow = true;
+    if (fs.ext_pix) {                         /* converted from device memory: the planes are where they stay */
+        fs.F.pix16 = fs.ext_pix;
+        S->borrowers++;
+        fs.staged = true;
+        return 1;
+    }
     fs.ext_pix = (const int16_t *) (S->qpix + S->qpix_used);
     fs.F.pix16 = fs.ext_pix;
     for (int b = 0; b < bands; b++)
@@ -1298,6 +1312,10 @@ static void core1_unstage(void *h)
     if (S->pinned) (void) hipHostFree(S->pinned);
     if (S->ustream) { (void) hipStreamSynchronize(S->ustream); (void) hipStreamDestroy(S->ustream); }
     if (S->ev_up) (void) hipEventDestroy(S->ev_up);
+    if (S->ev_ic) (void) hipEventDestroy(S->ev_ic);
+    if (S->ic_tab) (void) hipHostFree(S->ic_tab);
+    if (S->d_ic) (void) hipFree(S->d_ic);
+    if (S->peer_buf) (void) hipFree(S->peer_buf);
     if (S->up_host && !S->up_host_shared) (void) hipHostFree(S->up_host);
     for (int i = 0; i < 2; i++) if (S->up_dev[i]) (void) hipFree(S->up_dev[i]);
     if (S->ev0) (void) hipEventDestroy(S->ev0);
@@ -1372,7 +1390,7 @@ static void fit_hbm(Staged *S)
     const size_t resident = (size_t) S->ncu * frames_per_cu(probe);
     if (want > resident) want = resident;
     const bool hbm_bound = hipMemGetInfo(&free_b, &total_b) == hipSuccess && probe.L.total * want > free_b + pooled;
-    if ((hbm_bound || S->slots.size() > resident) && queue_eligible(S, probe)) {
+    if ((hbm_bound || S->slots.size() > resident) && queue_eligible(S, probe) && !probe.ext_pix) {
         /* the pixel planes of the frames that will queue for a slab: set aside before the slabs
          * take what HBM has (when HBM is the limit nobody knows yet how many slabs will fit) */
         const fa_image *im = S->jobs[probe.job].image;
@@ -1446,7 +1464,12 @@ static void stage_frames(Staged *S)
     }
 }
 
-static void *core1_stage(unsigned n, fa_job *jobs)
+/* input_convert.inc: the planes of every slot's frame from 8-bit pixels in device memory into up_dev[parity] */
+static bool ic_convert(Staged *S, const fiasco_amd_device_frame *frames, int parity, hipEvent_t ready, bool next, bool prepare_only);
+
+/* frames != NULL: frames[i] is the 8-bit picture of jobs[i] in device memory (jobs[i].image has no host planes), ready
+ * once `ready' has happened */
+static void *core1_stage(unsigned n, fa_job *jobs, const fiasco_amd_device_frame *frames = nullptr, hipEvent_t ready = nullptr)
 {
     Staged *S = new Staged;
     int ndev = 0;
@@ -1489,6 +1512,17 @@ static void *core1_stage(unsigned n, fa_job *jobs)
     }
     for (unsigned i = 0; i < n; i++)
         if (device_supported(&jobs[i], jobs[i].errmsg, sizeof jobs[i].errmsg)) S->slots.push_back(first_guess(S, i));
+    if (frames && !S->slots.empty()) {
+        /* the planes never pass through the host: converted into the buffer the first pass reads, before any slot is
+         * staged (a slot with ext_pix uploads no pixels) */
+        if (!ic_convert(S, frames, S->up_parity, ready, false, false) || hipStreamWaitEvent(S->stream, S->ev_up, 0) != hipSuccess) {
+            snprintf(S->ic_failed, sizeof S->ic_failed, "%s", fiasco_get_error_message());
+            if (!S->ic_failed[0]) snprintf(S->ic_failed, sizeof S->ic_failed, "HIP error: the frames in device memory could not be converted");
+            for (unsigned i = 0; i < n; i++)
+                if (!jobs[i].errmsg[0]) snprintf(jobs[i].errmsg, sizeof jobs[i].errmsg, "%s", fiasco_get_error_message());
+            S->slots.clear();
+        }
+    }
     if (!S->slots.empty()) fit_hbm(S);
     stage_frames(S);
     (void) hipStreamSynchronize(S->stream);
@@ -2511,7 +2545,7 @@ template <typename Fn> static void for_each_share(MultiStaged *M, Fn fn)
     for_shares(share, fn);
 }
 
-extern "C" void *fa_core_stage(unsigned n, fa_job *jobs)
+static void *stage_shares(unsigned n, fa_job *jobs, const fiasco_amd_device_frame *frames, hipEvent_t ready)
 {
     resolve_devices();
     MultiStaged *M = new MultiStaged;
@@ -2523,7 +2557,7 @@ extern "C" void *fa_core_stage(unsigned n, fa_job *jobs)
      * of a video, fa_host.h fa_share_of): the share is a function of the key and of the number of devices ALONE -- not
      * of how many jobs this call happens to hold --, shares without a job get no part */
     if (!keyed && D > n) D = n ? n : 1;
-    if (D == 1) { M->parts.resize(1); for_each_share(M, [&](size_t) { M->parts[0].staged = core1_stage(n, jobs); }); return M; }
+    if (D == 1) { M->parts.resize(1); for_each_share(M, [&](size_t) { M->parts[0].staged = core1_stage(n, jobs, frames, ready); }); return M; }
     {
         std::vector<MultiStaged::Part> all(D);
         for (unsigned i = 0; i < n; i++) all[fa_share_of(jobs[i].share_key, i, (unsigned) D)].idx.push_back(i);
@@ -2533,7 +2567,7 @@ extern "C" void *fa_core_stage(unsigned n, fa_job *jobs)
             /* every job on one share (the last GOPs of a video): ONE part that works on jobs[] itself, on that share */
             M->parts.resize(1);
             M->parts[0].share = used ? only : 0;
-            for_each_share(M, [&](size_t) { M->parts[0].staged = core1_stage(n, jobs); });
+            for_each_share(M, [&](size_t) { M->parts[0].staged = core1_stage(n, jobs, frames, ready); });
             return M;
         }
         for (size_t k = 0; k < D; k++)
@@ -2545,11 +2579,19 @@ extern "C" void *fa_core_stage(unsigned n, fa_job *jobs)
         P.sub.resize(P.idx.size());
         for (size_t j = 0; j < P.idx.size(); j++) P.sub[j] = jobs[P.idx[j]];
     }
-    for_each_share(M, [&](size_t k) { MultiStaged::Part &P = M->parts[k]; P.staged = core1_stage((unsigned) P.sub.size(), P.sub.data()); });
+    std::vector<std::vector<fiasco_amd_device_frame>> subf(frames ? D : 0);     /* every share converts its own frames */
+    for (size_t k = 0; k < subf.size(); k++)
+        for (size_t j = 0; j < M->parts[k].idx.size(); j++) subf[k].push_back(frames[M->parts[k].idx[j]]);
+    for_each_share(M, [&](size_t k) {
+        MultiStaged::Part &P = M->parts[k];
+        P.staged = core1_stage((unsigned) P.sub.size(), P.sub.data(), frames ? subf[k].data() : nullptr, ready);
+    });
     for (size_t k = 0; k < D; k++)                                              /* what staging said about a job */
         for (size_t j = 0; j < M->parts[k].idx.size(); j++) jobs[M->parts[k].idx[j]] = M->parts[k].sub[j];
     return M;
 }
+
+extern "C" void *fa_core_stage(unsigned n, fa_job *jobs) { return stage_shares(n, jobs, nullptr, nullptr); }
 
 extern "C" void fa_core_unstage(void *h)
 {
@@ -2809,3 +2851,4 @@ extern "C" int fiasco_amd_rccl_gather(void *comm, void *stream_, int rank, int w
 }
 
 #include "frame_decoder.inc"
+#include "input_convert.inc"

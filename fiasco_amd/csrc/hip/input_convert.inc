@@ -1,0 +1,472 @@
+/*
+ *  input_convert.inc -- frames that already live in device memory (included by core_hip.cpp).
+ *
+ *  The PNM entries parse a header on the host, convert every pixel there (host/fa_image.c convert_planes, reference
+ *  lib/image.c:365-389) and copy the 12.4 fixed-point planes through pinned memory into HBM.  Here the 8-bit pixels
+ *  are in HBM already: ONE launch of ic_convert_kernel per device share writes the planes of all its frames into the
+ *  input buffer that the hand-over of replacement frames uses anyway (Staged::up_dev, FrameSlot::ext_pix / ext_next).
+ *  The host never sees a pixel; fa_image_host_planes() fetches planes back for the few calls that want them.
+ *
+ *  Arithmetic: exactly convert_planes().  gray (g - 128) * 16; colour the three sums in double, evaluated left to
+ *  right, * 16 last, truncated toward zero to int and narrowed.  Nothing may be contracted into a fused multiply-add:
+ *  the file is built with -ffp-contract=off and the function says so again.
+ *
+ *  Shape: a work item is 16 neighbouring pixels of one row -- one 16-byte load per 8-bit plane (three for interleaved
+ *  RGB) where the address allows it, byte loads otherwise (a ragged row end, a source that starts at an odd column),
+ *  and 32 bytes of int16 per band, stored as 16-byte vectors (8- or 4-byte ones where a row of the plane does not start
+ *  on a 16-byte boundary).  Neighbouring lanes take neighbouring items, so a wave reads 1 KiB and writes 2 KiB per
+ *  band contiguously.  The items of all frames form one sequence (IcFrame::first = items before the frame); the grid
+ *  is sized from the CU count and every workgroup of 256 takes one contiguous stretch of the sequence, so the frame
+ *  of an item is found by one search per workgroup and a step forward now and then.
+ */
+
+struct IcFrame {
+    const unsigned char *src;        /* first pixel */
+    int16_t            *dst;         /* planes [bands][height][width] */
+    unsigned long long  pitch, plane_stride;
+    unsigned long long  first;       /* work items of the frames before this one */
+    unsigned            width, height, layout, cpr;    /* cpr: items per row */
+};
+
+/* sources and planes come out of the descriptor table: the compiler cannot see that they are global memory and would
+ * use flat loads and stores */
+#define IC_GLOBAL __attribute__((address_space(1)))
+typedef unsigned ic_u4 __attribute__((ext_vector_type(4)));
+typedef unsigned ic_u2 __attribute__((ext_vector_type(2)));
+
+/* 16 bytes from p as four words: one vector load, or `n' byte loads (the rest reads as zero) */
+static __device__ __forceinline__ void ic_load16(const unsigned char *p, unsigned n, unsigned w[4])
+{
+    if (n == 16 && ((size_t) p & 15) == 0) {
+        const ic_u4 v = *(const IC_GLOBAL ic_u4 *) p;
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+        return;
+    }
+    w[0] = w[1] = w[2] = w[3] = 0;
+#pragma unroll
+    for (unsigned k = 0; k < 16; k++)
+        if (k < n) w[k >> 2] |= (unsigned) ((const IC_GLOBAL unsigned char *) p)[k] << (8 * (k & 3));
+}
+
+/* 16 values (`n' of them valid, n even) as packed pairs to q, which is 4-byte aligned */
+static __device__ __forceinline__ void ic_store16(int16_t *q, unsigned n, const unsigned v[8])
+{
+    if (n == 16 && ((size_t) q & 15) == 0) {
+        ((IC_GLOBAL ic_u4 *) q)[0] = ic_u4{ v[0], v[1], v[2], v[3] };
+        ((IC_GLOBAL ic_u4 *) q)[1] = ic_u4{ v[4], v[5], v[6], v[7] };
+    } else if (n == 16 && ((size_t) q & 7) == 0) {
+#pragma unroll
+        for (unsigned k = 0; k < 4; k++) ((IC_GLOBAL ic_u2 *) q)[k] = ic_u2{ v[2 * k], v[2 * k + 1] };
+    } else {
+#pragma unroll
+        for (unsigned k = 0; k < 8; k++)
+            if (2 * k < n) ((IC_GLOBAL unsigned *) q)[k] = v[k];
+    }
+}
+
+static __device__ __forceinline__ unsigned ic_byte(const unsigned *w, unsigned k) { return (w[k >> 2] >> (8 * (k & 3))) & 255u; }
+static __device__ __forceinline__ unsigned ic_pair(int lo, int hi) { return ((unsigned) lo & 0xffffu) | ((unsigned) hi << 16); }
+
+__global__ void __launch_bounds__(256) ic_convert_kernel(const IcFrame *__restrict__ frames, unsigned nframes, unsigned long long total)
+{
+#pragma clang fp contract(off)
+    const unsigned long long tiles = (total + 255) / 256;
+    const unsigned long long t0 = tiles * blockIdx.x / gridDim.x, t1 = tiles * (blockIdx.x + 1) / gridDim.x;
+    if (t0 >= t1) return;
+    unsigned f = 0;
+    {   /* the frame of the stretch's first item: the last one that starts at or before it */
+        unsigned lo = 0, hi = nframes;
+        while (hi - lo > 1) {
+            const unsigned mid = (lo + hi) / 2;
+            if (frames[mid].first <= t0 * 256) lo = mid; else hi = mid;
+        }
+        f = lo;
+    }
+    for (unsigned long long t = t0; t < t1; t++) {
+        const unsigned long long it = t * 256 + threadIdx.x;
+        if (it >= total) break;
+        while (f + 1 < nframes && frames[f + 1].first <= it) f++;
+        const IcFrame F = frames[f];
+        const unsigned local = (unsigned) (it - F.first);
+        const unsigned row = local / F.cpr, x0 = (local - row * F.cpr) * 16;
+        const unsigned n = F.width - x0 < 16 ? F.width - x0 : 16;
+        const size_t npix = (size_t) F.width * F.height;
+        int16_t *q = F.dst + (size_t) row * F.width + x0;
+        const unsigned char *p = F.src + (size_t) row * F.pitch;
+        unsigned out[8];
+        if (F.layout == FIASCO_AMD_GRAY8) {
+            unsigned w[4];
+            ic_load16(p + x0, n, w);
+#pragma unroll
+            for (unsigned k = 0; k < 8; k++)
+                out[k] = ic_pair(((int) ic_byte(w, 2 * k) - 128) * 16, ((int) ic_byte(w, 2 * k + 1) - 128) * 16);
+            ic_store16(q, n, out);
+            continue;
+        }
+        unsigned w[12];
+        if (F.layout == FIASCO_AMD_RGB8_INTERLEAVED) {
+            const unsigned char *s = p + (size_t) x0 * 3;
+            const unsigned nb = n * 3;
+            ic_load16(s, nb >= 16 ? 16 : nb, w);
+            ic_load16(s + 16, nb >= 32 ? 16 : nb > 16 ? nb - 16 : 0, w + 4);
+            ic_load16(s + 32, nb >= 48 ? 16 : nb > 32 ? nb - 32 : 0, w + 8);
+        } else {
+            ic_load16(p + x0, n, w);
+            ic_load16(p + F.plane_stride + x0, n, w + 4);
+            ic_load16(p + 2 * F.plane_stride + x0, n, w + 8);
+        }
+        int y[16], cb[16], cr[16];
+#pragma unroll
+        for (unsigned k = 0; k < 16; k++) {
+            int r, g, bl;
+            if (F.layout == FIASCO_AMD_RGB8_INTERLEAVED) { r = (int) ic_byte(w, 3 * k); g = (int) ic_byte(w, 3 * k + 1); bl = (int) ic_byte(w, 3 * k + 2); }
+            else { r = (int) ic_byte(w, k); g = (int) ic_byte(w + 4, k); bl = (int) ic_byte(w + 8, k); }
+            /* host/fa_image.c:108-110, character for character: double arithmetic, left to right, C truncation */
+            y[k]  = (int) ((+0.2989 * r + 0.5866 * g + 0.1145 * bl - 128) * 16);
+            cb[k] = (int) ((-0.1687 * r - 0.3312 * g + 0.5000 * bl) * 16);
+            cr[k] = (int) ((+0.5000 * r - 0.4183 * g - 0.0816 * bl) * 16);
+        }
+#pragma unroll
+        for (unsigned k = 0; k < 8; k++) out[k] = ic_pair(y[2 * k], y[2 * k + 1]);
+        ic_store16(q, n, out);
+#pragma unroll
+        for (unsigned k = 0; k < 8; k++) out[k] = ic_pair(cb[2 * k], cb[2 * k + 1]);
+        ic_store16(q + npix, n, out);
+#pragma unroll
+        for (unsigned k = 0; k < 8; k++) out[k] = ic_pair(cr[2 * k], cr[2 * k + 1]);
+        ic_store16(q + 2 * npix, n, out);
+    }
+}
+
+/* ------------------------------------------------------------------ one share */
+
+static size_t ic_row_bytes(const fiasco_amd_device_frame &f) { return (size_t) f.width * (f.layout == FIASCO_AMD_RGB8_INTERLEAVED ? 3 : 1); }
+/* bytes from the first to behind the last pixel (pitch and plane_stride filled in) */
+static size_t ic_extent(const fiasco_amd_device_frame &f)
+{
+    return (f.layout == FIASCO_AMD_RGB8_PLANAR ? 2 * f.plane_stride : 0) + (size_t) (f.height - 1) * f.pitch + ic_row_bytes(f);
+}
+
+/* The planes of every slot's frame into up_dev[parity], by one kernel launch on the upload stream after `ready'.
+ * frames[j] belongs to jobs[j]; pitch and plane_stride are filled in and everything was checked (ic_check_frame).
+ * next: the frames of the NEXT pass (ext_next, taken over by the next submit), else of the first pass (ext_pix).
+ * Records ev_up behind the kernel.  Nothing here waits on the host for the device, but for the descriptor table of
+ * the upload before this one, which a whole pass ago left the pinned memory.
+ * prepare_only: everything that can run out of memory -- stream, events, the input buffer, the staging buffer, the
+ * descriptor table -- and nothing else: no buffer is written, no slot changed.  fiasco_amd_batch_upload_device() prepares
+ * every share before any share converts, so that a share without memory refuses the upload while the batch is whole. */
+static bool ic_convert(Staged *S, const fiasco_amd_device_frame *frames, int parity, hipEvent_t ready, bool next, bool prepare_only)
+{
+    const size_t ns = S->slots.size();
+    if (!ns) return true;
+    if (!S->ustream && hipStreamCreateWithFlags(&S->ustream, hipStreamNonBlocking) != hipSuccess) { S->ustream = nullptr; goto hip_failed; }
+    if (!S->ev_up && hipEventCreateWithFlags(&S->ev_up, hipEventDisableTiming) != hipSuccess) { S->ev_up = nullptr; goto hip_failed; }
+    if (!S->ev_ic && hipEventCreateWithFlags(&S->ev_ic, hipEventDisableTiming) != hipSuccess) { S->ev_ic = nullptr; goto hip_failed; }
+    {
+        int here = -1;
+        if (hipGetDevice(&here) != hipSuccess) goto hip_failed;
+        size_t need = 0, peer_need = 0;
+        std::vector<int> srcdev(ns, here);
+        for (size_t k = 0; k < ns; k++) {
+            const fa_image *im = S->jobs[S->slots[k].job].image;
+            const fiasco_amd_device_frame &f = frames[S->slots[k].job];
+            hipPointerAttribute_t at;
+            need += align_up((size_t) im->width * im->height * (im->color ? 3 : 1) * 2, 256);
+            if (hipPointerGetAttributes(&at, f.data) == hipSuccess) srcdev[k] = at.device; else (void) hipGetLastError();
+            if (srcdev[k] != here) peer_need += align_up(ic_extent(f), 256);
+        }
+        if (!grow_buffer(S->up_dev[parity], S->up_dev_bytes[parity], need)
+            || (peer_need && !grow_buffer(S->peer_buf, S->peer_bytes, peer_need))) {
+            fa_set_error("out of HBM: no room for %.1f MiB of frames", (need + peer_need) / 1048576.0);
+            return false;
+        }
+        if (ns > S->ic_cap) {
+            if (S->ic_tab) (void) hipHostFree(S->ic_tab);
+            if (S->d_ic) (void) hipFree(S->d_ic);
+            S->ic_tab = S->d_ic = nullptr; S->ic_cap = 0;
+            if (hipHostMalloc((void **) &S->ic_tab, ns * sizeof(IcFrame), hipHostMallocDefault) != hipSuccess
+                || hipMalloc((void **) &S->d_ic, ns * sizeof(IcFrame)) != hipSuccess) goto hip_failed;
+            S->ic_cap = ns;
+        }
+        if (prepare_only) return true;
+        if (hipEventSynchronize(S->ev_ic) != hipSuccess) goto hip_failed;
+        if (hipStreamWaitEvent(S->ustream, ready, 0) != hipSuccess) goto hip_failed;
+        unsigned long long total = 0;
+        size_t at = 0, peer_at = 0;
+        for (size_t k = 0; k < ns; k++) {
+            const fa_image *im = S->jobs[S->slots[k].job].image;
+            const fiasco_amd_device_frame &f = frames[S->slots[k].job];
+            IcFrame &d = S->ic_tab[k];
+            d.src = (const unsigned char *) f.data;
+            if (srcdev[k] != here) {
+                /* a source on another device: its bytes, rows and gaps as they lie, over the peer link first */
+                if (hipMemcpyPeerAsync(S->peer_buf + peer_at, here, f.data, srcdev[k], ic_extent(f), S->ustream) != hipSuccess) goto hip_failed;
+                d.src = (const unsigned char *) S->peer_buf + peer_at;
+                peer_at += align_up(ic_extent(f), 256);
+            }
+            d.dst = (int16_t *) (S->up_dev[parity] + at);
+            d.pitch = f.pitch; d.plane_stride = f.plane_stride; d.first = total;
+            d.width = f.width; d.height = f.height; d.layout = (unsigned) f.layout; d.cpr = (f.width + 15) / 16;
+            total += (unsigned long long) d.cpr * f.height;
+            at += align_up((size_t) im->width * im->height * (im->color ? 3 : 1) * 2, 256);
+        }
+        if (hipMemcpyAsync(S->d_ic, S->ic_tab, ns * sizeof(IcFrame), hipMemcpyHostToDevice, S->ustream) != hipSuccess
+            || hipEventRecord(S->ev_ic, S->ustream) != hipSuccess) goto hip_failed;
+        /* eight workgroups of four waves per CU, fewer when the work is less */
+        unsigned long long grid = (unsigned long long) S->ncu * 8, tiles = (total + 255) / 256;
+        if (grid > tiles) grid = tiles;
+        ic_convert_kernel<<<dim3((unsigned) grid), dim3(256), 0, S->ustream>>>(S->d_ic, (unsigned) ns, total);
+        if (hipGetLastError() != hipSuccess || hipEventRecord(S->ev_up, S->ustream) != hipSuccess) goto hip_failed;
+        for (size_t k = 0; k < ns; k++) {
+            FrameSlot &fs = S->slots[k];
+            fa_image *im = (fa_image *) S->jobs[fs.job].image;
+            const int16_t *planes = S->ic_tab[k].dst;
+            if (next) fs.ext_next = planes; else { fs.ext_pix = planes; fs.F.pix16 = planes; }
+            im->src_dev = planes; im->src_dev_id = here; im->src_owner = S;
+        }
+        if (next) S->up_pending = true;
+    }
+    return true;
+hip_failed:
+    fa_set_error("HIP error: %s", hipGetErrorString(hipGetLastError()));
+    return false;
+}
+
+/* fa_image_fetch (fa_host.h): the planes of a device-fed frame into im->pixels[], which fa_image_host_planes allocated */
+static int ic_fetch(fa_image *im)
+{
+    Staged *S = (Staged *) im->src_owner;
+    const size_t npix = (size_t) im->width * im->height;
+    int cur = -1, ok = 1;
+    if (hipGetDevice(&cur) != hipSuccess) { (void) hipGetLastError(); cur = -1; }
+    if (im->src_dev_id >= 0 && cur != im->src_dev_id) (void) hipSetDevice(im->src_dev_id);
+    if (S && S->ustream) ok = hipStreamSynchronize(S->ustream) == hipSuccess;       /* the conversion may still run */
+    for (int b = 0; ok && b < (im->color ? 3 : 1); b++)
+        ok = hipMemcpy(im->pixels[b], im->src_dev + (size_t) b * npix, npix * 2, hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) fa_set_error("HIP error: %s", hipGetErrorString(hipGetLastError()));
+    if (cur >= 0 && im->src_dev_id >= 0 && cur != im->src_dev_id) (void) hipSetDevice(cur);
+    return ok;
+}
+
+/* ------------------------------------------------------------------ the entry points (include/libfiasco_amd_hip.h) */
+
+/* one caller's frame: the size rules and messages of the PNM reader, pitch, layout, and that its rows lie in device
+ * memory.  *out = the frame with pitch and plane_stride filled in. */
+static bool ic_check_frame(unsigned i, const fiasco_amd_device_frame *in, fiasco_amd_device_frame *out)
+{
+    char name[32];
+    snprintf(name, sizeof name, "<device frame %u>", i);
+    *out = *in;
+    if (in->layout != FIASCO_AMD_GRAY8 && in->layout != FIASCO_AMD_RGB8_INTERLEAVED && in->layout != FIASCO_AMD_RGB8_PLANAR) {
+        fa_set_error("%s: unknown pixel layout %d.", name, in->layout);
+        return false;
+    }
+    if (!fa_image_check_size(in->width, in->height, name)) return false;
+    const size_t row = ic_row_bytes(*in);
+    if (!out->pitch) out->pitch = row;
+    if (out->pitch < row) {
+        fa_set_error("%s: pitch of %lu bytes is smaller than a row of %lu bytes.", name, (unsigned long) out->pitch, (unsigned long) row);
+        return false;
+    }
+    if (!out->plane_stride) out->plane_stride = out->pitch * in->height;
+    hipPointerAttribute_t at;
+    if (!in->data || hipPointerGetAttributes(&at, in->data) != hipSuccess || at.type != hipMemoryTypeDevice) {
+        (void) hipGetLastError();
+        fa_set_error("%s: the pixels are not in device memory.", name);
+        return false;
+    }
+    {   /* every row inside the allocation the pointer belongs to (the kernel reads what the descriptor says) */
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) in->data) != hipSuccess) (void) hipGetLastError();
+        else if ((const char *) in->data + ic_extent(*out) > (const char *) base + size) {
+            fa_set_error("%s: the rows reach %lu bytes beyond the end of their device allocation.", name,
+                         (unsigned long) ((const char *) in->data + ic_extent(*out) - ((const char *) base + size)));
+            return false;
+        }
+    }
+    return true;
+}
+
+static bool ic_have_device(void)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) return true;
+    (void) hipGetLastError();
+    fa_set_error("libfiasco_amd: no HIP device available (the hot path has no CPU fallback)");
+    return false;
+}
+
+/* the event that says "what `stream' holds now is done"; the caller destroys it (the waits hold on to what they need) */
+static hipEvent_t ic_mark_ready(void *stream)
+{
+    hipEvent_t ev = nullptr;
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, (hipStream_t) stream) != hipSuccess) {
+        fa_set_error("HIP error: %s", hipGetErrorString(hipGetLastError()));
+        if (ev) (void) hipEventDestroy(ev);
+        return nullptr;
+    }
+    return ev;
+}
+
+/* the caller's stream waits for the conversions of every share: the source may then be reused in stream order */
+static void ic_release_source(MultiStaged *M, void *stream)
+{
+    for (size_t k = 0; k < M->parts.size(); k++) {
+        Staged *S = (Staged *) M->parts[k].staged;
+        if (S && S->ev_up && hipStreamWaitEvent((hipStream_t) stream, S->ev_up, 0) != hipSuccess) (void) hipGetLastError();
+    }
+}
+
+extern "C" fiasco_amd_batch_t *fiasco_amd_batch_stage_device(unsigned n, const fiasco_amd_device_frame *frames, void *stream,
+                                                             float quality, const fiasco_c_options_t *options)
+{
+    fiasco_c_options_t *defaults = nullptr;
+    const fa_options *op;
+    fiasco_amd_batch_t *b = nullptr;
+    hipEvent_t ready = nullptr;
+    std::vector<fiasco_amd_device_frame> fr(n);
+    bool ok = false;
+
+    if (!n || !frames) { fa_set_error("No frames to stage."); return nullptr; }
+    if (quality <= 0) { fa_set_error("Compression quality has to be positive."); return nullptr; }
+    if (!ic_have_device()) return nullptr;
+    for (unsigned i = 0; i < n; i++) if (!ic_check_frame(i, &frames[i], &fr[i])) return nullptr;
+    if (options) { op = fa_cast_options(options); if (!op) return nullptr; }
+    else { defaults = fiasco_c_options_new(); if (!defaults) return nullptr; op = fa_cast_options(defaults); }
+    b = (fiasco_amd_batch_t *) calloc(1, sizeof *b);
+    if (b) {
+        b->jobs  = (fa_job *) calloc(n, sizeof *b->jobs);
+        b->ims   = (fa_image **) calloc(n, sizeof *b->ims);
+        b->infos = (fa_info *) calloc(n, sizeof *b->infos);
+    }
+    if (!b || !b->jobs || !b->ims || !b->infos) { fa_set_error("Out of memory!"); goto done; }
+    b->n = n;
+    b->normal_domains = op->normal_domains;
+    b->delta_domains  = op->delta_domains;
+    b->prediction     = op->prediction;
+    for (unsigned i = 0; i < n; i++) {
+        fa_cparams cp;
+        b->ims[i] = (fa_image *) calloc(1, sizeof(fa_image));           /* no host planes: fa_image_host_planes */
+        if (!b->ims[i]) { fa_set_error("Out of memory!"); goto done; }
+        b->ims[i]->width = fr[i].width; b->ims[i]->height = fr[i].height; b->ims[i]->color = fr[i].layout != FIASCO_AMD_GRAY8;
+        if (!fa_setup_params(op, quality, fr[i].width, fr[i].height, b->ims[i]->color, 1, &b->infos[i], &cp)
+            || !fa_prepare_job(&b->jobs[i], b->ims[i], &cp, op->basis_name)) goto done;
+    }
+    fa_image_fetch = ic_fetch;
+    ready = ic_mark_ready(stream);
+    if (!ready) goto done;
+    b->staged = stage_shares(n, b->jobs, fr.data(), ready);
+    ic_release_source((MultiStaged *) b->staged, stream);
+    ok = true;
+    for (size_t k = 0; k < ((MultiStaged *) b->staged)->parts.size(); k++) {
+        /* a share that could not convert its frames (no memory, a device error): NULL + message, like a PNM that
+         * cannot be read.  What the device coder refuses for a frame's options stays a per-frame message. */
+        const Staged *S = (const Staged *) ((MultiStaged *) b->staged)->parts[k].staged;
+        if (S && S->ic_failed[0]) { fa_set_error("%s", S->ic_failed); ok = false; }
+    }
+done:
+    if (ready) (void) hipEventDestroy(ready);
+    if (defaults) fiasco_c_options_delete(defaults);
+    if (!ok) { fiasco_amd_batch_free(b); b = nullptr; }
+    return b;
+}
+
+/* what fiasco_amd_batch_upload_device() keeps of one share, to put it back when a share fails */
+struct IcShareUndo {
+    std::vector<fiasco_amd_device_frame> frames;    /* the share's frames in the order of its jobs (several shares) */
+    std::vector<const fa_image *>        image;     /* jobs[].image before */
+    std::vector<const int16_t *>         ext_next;  /* slots[].ext_next before */
+    bool up_pending = false;
+    bool good = false;
+    char why[256] = "";                             /* the share's message: the error message is per thread */
+};
+
+extern "C" int fiasco_amd_batch_upload_device(fiasco_amd_batch_t *b, const fiasco_amd_device_frame *frames, void *stream)
+{
+    if (!b || !b->staged || !b->n) { fa_set_error("Batch is not staged."); return 0; }
+    if (!frames) { fa_set_error("No frames to stage."); return 0; }
+    MultiStaged *M = (MultiStaged *) b->staged;
+    std::vector<fiasco_amd_device_frame> fr(b->n);
+    for (unsigned i = 0; i < b->n; i++) {
+        const fa_image *old = b->ims[i];
+        if (!ic_check_frame(i, &frames[i], &fr[i])) return 0;
+        if (fr[i].width != old->width || fr[i].height != old->height || (fr[i].layout != FIASCO_AMD_GRAY8) != (old->color != 0)) {
+            fa_set_error("`<device frame %u>': replacement frames must keep the size and colour model of the batch.", i);
+            return 0;
+        }
+    }
+    for (size_t k = 0; k < M->parts.size(); k++) {
+        const Staged *S = (const Staged *) M->parts[k].staged;
+        if (!S || !S->ok) { fa_set_error("Batch is not staged."); return 0; }
+    }
+    fa_image **nims = (fa_image **) calloc(b->n, sizeof *nims);
+    hipEvent_t ready = nims ? ic_mark_ready(stream) : nullptr;
+    bool ok = nims && ready;
+    if (!nims) fa_set_error("Out of memory!");
+    for (unsigned i = 0; ok && i < b->n; i++) {
+        nims[i] = (fa_image *) calloc(1, sizeof(fa_image));
+        if (!nims[i]) { fa_set_error("Out of memory!"); ok = false; break; }
+        nims[i]->width = fr[i].width; nims[i]->height = fr[i].height; nims[i]->color = fr[i].layout != FIASCO_AMD_GRAY8;
+    }
+    if (ok) {
+        /* the shares convert the frames of THEIR jobs.  First every share gets its memory (nothing is written: a share
+         * that has none refuses the upload and the batch is whole), then every share converts.  A device error after
+         * that puts the slots and the images back as they were; the planes of an earlier upload that no submit had
+         * taken over yet may be overwritten by then, and the error says so. */
+        const bool one = M->parts.size() == 1;
+        std::vector<IcShareUndo> sh(M->parts.size());
+        for (size_t k = 0; k < M->parts.size(); k++) {
+            Staged *S = (Staged *) M->parts[k].staged;
+            for (unsigned j = 0; j < S->n; j++) {
+                const unsigned i = one ? j : M->parts[k].idx[j];
+                sh[k].image.push_back(S->jobs[j].image);
+                S->jobs[j].image = nims[i];
+                if (!one) sh[k].frames.push_back(fr[i]);
+            }
+            for (size_t j = 0; j < S->slots.size(); j++) sh[k].ext_next.push_back(S->slots[j].ext_next);
+            sh[k].up_pending = S->up_pending;
+        }
+        /* one step of every share; false and the message of a share that failed */
+        auto all_shares = [&](bool prepare_only) {
+            for_each_share(M, [&](size_t k) {
+                Staged *S = (Staged *) M->parts[k].staged;
+                sh[k].good = ic_convert(S, one ? fr.data() : sh[k].frames.data(), S->up_parity ^ 1, ready, true, prepare_only);
+                if (!sh[k].good) snprintf(sh[k].why, sizeof sh[k].why, "%s", fiasco_get_error_message());
+            });
+            bool all = true;
+            for (size_t k = 0; k < M->parts.size(); k++)
+                if (!sh[k].good) {
+                    all = false;
+                    fa_set_error("%s%s", sh[k].why, !prepare_only && sh[k].up_pending ? " (the frames of the upload before, not yet submitted, are lost)" : "");
+                }
+            return all;
+        };
+        ok = all_shares(true);
+        const bool touched = ok;
+        if (ok) ok = all_shares(false);
+        if (!ok)
+            for (size_t k = 0; k < M->parts.size(); k++) {
+                Staged *S = (Staged *) M->parts[k].staged;
+                for (unsigned j = 0; j < S->n; j++) S->jobs[j].image = sh[k].image[j];
+                for (size_t j = 0; touched && j < S->slots.size(); j++) S->slots[j].ext_next = sh[k].ext_next[j];
+                if (touched) S->up_pending = sh[k].up_pending;
+            }
+        ic_release_source(M, stream);
+    }
+    if (ready) (void) hipEventDestroy(ready);
+    if (!ok) {
+        if (nims) for (unsigned i = 0; i < b->n; i++) free(nims[i]);
+        free(nims);
+        return 0;
+    }
+    fa_image_fetch = ic_fetch;
+    if (b->prev_ims) {
+        for (unsigned i = 0; i < b->n; i++) fa_image_free(b->prev_ims[i]);
+        free(b->prev_ims);
+    }
+    b->prev_ims = b->ims;                      /* alive until the next upload */
+    b->ims = nims;
+    for (unsigned i = 0; i < b->n; i++) b->jobs[i].image = nims[i];
+    return 1;
+}

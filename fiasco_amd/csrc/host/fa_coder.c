@@ -201,7 +201,7 @@ bad:
 
 /* ---------------------------------------------------------------- one still -> bytes */
 
-static int prepare_job(fa_job *job, const fa_image *im, const fa_cparams *cp, const char *basis)
+int fa_prepare_job(fa_job *job, const fa_image *im, const fa_cparams *cp, const char *basis)
 {
     memset(job, 0, sizeof *job);
     job->image = im;
@@ -329,16 +329,7 @@ done:
 
 /* ---------------------------------------------------------------- public: batch */
 
-struct fiasco_amd_batch {
-    unsigned   n;
-    fa_job    *jobs;
-    fa_image **ims;
-    fa_image **prev_ims;      /* frames of the pass before the last upload: a pass that was
-                               * submitted with them may still be in flight */
-    fa_info   *infos;
-    int        normal_domains, delta_domains, prediction;
-    void      *staged;        /* core handle: inputs resident where the core computes */
-};
+/* struct fiasco_amd_batch: fa_host.h (the device-input entry points of the core fill one too) */
 
 int fiasco_amd_batch_stats(const fiasco_amd_batch_t *b, unsigned i, unsigned band,
                            float *costs, float *err, unsigned *width, unsigned *height)
@@ -410,6 +401,7 @@ int fiasco_amd_batch_decode_psnr(const fiasco_amd_batch_t *b, unsigned i, double
         fa_set_error("fiasco_amd_batch_decode_psnr: intra frames only (a P/B frame needs its reference frames)");
         return 0;
     }
+    if (!fa_image_host_planes(b->jobs[i].image)) return 0;     /* a frame that lives on the device: fetched now */
     dec = decode_job(&b->jobs[i]);
     if (!dec) return 0;
     psnr_of(b->jobs[i].image, dec, psnr_db, mse);
@@ -437,6 +429,7 @@ int fiasco_amd_batch_decode_psnr_all(const fiasco_amd_batch_t *b, double *psnr_d
     for (i = 0; i < b->n; i++) {
         const fa_job *job = &b->jobs[i];
         if (!job->status || !job->wfa || job->frame_type != FA_I_FRAME) { d[i].skip = 1; continue; }
+        if (!fa_image_host_planes(job->image)) { free(d); return 0; }      /* as fiasco_amd_batch_decode_psnr: 0 + message */
         d[i].wfa = job->wfa; d[i].width = job->image->width; d[i].height = job->image->height; d[i].color = job->image->color;
         d[i].frame_type = FA_I_FRAME;
     }
@@ -494,6 +487,21 @@ int fiasco_amd_batch_decode_plane(const fiasco_amd_batch_t *b, unsigned i, unsig
     return 1;
 }
 
+/* include/libfiasco_amd_hip.h: the planes the coder sees for frame i, all bands back to back; a frame that lives on
+ * the device is fetched (fa_image_host_planes) */
+int fiasco_amd_batch_input_planes(const fiasco_amd_batch_t *b, unsigned i, int16_t *out)
+{
+    const fa_image *im;
+    size_t npix;
+    int band;
+    if (!b || i >= b->n || !out) { fa_set_error("fiasco_amd_batch_input_planes: no frame %u", i); return 0; }
+    im = b->ims[i];
+    npix = (size_t) im->width * im->height;
+    if (!fa_image_host_planes(im)) return 0;
+    for (band = 0; band < (im->color ? 3 : 1); band++) memcpy(out + (size_t) band * npix, im->pixels[band], npix * 2);
+    return 1;
+}
+
 void fiasco_amd_batch_free(fiasco_amd_batch_t *b)
 {
     unsigned i;
@@ -542,7 +550,7 @@ fiasco_amd_batch_t *fiasco_amd_batch_stage(unsigned n, const unsigned char *cons
         b->ims[i] = fa_image_from_pnm(pnm[i], pnm_len[i], "<memory>");
         if (!b->ims[i] || !fa_setup_params(op, quality, b->ims[i]->width, b->ims[i]->height,
                                           b->ims[i]->color, 1, &b->infos[i], &cp)
-            || !prepare_job(&b->jobs[i], b->ims[i], &cp, op->basis_name)) {
+            || !fa_prepare_job(&b->jobs[i], b->ims[i], &cp, op->basis_name)) {
             if (defaults) fiasco_c_options_delete(defaults);
             fiasco_amd_batch_free(b);
             return NULL;

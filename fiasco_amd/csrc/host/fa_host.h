@@ -97,6 +97,12 @@ typedef struct fa_image {
     void    *dev;            /* decoded frames: the same planes [bands][height][width] on device dev_id, or NULL
                                 (fa_core_decode_frames; released by fa_image_free through fa_core_release_dev) */
     int      dev_id;
+    /* frames that were handed over in device memory (fiasco_amd_batch_stage_device / _upload_device): the converted
+     * planes [bands][height][width] inside the core's input buffer on device src_dev_id, borrowed.  Such a frame
+     * has no host planes (pixels[] NULL) until somebody asks for them: fa_image_host_planes() */
+    const int16_t *src_dev;
+    int      src_dev_id;
+    void    *src_owner;      /* the core's handle of the share that holds src_dev */
 } fa_image;
 /* parse raw P5/P6 from memory; returns NULL + error message on failure */
 fa_image *fa_image_from_pnm(const unsigned char *buf, size_t len, const char *name);
@@ -106,6 +112,15 @@ int       fa_pnm_header(const unsigned char *buf, size_t len, const char *name,
                         unsigned *w, unsigned *h, int *color, size_t *data_off);
 void      fa_image_free(fa_image *im);
 fa_image *fa_image_alloc(unsigned width, unsigned height, int color);   /* zeroed planes */
+/* the geometry rules of read_pnmheader / read_image (lib/image.c:194-195, :316-323) for a frame that does not come
+ * from a PNM header; 0 + the reader's message */
+int       fa_image_check_size(unsigned width, unsigned height, const char *name);
+/* Host planes on demand.  The host never reads input pixels while it encodes; only the decoded-PSNR calls and
+ * fiasco_amd_batch_input_planes() do.  For a frame that lives on the device the planes are allocated here and
+ * filled by fa_image_fetch, which the product's core sets (the host C names no core function: the test oracle
+ * links the same files).  1 ok / 0 + message. */
+extern int (*fa_image_fetch)(fa_image *im);
+int       fa_image_host_planes(const fa_image *im);
 
 /* ---------------- reconstruction (reference codec/decoder.c, codec/motion.c) ------- */
 unsigned char *fa_read_whole_file(const char *name, const char *env_var, size_t *len);
@@ -340,6 +355,18 @@ void     fa_seq_ycol_resolve(uint8_t *chain, const uint8_t *raw, unsigned n);
 int      fa_seq_write(fa_seq *s, unsigned k, const uint8_t *ycol, fa_bitw *out);
 
 /* ---------------- frame driver pieces shared by fiasco_coder and the batch API ----- */
+struct fiasco_amd_batch {
+    unsigned   n;
+    fa_job    *jobs;
+    fa_image **ims;
+    fa_image **prev_ims;      /* frames of the pass before the last upload: a pass that was
+                               * submitted with them may still be in flight */
+    fa_info   *infos;
+    int        normal_domains, delta_domains, prediction;
+    void      *staged;        /* core handle: inputs resident where the core computes */
+};
+/* the job of one still: the automaton with the initial basis loaded (1 ok / 0 + message) */
+int fa_prepare_job(fa_job *job, const fa_image *im, const fa_cparams *cp, const char *basis);
 unsigned fa_image_level(unsigned width, unsigned height);      /* codec/coder.c:247-255 */
 int fa_setup_params(const fa_options *op, float quality, unsigned width, unsigned height,
                     int color, unsigned frames, fa_info *wi, fa_cparams *cp);

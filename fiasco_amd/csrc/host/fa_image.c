@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <ctype.h>
+#include <pthread.h>
 #include "fa_host.h"
 
 typedef struct cursor { const unsigned char *p, *end; } cursor;
@@ -91,6 +92,44 @@ void fa_image_free(fa_image *im)
     if (!im->borrowed)
         for (b = 0; b < 3; b++) free(im->pixels[b]);
     free(im);
+}
+
+int (*fa_image_fetch)(fa_image *im) = NULL;
+
+int fa_image_host_planes(const fa_image *cim)
+{
+    static pthread_mutex_t mu = PTHREAD_MUTEX_INITIALIZER;
+    fa_image *im = (fa_image *) cim;
+    const size_t n = (size_t) im->width * im->height;
+    int b, nb = im->color ? 3 : 1, ok = 1;
+    pthread_mutex_lock(&mu);
+    if (!im->pixels[0]) {
+        if (!im->src_dev || !fa_image_fetch) { fa_set_error("Frame has no pixel planes."); ok = 0; }
+        for (b = 0; ok && b < nb; b++) {
+            im->pixels[b] = (int16_t *) malloc(n * sizeof(int16_t));
+            if (!im->pixels[b]) { fa_set_error("Out of memory!"); ok = 0; }
+        }
+        if (ok) { im->borrowed = 0; ok = fa_image_fetch(im); }
+        if (!ok) for (b = 0; b < 3; b++) { free(im->pixels[b]); im->pixels[b] = NULL; }
+    }
+    pthread_mutex_unlock(&mu);
+    return ok;
+}
+
+int fa_image_check_size(unsigned width, unsigned height, const char *name)
+{
+    if (width < 32) { fa_set_error("Width of image `%s' has to be at least 32 pixels.", name); return 0; }
+    if (height < 32) { fa_set_error("Height of image `%s' has to be at least 32 pixels.", name); return 0; }
+    if ((width & 1) || (height & 1)) {
+        fa_set_error("Width and height of images must be even numbers.");
+        return 0;
+    }
+    if (width > (1u << (FA_CAP_LEVEL / 2)) || height > (1u << (FA_CAP_LEVEL / 2))) {
+        fa_set_error("Image `%s' is too large (at most %u x %u pixels).", name,
+                     1u << (FA_CAP_LEVEL / 2), 1u << (FA_CAP_LEVEL / 2));
+        return 0;
+    }
+    return 1;
 }
 
 /* the pixel conversion of read_image (lib/image.c:365-389) into caller-provided planes */

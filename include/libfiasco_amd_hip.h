@@ -9,6 +9,8 @@
 #ifndef LIBFIASCO_AMD_HIP_H
 #define LIBFIASCO_AMD_HIP_H 1
 #include <stddef.h>
+#include <stdint.h>
+#include "libfiasco_amd.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -115,6 +117,43 @@ unsigned fiasco_amd_share_of(unsigned share_key, unsigned index, unsigned shares
 int fiasco_amd_set_device(int device);
 int fiasco_amd_set_devices(const int *ids, int n);      /* n = 0: back to the automatic choice */
 int fiasco_amd_device_count(void);                      /* shares a batch is split into */
+
+/* Frames that already live in device memory.  The batch entries of libfiasco_amd.h take PNM bytes on the host; these
+ * take 8-bit pixels where a decoder, a renderer or a tensor library left them, and ONE kernel launch per device share
+ * converts all of them into the coder's planes -- bit for bit what the PNM reader writes (lib/image.c:365-389: gray
+ * (g - 128) * 16; colour the three double-precision sums, left to right, * 16, truncated) -- inside HBM.
+ *   layout        GRAY8: height x width bytes; RGB8_INTERLEAVED: height x width x 3, PPM order R, G, B;
+ *                 RGB8_PLANAR: 3 x height x width, planes plane_stride bytes apart
+ *   pitch         bytes between rows, >= width * bytes per pixel (a frame cut out of a larger picture); 0 = packed
+ *   stream        the hipStream_t on which the caller's pixels become ready (NULL: the default stream).  The library
+ *                 makes its conversion wait for what `stream' holds at the call and makes `stream' wait for the
+ *                 conversion: the caller may overwrite or free the source in stream order right after the call.
+ * fiasco_amd_batch_stage_device() is fiasco_amd_batch_stage() without PNM: same options, same size rules and messages
+ * (sides even, 32 .. 8192), and the batch works with every batch call of libfiasco_amd.h; _upload() and
+ * _upload_device() may follow each other in any order.  fiasco_amd_batch_upload_device() is fiasco_amd_batch_upload():
+ * new frames of the same size and colour model for every slot, converted into the buffer the running pass does not
+ * read and taken over by the next submit.  It does not wait on the host for the caller's stream or for the conversion;
+ * its one host wait is for the descriptor table of the upload before, a few KiB copied a pass earlier.  Refused with
+ * a message, the batch unchanged:
+ * n == 0, a pointer that is not device memory (hipPointerGetAttributes) or whose rows leave its allocation, a pitch
+ * smaller than a row, a layout that contradicts the batch's colour model.  With several device shares every share
+ * converts its own frames on its own device (a source on another device is fetched over the peer link first).
+ * fiasco_amd_batch_input_planes(): the planes the coder sees for frame i, all bands back to back (width * height
+ * int16 each, 12.4 fixed point), for PNM-fed and device-fed batches.  The decoded-PSNR calls fetch the original the
+ * same way when a frame has no host copy.  Videos (fiasco_amd_seq_*, fiasco_coder()) take PNM only. */
+enum { FIASCO_AMD_GRAY8 = 0, FIASCO_AMD_RGB8_INTERLEAVED = 1, FIASCO_AMD_RGB8_PLANAR = 2 };
+typedef struct fiasco_amd_device_frame {
+    const void *data;        /* device memory */
+    size_t pitch;            /* bytes between rows; 0 = tightly packed */
+    size_t plane_stride;     /* bytes between colour planes (PLANAR); 0 = pitch * height */
+    unsigned width, height;
+    int layout;
+} fiasco_amd_device_frame;
+
+fiasco_amd_batch_t *fiasco_amd_batch_stage_device(unsigned n, const fiasco_amd_device_frame *frames,
+                                                  void *stream, float quality, const fiasco_c_options_t *options);
+int fiasco_amd_batch_upload_device(fiasco_amd_batch_t *b, const fiasco_amd_device_frame *frames, void *stream);
+int fiasco_amd_batch_input_planes(const fiasco_amd_batch_t *b, unsigned i, int16_t *out);
 
 /* The launcher keeps the per-frame HBM slabs of finished calls in a process-wide pool
  * (hipMalloc of hundreds of MB per frame is slow); this returns the pool to the driver. */
