@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "fiasco_amd_seq_search", "fiasco_amd_seq_gop_result", "fiasco_amd_seq_ycol", "fiasco_amd_seq_write",
     "fiasco_amd_seq_probe",
     "fiasco_amd_batch_stage_device", "fiasco_amd_batch_upload_device", "fiasco_amd_batch_input_planes",
+    "fiasco_amd_batch_decode_device", "fiasco_amd_planes_to_pixels_device",
 ]
 
 # pixel layouts of a frame in device memory (include/libfiasco_amd_hip.h)
@@ -53,6 +54,12 @@ FIASCO_AMD_GRAY8, FIASCO_AMD_RGB8_INTERLEAVED, FIASCO_AMD_RGB8_PLANAR = 0, 1, 2
 
 class DeviceFrame(ctypes.Structure):
     """struct fiasco_amd_device_frame (include/libfiasco_amd_hip.h)."""
+    _fields_ = [("data", ctypes.c_void_p), ("pitch", ctypes.c_size_t), ("plane_stride", ctypes.c_size_t),
+                ("width", ctypes.c_uint), ("height", ctypes.c_uint), ("layout", ctypes.c_int)]
+
+
+class DeviceTarget(ctypes.Structure):
+    """struct fiasco_amd_device_target (include/libfiasco_amd_hip.h): a DeviceFrame whose memory is written."""
     _fields_ = [("data", ctypes.c_void_p), ("pitch", ctypes.c_size_t), ("plane_stride", ctypes.c_size_t),
                 ("width", ctypes.c_uint), ("height", ctypes.c_uint), ("layout", ctypes.c_int)]
 
@@ -385,6 +392,27 @@ class Batch:
             raise FiascoError(self.lib.error_message())
         return buf.raw
 
+    def decode_device(self, targets, stream=None):
+        """fiasco_amd_batch_decode_device: the frames of the last finished pass, decoded on the device and written as
+        8-bit pixels into `targets` -- the bytes of the PGM / PPM `dfiasco -s 0 -o` writes.  A target is a torch uint8
+        tensor on the GPU or any writable object with __cuda_array_interface__, of the frame's size: H x W for a gray
+        frame, H x W x 3 or 3 x H x W for a colour frame (pitch and plane stride from the strides, as from_device);
+        None skips the frame.  `stream`: the hipStream_t (integer) the targets were last used on; None = torch's
+        current stream for torch tensors, else the default stream.  That stream waits for the conversion: what is
+        queued on it afterwards sees the pixels, no host synchronisation needed.  Returns the number of frames written."""
+        c = ctypes
+        targets = list(targets)
+        if len(targets) != self.n:
+            raise FiascoError("decode_device: %d targets for a batch of %d" % (len(targets), self.n))
+        arr = _device_targets(targets)
+        f = self.lib.L.fiasco_amd_batch_decode_device
+        f.argtypes = [c.c_void_p, c.POINTER(DeviceTarget), c.c_void_p]
+        f.restype = c.c_int
+        good = f(self.handle, arr, _stream_of([t for t in targets if t is not None], stream))
+        if not good:
+            raise FiascoError(self.lib.error_message())
+        return good
+
     def decode_psnr_all(self):
         """fiasco_amd_batch_decode_psnr_all: (n decoded, [[psnr dB per band]], [[mse per band]]) of all frames,
         decoded by one call of the device decoder."""
@@ -421,46 +449,83 @@ def _pnm_geometry(buf):
     return (int(m.group(2)), int(m.group(3)), 1 if m.group(1) == b"5" else 3) if m else None
 
 
+def _describe(what, i, fr, d):
+    """One GPU array (a torch tensor, anything with __cuda_array_interface__) into the DeviceFrame / DeviceTarget d:
+    layout from the shape, pitch and plane stride from the strides.  Returns the interface's read-only flag."""
+    cai = getattr(fr, "__cuda_array_interface__", None)
+    if cai is None:
+        raise FiascoError("%s %d is not in device memory (no __cuda_array_interface__)" % (what, i))
+    if cai["typestr"] not in ("|u1", "<u1", ">u1", "=u1"):
+        raise FiascoError("%s %d: 8-bit unsigned pixels expected, not %s" % (what, i, cai["typestr"]))
+    shape = tuple(int(v) for v in cai["shape"])
+    strides = cai.get("strides")
+    if strides is None:
+        strides = tuple(_packed_strides(shape))
+    strides = tuple(int(v) for v in strides)
+    d.data = int(cai["data"][0])
+    bad = None
+    if len(shape) == 2:
+        d.layout, (d.height, d.width) = FIASCO_AMD_GRAY8, shape
+        if strides[1] != 1:
+            bad = "pixels of a row must be adjacent"
+        d.pitch, d.plane_stride = strides[0], 0
+    elif len(shape) == 3 and shape[2] == 3:
+        d.layout, (d.height, d.width) = FIASCO_AMD_RGB8_INTERLEAVED, shape[:2]
+        if strides[2] != 1 or strides[1] != 3:
+            bad = "R, G, B of a pixel and the pixels of a row must be adjacent"
+        d.pitch, d.plane_stride = strides[0], 0
+    elif len(shape) == 3 and shape[0] == 3:
+        d.layout, (d.height, d.width) = FIASCO_AMD_RGB8_PLANAR, shape[1:]
+        if strides[2] != 1:
+            bad = "pixels of a row must be adjacent"
+        d.pitch, d.plane_stride = strides[1], strides[0]
+    else:
+        raise FiascoError("%s %d: shape %s is neither H x W, H x W x 3 nor 3 x H x W" % (what, i, shape))
+    if bad is None and (min(strides) <= 0):
+        bad = "strides must be positive"
+    if bad:
+        raise FiascoError("%s %d: strides %s cannot be described by pitch and plane stride (%s)" % (what, i, strides, bad))
+    return bool(cai["data"][1])
+
+
 def _device_frames(frames):
-    """The fiasco_amd_device_frame array of a list of GPU arrays (torch tensors, anything with
-    __cuda_array_interface__): layout from the shape, pitch and plane stride from the strides."""
+    """The fiasco_amd_device_frame array of a list of GPU arrays (_describe)."""
     arr = (DeviceFrame * max(len(frames), 1))()
     for i, fr in enumerate(frames):
-        cai = getattr(fr, "__cuda_array_interface__", None)
-        if cai is None:
-            raise FiascoError("frame %d is not in device memory (no __cuda_array_interface__)" % i)
-        if cai["typestr"] not in ("|u1", "<u1", ">u1", "=u1"):
-            raise FiascoError("frame %d: 8-bit unsigned pixels expected, not %s" % (i, cai["typestr"]))
-        shape = tuple(int(v) for v in cai["shape"])
-        strides = cai.get("strides")
-        if strides is None:
-            strides = tuple(_packed_strides(shape))
-        strides = tuple(int(v) for v in strides)
-        d = arr[i]
-        d.data = int(cai["data"][0])
-        bad = None
-        if len(shape) == 2:
-            d.layout, (d.height, d.width) = FIASCO_AMD_GRAY8, shape
-            if strides[1] != 1:
-                bad = "pixels of a row must be adjacent"
-            d.pitch, d.plane_stride = strides[0], 0
-        elif len(shape) == 3 and shape[2] == 3:
-            d.layout, (d.height, d.width) = FIASCO_AMD_RGB8_INTERLEAVED, shape[:2]
-            if strides[2] != 1 or strides[1] != 3:
-                bad = "R, G, B of a pixel and the pixels of a row must be adjacent"
-            d.pitch, d.plane_stride = strides[0], 0
-        elif len(shape) == 3 and shape[0] == 3:
-            d.layout, (d.height, d.width) = FIASCO_AMD_RGB8_PLANAR, shape[1:]
-            if strides[2] != 1:
-                bad = "pixels of a row must be adjacent"
-            d.pitch, d.plane_stride = strides[1], strides[0]
-        else:
-            raise FiascoError("frame %d: shape %s is neither H x W, H x W x 3 nor 3 x H x W" % (i, shape))
-        if bad is None and (min(strides) <= 0):
-            bad = "strides must be positive"
-        if bad:
-            raise FiascoError("frame %d: strides %s cannot be described by pitch and plane stride (%s)" % (i, strides, bad))
+        _describe("frame", i, fr, arr[i])
     return arr
+
+
+def _device_targets(targets):
+    """The fiasco_amd_device_target array of a list of writable GPU arrays (_describe); None: data = NULL, skipped."""
+    arr = (DeviceTarget * max(len(targets), 1))()
+    for i, t in enumerate(targets):
+        if t is not None and _describe("target", i, t, arr[i]):
+            raise FiascoError("target %d is read-only" % i)
+    return arr
+
+
+def planes_to_pixels_device(lib, planes, target, stream=None):
+    """fiasco_amd_planes_to_pixels_device: the decoder's last step alone.  `planes`: a packed int16 array on the GPU
+    (12.4 fixed point), H x W for gray or 3 x H x W for Y, Cb, Cr; `target`: as Batch.decode_device.  The conversion
+    runs on `stream` (default as decode_device)."""
+    c = ctypes
+    cai = getattr(planes, "__cuda_array_interface__", None)
+    if cai is None:
+        raise FiascoError("the planes are not in device memory (no __cuda_array_interface__)")
+    shape = tuple(int(v) for v in cai["shape"])
+    if cai["typestr"] not in ("<i2", "=i2") or len(shape) not in (2, 3) or (len(shape) == 3 and shape[0] != 3):
+        raise FiascoError("planes: int16 H x W or 3 x H x W expected, not %s %s" % (cai["typestr"], shape))
+    if cai.get("strides") is not None and tuple(int(v) for v in cai["strides"]) != tuple(2 * v for v in _packed_strides(shape)):
+        raise FiascoError("planes: strides %s are not those of a packed array" % (tuple(cai["strides"]),))
+    arr = _device_targets([target])
+    if (arr[0].height, arr[0].width) != shape[-2:]:
+        raise FiascoError("target of %d x %d pixels for planes of %d x %d" % (arr[0].width, arr[0].height, shape[-1], shape[-2]))
+    f = lib.L.fiasco_amd_planes_to_pixels_device
+    f.argtypes = [c.c_void_p, c.c_int, c.POINTER(DeviceTarget), c.c_void_p]
+    f.restype = c.c_int
+    if not f(int(cai["data"][0]), 1 if len(shape) == 3 else 0, arr, _stream_of([target], stream)):
+        raise FiascoError(lib.error_message())
 
 
 def _packed_strides(shape):

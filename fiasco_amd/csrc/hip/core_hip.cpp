@@ -2850,5 +2850,6 @@ extern "C" int fiasco_amd_rccl_gather(void *comm, void *stream_, int rank, int w
     return 1;
 }
 
-#include "frame_decoder.inc"
 #include "input_convert.inc"
+#include "output_convert.inc"
+#include "frame_decoder.inc"

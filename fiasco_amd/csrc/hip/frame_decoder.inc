@@ -348,9 +348,12 @@ extern "C" void fa_core_release_dev(void *dev, int dev_id)
 }
 
 /* One share of fa_core_decode_frames: the jobs `mine_idx' on the device share the calling thread is bound to
- * (for_shares / bind_share, core_hip.cpp).  Returns the number of frames decoded. */
+ * (for_shares / bind_share, core_hip.cpp).  Returns the number of frames decoded.
+ * out != NULL (fiasco_amd_batch_decode_device, output_convert.inc): behind the kernels of every flight ONE launch of
+ * oc_convert_kernel writes the frames of the flight as 8-bit pixels into out->target[job]; such a frame gets no host
+ * image and no copy to the host (jobs[].out stays NULL, out->done[job] says that it was written). */
 static pthread_mutex_t g_dec_stats_lock = PTHREAD_MUTEX_INITIALIZER;
-static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx)
+static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx, const OcOut *out)
 {
     int good = 0;
     {
@@ -381,11 +384,14 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx)
             std::vector<DecFrame> fr(f1 - f0);
             std::vector<size_t> mine;
             std::vector<DecDesc> descs;
+            std::vector<OcFrame> octab;                    /* source of an asynchronous upload, like descs */
             size_t need = 0;
             for (size_t f = f0; f < f1; f++)
                 if (dec_prepare(&jobs[todo[f]], fr[f - f0])) { mine.push_back(f); need += align_up(fr[f - f0].scratch_b, 256); }
             const size_t desc_off = need;
             need += align_up(FLIGHT * sizeof(DecDesc), 256);
+            const size_t oc_off = need;
+            if (out) need += align_up(FLIGHT * sizeof(OcFrame), 256);
             if (need > arena_b) {                          /* one arena per device, grown when a flight needs more */
                 if (arena) (void) hipFree(arena);
                 arena = nullptr; arena_b = 0;
@@ -441,6 +447,19 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx)
                     for (size_t f : mine) dec_fail(&jobs[todo[f]], "device decoder: HIP error");
                     mine.clear();
                 }
+                if (out && !mine.empty()) {
+                    /* the frames of the flight into the caller's buffers, once the caller's stream has let go of them */
+                    unsigned long long total = 0;
+                    octab.resize(mine.size());
+                    for (size_t k = 0; k < mine.size(); k++) oc_describe(octab[k], fr[mine[k] - f0].planes, out->target[todo[mine[k]]], total);
+                    if (hipStreamWaitEvent(stream, out->ready, 0) != hipSuccess
+                        || hipMemcpyAsync(arena + oc_off, octab.data(), octab.size() * sizeof(OcFrame), hipMemcpyHostToDevice, stream) != hipSuccess
+                        || !oc_launch((const OcFrame *) (arena + oc_off), (unsigned) octab.size(), total, oc_cus(), stream)) {
+                        (void) hipGetLastError();
+                        for (size_t f : mine) dec_fail(&jobs[todo[f]], "device decoder: HIP error");
+                        mine.clear();
+                    }
+                }
             }
             (void) hipEventRecord(ev1, stream);
             if (hipStreamSynchronize(stream) != hipSuccess) {
@@ -459,6 +478,16 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx)
             for (size_t f : mine) {
                 fa_dec_job *j = &jobs[todo[f]];
                 DecFrame &D = fr[f - f0];
+                if (out) {
+                    /* read: 2 bytes per pixel and band; written: the 8-bit pixels */
+                    const unsigned long long vals = (unsigned long long) j->width * j->height * (j->color ? 3 : 1);
+                    out->done[todo[f]] = 1;
+                    pthread_mutex_lock(&g_dec_stats_lock);
+                    g_stats.decoder_frames += 1; g_stats.decoder_bytes += D.bytes + 3 * vals;
+                    pthread_mutex_unlock(&g_dec_stats_lock);
+                    good++;
+                    continue;
+                }
                 fa_image *im = fa_image_alloc(j->width, j->height, j->color);
                 const size_t npix = (size_t) j->width * j->height;
                 bool ok = im != nullptr;
@@ -479,6 +508,13 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx)
             }
             f0 = f0_next;
         }
+        if (out && stream) {
+            /* the caller's stream behind the conversions: it may read the pixels without a host synchronisation */
+            hipEvent_t written = nullptr;
+            if (hipEventCreateWithFlags(&written, hipEventDisableTiming) != hipSuccess || hipEventRecord(written, stream) != hipSuccess
+                || hipStreamWaitEvent(out->caller, written, 0) != hipSuccess) (void) hipGetLastError();
+            if (written) (void) hipEventDestroy(written);
+        }
         if (arena) (void) hipFree(arena);
         if (ev0) (void) hipEventDestroy(ev0);
         if (ev1) (void) hipEventDestroy(ev1);
@@ -492,7 +528,7 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx)
  * frame of that GOP is searched and stays in that device's HBM (fa_image.dev).  The shares decode side by side, each
  * on its own host thread (share 0 on the caller's; for_shares, core_hip.cpp).  Returns the number of frames decoded; a
  * failed job has out == NULL and a message. */
-extern "C" int fa_core_decode_frames(unsigned n, fa_dec_job *jobs)
+static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out)
 {
     resolve_devices();
     size_t ND = g_devices.size();
@@ -505,8 +541,10 @@ extern "C" int fa_core_decode_frames(unsigned n, fa_dec_job *jobs)
     for (size_t k = 0; k < ND; k++) if (!deal[k].empty()) share.push_back(k);
     if (share.empty()) return 0;
     std::vector<int> goodv(share.size(), 0);
-    for_shares(share, [&](size_t part) { goodv[part] = decode_share(jobs, deal[share[part]]); });
+    for_shares(share, [&](size_t part) { goodv[part] = decode_share(jobs, deal[share[part]], out); });
     int good = 0;
     for (size_t k = 0; k < goodv.size(); k++) good += goodv[k];
     return good;
 }
+
+extern "C" int fa_core_decode_frames(unsigned n, fa_dec_job *jobs) { return decode_frames(n, jobs, nullptr); }

@@ -250,12 +250,12 @@ static int ic_fetch(fa_image *im)
 
 /* ------------------------------------------------------------------ the entry points (include/libfiasco_amd_hip.h) */
 
-/* one caller's frame: the size rules and messages of the PNM reader, pitch, layout, and that its rows lie in device
+/* one caller's frame (what: "device frame", or "device target" for output_convert.inc): the size rules and messages of the PNM reader, pitch, layout, and that its rows lie in device
  * memory.  *out = the frame with pitch and plane_stride filled in. */
-static bool ic_check_frame(unsigned i, const fiasco_amd_device_frame *in, fiasco_amd_device_frame *out)
+static bool ic_check_frame(const char *what, unsigned i, const fiasco_amd_device_frame *in, fiasco_amd_device_frame *out)
 {
     char name[32];
-    snprintf(name, sizeof name, "<device frame %u>", i);
+    snprintf(name, sizeof name, "<%s %u>", what, i);
     *out = *in;
     if (in->layout != FIASCO_AMD_GRAY8 && in->layout != FIASCO_AMD_RGB8_INTERLEAVED && in->layout != FIASCO_AMD_RGB8_PLANAR) {
         fa_set_error("%s: unknown pixel layout %d.", name, in->layout);
@@ -331,7 +331,7 @@ extern "C" fiasco_amd_batch_t *fiasco_amd_batch_stage_device(unsigned n, const f
     if (!n || !frames) { fa_set_error("No frames to stage."); return nullptr; }
     if (quality <= 0) { fa_set_error("Compression quality has to be positive."); return nullptr; }
     if (!ic_have_device()) return nullptr;
-    for (unsigned i = 0; i < n; i++) if (!ic_check_frame(i, &frames[i], &fr[i])) return nullptr;
+    for (unsigned i = 0; i < n; i++) if (!ic_check_frame("device frame", i, &frames[i], &fr[i])) return nullptr;
     if (options) { op = fa_cast_options(options); if (!op) return nullptr; }
     else { defaults = fiasco_c_options_new(); if (!defaults) return nullptr; op = fa_cast_options(defaults); }
     b = (fiasco_amd_batch_t *) calloc(1, sizeof *b);
@@ -390,7 +390,7 @@ extern "C" int fiasco_amd_batch_upload_device(fiasco_amd_batch_t *b, const fiasc
     std::vector<fiasco_amd_device_frame> fr(b->n);
     for (unsigned i = 0; i < b->n; i++) {
         const fa_image *old = b->ims[i];
-        if (!ic_check_frame(i, &frames[i], &fr[i])) return 0;
+        if (!ic_check_frame("device frame", i, &frames[i], &fr[i])) return 0;
         if (fr[i].width != old->width || fr[i].height != old->height || (fr[i].layout != FIASCO_AMD_GRAY8) != (old->color != 0)) {
             fa_set_error("`<device frame %u>': replacement frames must keep the size and colour model of the batch.", i);
             return 0;

@@ -155,6 +155,37 @@ fiasco_amd_batch_t *fiasco_amd_batch_stage_device(unsigned n, const fiasco_amd_d
 int fiasco_amd_batch_upload_device(fiasco_amd_batch_t *b, const fiasco_amd_device_frame *frames, void *stream);
 int fiasco_amd_batch_input_planes(const fiasco_amd_batch_t *b, unsigned i, int16_t *out);
 
+/* The way back: decoded frames as 8-bit pixels in device memory.  The device decoder (csrc/hip/frame_decoder.inc)
+ * reconstructs a frame in HBM; ONE kernel launch per flight of <= 32 frames (csrc/hip/output_convert.inc) then writes
+ * the bytes `dfiasco -s 0 -o' puts into its PGM / PPM -- lib/image.c gray_write :450-480: clip255((p >> 4) + 128);
+ * color_write :534-582 with the chroma tables of :487-532 -- into buffers the caller owns.  No pixel crosses to the
+ * host.  A target has the fields of fiasco_amd_device_frame with the same meaning (layout, pitch, plane_stride; 0 =
+ * packed), its memory is written.
+ * fiasco_amd_batch_decode_device(): the frames of the batch's last finished pass into targets[i] (b->n entries).
+ * Frames without a finished intra automaton are skipped as fiasco_amd_batch_decode_psnr_all() skips them, and so is
+ * frame i when targets[i].data == NULL.  Returns the number of frames written; 0 + message when nothing could be done.
+ *   stream        the hipStream_t on which the targets were last used (NULL: the default stream).  The conversion
+ *                 waits for what `stream' holds at the call, and `stream' is made to wait for the conversion: the
+ *                 caller may read the pixels in stream order without a host synchronisation.  The call itself waits
+ *                 on the host for the decoder's flights.
+ * Refused with a message, nothing written: b == NULL, an empty batch, no finished pass; a target that is not device
+ * memory (hipPointerGetAttributes) or whose rows leave its allocation; a pitch smaller than a row; a width or height
+ * other than the frame's; a layout that contradicts the colour model (GRAY8 <-> gray, the RGB8 layouts <-> colour); a
+ * target on a device other than the one the frame's share decodes on (the message names both; there is no peer copy on
+ * this path).  Intra frames only; no smoothing (dfiasco -s 0), no magnification.
+ * fiasco_amd_planes_to_pixels_device(): the conversion alone, on `stream' itself: planes [bands][height][width] int16
+ * (12.4 fixed point, bands = color ? 3 : 1) in device memory -> target.  1 ok / 0 + message. */
+typedef struct fiasco_amd_device_target {
+    void *data;              /* device memory, written */
+    size_t pitch;            /* bytes between rows; 0 = tightly packed */
+    size_t plane_stride;     /* bytes between colour planes (PLANAR); 0 = pitch * height */
+    unsigned width, height;
+    int layout;
+} fiasco_amd_device_target;
+
+int fiasco_amd_batch_decode_device(const fiasco_amd_batch_t *b, const fiasco_amd_device_target *targets, void *stream);
+int fiasco_amd_planes_to_pixels_device(const int16_t *planes, int color, const fiasco_amd_device_target *target, void *stream);
+
 /* The launcher keeps the per-frame HBM slabs of finished calls in a process-wide pool
  * (hipMalloc of hundreds of MB per frame is slow); this returns the pool to the driver. */
 void fiasco_amd_release_memory(void);
