@@ -27,11 +27,15 @@ _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ.setdefault("FIASCO_DATA", os.path.join(_ROOT, "tests", "golden") + ":" + os.path.join(_ROOT, "oracle", "_ref", "share"))
 
 
-def random_image(rng, colour):
+def random_image(rng, colour, size=None):
+    """size: (w, h) of the caller's own draw (tests/decoder_cases.py); None draws one here"""
     big = int(os.environ.get("FUZZ_BIG", "0"))          # FUZZ_BIG=1: sizes up to 1000 x 800
-    w = int(rng.integers(16, 500 if big else 200)) * 2
-    h = int(rng.integers(16, 400 if big else 160)) * 2
-    if os.environ.get("FUZZ_HUGE") == "1":              # beyond the stock reference: one side > 2048 (level >= 23)
+    if size:
+        w, h = size
+    else:
+        w = int(rng.integers(16, 500 if big else 200)) * 2
+        h = int(rng.integers(16, 400 if big else 160)) * 2
+    if not size and os.environ.get("FUZZ_HUGE") == "1":              # beyond the stock reference: one side > 2048 (level >= 23)
         w = int(rng.integers(1030, 1300)) * 2
         h = int(rng.integers(100, 850)) * 2
         if rng.integers(0, 3) == 0:
@@ -55,7 +59,8 @@ def random_image(rng, colour):
     return synth.pgm_bytes(plane())
 
 
-def random_options(rng, lib=None):
+def random_options(rng, lib=None, prediction=False):
+    """prediction=True: what FUZZ_PRED=1 does, for a caller that must not touch the environment"""
     lo = int(rng.integers(4, 9))
     hi = int(rng.integers(max(lo, 6), 13))
     el = int(rng.integers(1, 6))
@@ -65,7 +70,7 @@ def random_options(rng, lib=None):
     rr = int(rng.integers(0, 4)); dr = int(rng.integers(0, 4))
     cq = float(rng.choice([1.0, 2.0, 3.5])); cd = int(rng.choice([1, 5, 40, 63, 64, 100, 200]))
     pred = (0, 6, 10)
-    if os.environ.get("FUZZ_PRED") == "1" and rng.integers(0, 4):     # intra prediction (ND)
+    if (prediction or os.environ.get("FUZZ_PRED") == "1") and rng.integers(0, 4):     # intra prediction (ND)
         plo = int(rng.integers(6, 11))
         pred = (1, plo, int(rng.integers(plo, 13)))
     if os.environ.get("FUZZ_SPEC") == "1":
