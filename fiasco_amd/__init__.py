@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = [
     "fiasco_amd_seq_probe",
     "fiasco_amd_batch_stage_device", "fiasco_amd_batch_upload_device", "fiasco_amd_batch_input_planes",
     "fiasco_amd_batch_decode_device", "fiasco_amd_planes_to_pixels_device",
+    "fiasco_amd_batch_decode_distortion_device", "fiasco_amd_planes_distortion_device",
 ]
 
 # pixel layouts of a frame in device memory (include/libfiasco_amd_hip.h)
@@ -413,6 +414,37 @@ class Batch:
             raise FiascoError(self.lib.error_message())
         return good
 
+    def decode_distortion_device(self, targets=None, stream=None):
+        """fiasco_amd_batch_decode_distortion_device: the frames of the last finished pass, decoded on the device and
+        compared with their originals there.  Returns (n measured, sse, maxdiff, psnr_db), each [[per band] per frame]:
+        the exact integer sum of the squared byte differences, the largest absolute byte difference, and
+        10 log10(255^2 W H / sse) in double (inf for sse == 0; the mean is over the pixels of the image, as
+        decode_psnr).  Bands a frame does not have read 0 / 0 / 0.0; a skipped frame reads as sse 0.  `targets`: None, or
+        one target per frame as decode_device takes them (None: measured, not written) -- one decode serves both;
+        `stream` as decode_device."""
+        import math
+        c = ctypes
+        n = self.n
+        arr = None
+        if targets is not None:
+            targets = list(targets)
+            if len(targets) != n:
+                raise FiascoError("decode_distortion_device: %d targets for a batch of %d" % (len(targets), n))
+            arr = _device_targets(targets)
+        f = self.lib.L.fiasco_amd_batch_decode_distortion_device
+        f.argtypes = [c.c_void_p, c.POINTER(c.c_ulonglong), c.POINTER(c.c_uint), c.POINTER(DeviceTarget), c.c_void_p]
+        f.restype = c.c_int
+        s, m = (c.c_ulonglong * (3 * n))(), (c.c_uint * (3 * n))()
+        good = f(self.handle, s, m, arr, _stream_of([t for t in targets or [] if t is not None], stream))
+        if not good:
+            raise FiascoError(self.lib.error_message())
+        psnr = []
+        for i in range(n):
+            w, h, bands = self._geom[i]
+            psnr.append([0.0 if k >= bands else float("inf") if not s[3 * i + k]
+                         else 10.0 * math.log10(255.0 * 255.0 * w * h / s[3 * i + k]) for k in range(3)])
+        return good, [list(s[3 * i:3 * i + 3]) for i in range(n)], [list(m[3 * i:3 * i + 3]) for i in range(n)], psnr
+
     def decode_psnr_all(self):
         """fiasco_amd_batch_decode_psnr_all: (n decoded, [[psnr dB per band]], [[mse per band]]) of all frames,
         decoded by one call of the device decoder."""
@@ -526,6 +558,35 @@ def planes_to_pixels_device(lib, planes, target, stream=None):
     f.restype = c.c_int
     if not f(int(cai["data"][0]), 1 if len(shape) == 3 else 0, arr, _stream_of([target], stream)):
         raise FiascoError(lib.error_message())
+
+
+def planes_distortion_device(lib, a, b, stream=None):
+    """fiasco_amd_planes_distortion_device: the measuring kernel alone.  `a`, `b`: two packed int16 arrays of one shape
+    on the GPU (12.4 fixed point; torch tensors or anything with __cuda_array_interface__), H x W or 3 x H x W.  Returns
+    (sse, maxdiff), three integers each (0 for bands the planes do not have).  Runs on `stream` (default as
+    decode_device) and waits for the result."""
+    c = ctypes
+    cais = []
+    for name, p in (("a", a), ("b", b)):
+        cai = getattr(p, "__cuda_array_interface__", None)
+        if cai is None:
+            raise FiascoError("the planes `%s' are not in device memory (no __cuda_array_interface__)" % name)
+        shape = tuple(int(v) for v in cai["shape"])
+        if cai["typestr"] not in ("<i2", "=i2") or len(shape) not in (2, 3) or (len(shape) == 3 and shape[0] != 3):
+            raise FiascoError("planes `%s': int16 H x W or 3 x H x W expected, not %s %s" % (name, cai["typestr"], shape))
+        if cai.get("strides") is not None and tuple(int(v) for v in cai["strides"]) != tuple(2 * v for v in _packed_strides(shape)):
+            raise FiascoError("planes `%s': strides %s are not those of a packed array" % (name, tuple(cai["strides"])))
+        cais.append((int(cai["data"][0]), shape))
+    if cais[0][1] != cais[1][1]:
+        raise FiascoError("planes of %s against planes of %s" % (cais[0][1], cais[1][1]))
+    shape = cais[0][1]
+    f = lib.L.fiasco_amd_planes_distortion_device
+    f.argtypes = [c.c_void_p, c.c_void_p, c.c_int, c.c_uint, c.c_uint, c.POINTER(c.c_ulonglong), c.POINTER(c.c_uint), c.c_void_p]
+    f.restype = c.c_int
+    s, m = (c.c_ulonglong * 3)(), (c.c_uint * 3)()
+    if not f(cais[0][0], cais[1][0], 3 if len(shape) == 3 else 1, shape[-1], shape[-2], s, m, _stream_of([a], stream)):
+        raise FiascoError(lib.error_message())
+    return list(s), list(m)
 
 
 def _packed_strides(shape):

@@ -2852,4 +2852,5 @@ extern "C" int fiasco_amd_rccl_gather(void *comm, void *stream_, int rank, int w
 
 #include "input_convert.inc"
 #include "output_convert.inc"
+#include "distortion.inc"
 #include "frame_decoder.inc"

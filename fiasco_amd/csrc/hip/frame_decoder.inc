@@ -351,9 +351,14 @@ extern "C" void fa_core_release_dev(void *dev, int dev_id)
  * (for_shares / bind_share, core_hip.cpp).  Returns the number of frames decoded.
  * out != NULL (fiasco_amd_batch_decode_device, output_convert.inc): behind the kernels of every flight ONE launch of
  * oc_convert_kernel writes the frames of the flight as 8-bit pixels into out->target[job]; such a frame gets no host
- * image and no copy to the host (jobs[].out stays NULL, out->done[job] says that it was written). */
+ * image and no copy to the host (jobs[].out stays NULL, out->done[job] says that it was written).
+ * ds != NULL (fiasco_amd_batch_decode_distortion_device, distortion.inc): behind the kernels of every flight the result
+ * array is zeroed and ONE launch of ds_distortion_kernel compares the frames of the flight with their originals --
+ * ds->orig[job] in place, else the host planes of ds->image[job], copied into the arena -- before the pixels are
+ * written, if they are (a frame whose target has no data is measured only); 12 bytes per band come back after the
+ * flight's synchronisation.  Such a frame gets no host image either; ds->done[job] says that it was measured. */
 static pthread_mutex_t g_dec_stats_lock = PTHREAD_MUTEX_INITIALIZER;
-static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx, const OcOut *out)
+static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx, const OcOut *out, const DsOut *ds)
 {
     int good = 0;
     {
@@ -378,6 +383,17 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx,
         size_t arena_b = 0;
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         if (dev != -2 && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) { (void) hipGetLastError(); }
+        if (ds && stream) {
+            /* originals read in place: the conversion that wrote them may still run on the upload stream of the share
+             * that owns them (ic_fetch waits on the host for the same reason; here the stream waits) */
+            std::vector<const Staged *> seen;
+            for (unsigned i : todo) {
+                const Staged *S = ds->orig[i] ? (const Staged *) ds->image[i]->src_owner : nullptr;
+                if (!S || !S->ev_up || std::find(seen.begin(), seen.end(), S) != seen.end()) continue;
+                seen.push_back(S);
+                if (hipStreamWaitEvent(stream, S->ev_up, 0) != hipSuccess) (void) hipGetLastError();
+            }
+        }
         for (size_t f0 = 0; f0 < todo.size(); ) {
             const size_t f1 = f0 + flight < todo.size() ? f0 + flight : todo.size();
             const size_t f0_next = f1;
@@ -385,6 +401,8 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx,
             std::vector<size_t> mine;
             std::vector<DecDesc> descs;
             std::vector<OcFrame> octab;                    /* source of an asynchronous upload, like descs */
+            std::vector<DsPlane> dstab;                    /* likewise */
+            union { unsigned long long sums[DS_SLOTS]; char bytes[DS_RES_BYTES]; } dsres;
             size_t need = 0;
             for (size_t f = f0; f < f1; f++)
                 if (dec_prepare(&jobs[todo[f]], fr[f - f0])) { mine.push_back(f); need += align_up(fr[f - f0].scratch_b, 256); }
@@ -392,6 +410,13 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx,
             need += align_up(FLIGHT * sizeof(DecDesc), 256);
             const size_t oc_off = need;
             if (out) need += align_up(FLIGHT * sizeof(OcFrame), 256);
+            /* measuring: the table of the planes, the result array, the originals that come from the host */
+            const size_t ds_off = need;
+            if (ds) need += align_up(DS_SLOTS * sizeof(DsPlane), 256);
+            const size_t res_off = need;
+            if (ds) need += align_up(DS_RES_BYTES, 256);
+            const size_t orig_off = need;
+            if (ds) for (size_t f : mine) if (!ds->orig[todo[f]]) need += fr[f - f0].plane_bytes;
             if (need > arena_b) {                          /* one arena per device, grown when a flight needs more */
                 if (arena) (void) hipFree(arena);
                 arena = nullptr; arena_b = 0;
@@ -447,14 +472,45 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx,
                     for (size_t f : mine) dec_fail(&jobs[todo[f]], "device decoder: HIP error");
                     mine.clear();
                 }
+                if (ds && !mine.empty()) {
+                    /* the frames of the flight against their originals */
+                    size_t at = orig_off;
+                    bool ok = true;
+                    for (size_t k = 0; k < mine.size() && ok; k++) {
+                        const fa_dec_job *j = &jobs[todo[mine[k]]];
+                        const DecFrame &D = fr[mine[k] - f0];
+                        const unsigned bands = j->color ? 3 : 1;
+                        const size_t npix = (size_t) j->width * j->height;
+                        const int16_t *o = ds->orig[todo[mine[k]]];
+                        if (!o) {
+                            const fa_image *im = ds->image[todo[mine[k]]];
+                            for (unsigned b = 0; b < bands && ok; b++)
+                                ok = hipMemcpyAsync(arena + at + b * npix * 2, im->pixels[b], npix * 2, hipMemcpyHostToDevice, stream) == hipSuccess;
+                            o = (const int16_t *) (arena + at);
+                            at += D.plane_bytes;
+                        }
+                        ds_describe(dstab, (unsigned) k, o, D.planes, j->width, j->height, bands);
+                    }
+                    if (!ok || hipMemsetAsync(arena + res_off, 0, DS_RES_BYTES, stream) != hipSuccess
+                        || hipMemcpyAsync(arena + ds_off, dstab.data(), dstab.size() * sizeof(DsPlane), hipMemcpyHostToDevice, stream) != hipSuccess
+                        || !ds_launch((const DsPlane *) (arena + ds_off), dstab, arena + res_off, oc_cus(), stream)) {
+                        (void) hipGetLastError();
+                        for (size_t f : mine) dec_fail(&jobs[todo[f]], "device decoder: HIP error");
+                        mine.clear();
+                    }
+                }
                 if (out && !mine.empty()) {
                     /* the frames of the flight into the caller's buffers, once the caller's stream has let go of them */
                     unsigned long long total = 0;
-                    octab.resize(mine.size());
-                    for (size_t k = 0; k < mine.size(); k++) oc_describe(octab[k], fr[mine[k] - f0].planes, out->target[todo[mine[k]]], total);
-                    if (hipStreamWaitEvent(stream, out->ready, 0) != hipSuccess
-                        || hipMemcpyAsync(arena + oc_off, octab.data(), octab.size() * sizeof(OcFrame), hipMemcpyHostToDevice, stream) != hipSuccess
-                        || !oc_launch((const OcFrame *) (arena + oc_off), (unsigned) octab.size(), total, oc_cus(), stream)) {
+                    for (size_t k = 0; k < mine.size(); k++) {
+                        if (!out->target[todo[mine[k]]].data) continue;            /* measured only */
+                        octab.emplace_back();
+                        oc_describe(octab.back(), fr[mine[k] - f0].planes, out->target[todo[mine[k]]], total);
+                    }
+                    if (!octab.empty()
+                        && (hipStreamWaitEvent(stream, out->ready, 0) != hipSuccess
+                            || hipMemcpyAsync(arena + oc_off, octab.data(), octab.size() * sizeof(OcFrame), hipMemcpyHostToDevice, stream) != hipSuccess
+                            || !oc_launch((const OcFrame *) (arena + oc_off), (unsigned) octab.size(), total, oc_cus(), stream))) {
                         (void) hipGetLastError();
                         for (size_t f : mine) dec_fail(&jobs[todo[f]], "device decoder: HIP error");
                         mine.clear();
@@ -467,6 +523,11 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx,
                 for (size_t f : mine) dec_fail(&jobs[todo[f]], "device decoder: kernel failed");
                 mine.clear();
             }
+            if (ds && !mine.empty() && hipMemcpy(dsres.bytes, arena + res_off, DS_RES_BYTES, hipMemcpyDeviceToHost) != hipSuccess) {
+                (void) hipGetLastError();
+                for (size_t f : mine) dec_fail(&jobs[todo[f]], "device decoder: download failed");
+                mine.clear();
+            }
             {
                 float ms = 0;
                 if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) {
@@ -475,15 +536,25 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx,
                     pthread_mutex_unlock(&g_dec_stats_lock);
                 } else (void) hipGetLastError();
             }
-            for (size_t f : mine) {
+            for (size_t k = 0; k < mine.size(); k++) {
+                const size_t f = mine[k];
                 fa_dec_job *j = &jobs[todo[f]];
                 DecFrame &D = fr[f - f0];
-                if (out) {
-                    /* read: 2 bytes per pixel and band; written: the 8-bit pixels */
+                if (out || ds) {
+                    /* pixels: 2 bytes read per pixel and band, the 8-bit pixel written; measuring: 2 bytes read per side */
                     const unsigned long long vals = (unsigned long long) j->width * j->height * (j->color ? 3 : 1);
-                    out->done[todo[f]] = 1;
+                    const bool written = out && out->target[todo[f]].data;
+                    if (written) out->done[todo[f]] = 1;
+                    if (ds) {
+                        const unsigned *mx = (const unsigned *) (dsres.bytes + DS_SLOTS * sizeof(unsigned long long));
+                        for (unsigned b = 0; b < (j->color ? 3u : 1u); b++) {
+                            if (ds->sse) ds->sse[(size_t) todo[f] * 3 + b] = dsres.sums[k * 3 + b];
+                            if (ds->maxdiff) ds->maxdiff[(size_t) todo[f] * 3 + b] = mx[k * 3 + b];
+                        }
+                        ds->done[todo[f]] = 1;
+                    }
                     pthread_mutex_lock(&g_dec_stats_lock);
-                    g_stats.decoder_frames += 1; g_stats.decoder_bytes += D.bytes + 3 * vals;
+                    g_stats.decoder_frames += 1; g_stats.decoder_bytes += D.bytes + (ds ? 4 * vals : 0) + (written ? 3 * vals : 0);
                     pthread_mutex_unlock(&g_dec_stats_lock);
                     good++;
                     continue;
@@ -528,7 +599,7 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx,
  * frame of that GOP is searched and stays in that device's HBM (fa_image.dev).  The shares decode side by side, each
  * on its own host thread (share 0 on the caller's; for_shares, core_hip.cpp).  Returns the number of frames decoded; a
  * failed job has out == NULL and a message. */
-static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out)
+static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const DsOut *ds)
 {
     resolve_devices();
     size_t ND = g_devices.size();
@@ -541,10 +612,12 @@ static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out)
     for (size_t k = 0; k < ND; k++) if (!deal[k].empty()) share.push_back(k);
     if (share.empty()) return 0;
     std::vector<int> goodv(share.size(), 0);
-    for_shares(share, [&](size_t part) { goodv[part] = decode_share(jobs, deal[share[part]], out); });
+    for_shares(share, [&](size_t part) { goodv[part] = decode_share(jobs, deal[share[part]], out, ds); });
     int good = 0;
     for (size_t k = 0; k < goodv.size(); k++) good += goodv[k];
     return good;
 }
 
-extern "C" int fa_core_decode_frames(unsigned n, fa_dec_job *jobs) { return decode_frames(n, jobs, nullptr); }
+static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out) { return decode_frames(n, jobs, out, nullptr); }
+
+extern "C" int fa_core_decode_frames(unsigned n, fa_dec_job *jobs) { return decode_frames(n, jobs, nullptr, nullptr); }

@@ -186,6 +186,30 @@ typedef struct fiasco_amd_device_target {
 int fiasco_amd_batch_decode_device(const fiasco_amd_batch_t *b, const fiasco_amd_device_target *targets, void *stream);
 int fiasco_amd_planes_to_pixels_device(const int16_t *planes, int color, const fiasco_amd_device_target *target, void *stream);
 
+/* How good is what was just coded: the decoded frames of a staged batch compared with their originals in device memory
+ * (csrc/hip/distortion.inc).  Behind the kernels of every decoder flight ONE reduction kernel compares the decoded
+ * planes with the original planes, both as the bytes fiasco_amd_batch_decode_psnr() compares -- clip255((p >> 4) + 128),
+ * Y, Cb and Cr as planes -- and returns per frame and band the EXACT integer sum of the squared differences and the
+ * largest absolute difference: 12 bytes per band cross to the host, no plane.  (The PSNR calls sum in float as
+ * bin/pnmpsnr.c does; below 2^24 that sum is this one, beyond it rounds.)  The original of a frame that was handed over
+ * in device memory is read where the input conversion left it when that is the device the frame is decoded on; every
+ * other original is copied up from its host planes.  Intra frames of staged batches only; no smoothing.
+ * fiasco_amd_batch_decode_distortion_device(): */
+/* frames of the last finished pass: decoded on the device, compared with their originals on the device.
+ * sse / maxdiff: [b->n][3], either may be NULL; bands a frame does not have and skipped frames get 0.
+ * targets: NULL, or b->n targets with the rules, layouts and bytes of fiasco_amd_batch_decode_device()
+ * (data == NULL: measured, not written) -- one decode serves both.  Returns the number of frames measured. */
+int fiasco_amd_batch_decode_distortion_device(const fiasco_amd_batch_t *b, unsigned long long *sse, unsigned *maxdiff,
+                                              const fiasco_amd_device_target *targets, void *stream);
+/* Refused with a message, nothing written: b == NULL, an empty batch, no finished pass; sse, maxdiff and targets all
+ * NULL; every target refusal of fiasco_amd_batch_decode_device(). */
+/* the reduction alone, on `stream': two sets of planes [bands][height][width] int16 in device memory,
+ * width, height 1 .. 8192 (any parity), bands 1 or 3; the call waits on the host.  1 ok / 0 + message. */
+int fiasco_amd_planes_distortion_device(const int16_t *a, const int16_t *b, int bands, unsigned width, unsigned height,
+                                        unsigned long long sse[3], unsigned maxdiff[3], void *stream);
+/* Refused with a message, nothing written: a pointer that is not device memory, planes that leave their allocation,
+ * planes on different devices, a size or a band count out of range. */
+
 /* The launcher keeps the per-frame HBM slabs of finished calls in a process-wide pool
  * (hipMalloc of hundreds of MB per frame is slow); this returns the pool to the driver. */
 void fiasco_amd_release_memory(void);
