@@ -2850,6 +2850,39 @@ extern "C" int fiasco_amd_rccl_gather(void *comm, void *stream_, int rank, int w
     return 1;
 }
 
+/* ------------------------------------------------------------------ the device decoder and its outlets
+ * What the four files below agree on.  The decoder (frame_decoder.inc) works in flights of at most DEC_FLIGHT frames:
+ * the tables a flight uploads (DecDesc, OcFrame, DsPlane) and the result array of its measuring launch
+ * (distortion.inc DS_SLOTS) have room for that many. */
+enum { DEC_FLIGHT = 32 };
+
+struct OcOut;                                   /* output_convert.inc */
+struct DsOut;                                   /* distortion.inc */
+static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const DsOut *ds);      /* frame_decoder.inc */
+
+/* The dealing rule.  A job is decoded on the device share the SEARCH deals it to -- fa_share_of(): by its key where it
+ * has one (the GOP of a video), by its index otherwise --, so that the reference frame of a GOP is decoded where the
+ * next frame of that GOP is searched and stays in that device's HBM (fa_image.dev).  Jobs without keys spread over no
+ * more shares than there are jobs.  decode_frames() deals by these two; the batch entry points ask them where a frame
+ * will be decoded before they accept a target or an original that lives on a device. */
+static size_t dec_shares(unsigned n, const fa_dec_job *jobs)
+{
+    resolve_devices();
+    const size_t ND = g_devices.size();
+    bool keyed = false;
+    for (unsigned i = 0; i < n; i++) keyed = keyed || jobs[i].share_key != 0;
+    return !keyed && ND > n ? (n ? n : 1) : ND;
+}
+
+static size_t dec_share_of(const fa_dec_job *jobs, unsigned i, size_t shares) { return fa_share_of(jobs[i].share_key, i, (unsigned) shares); }
+
+/* cur: the calling thread's device, which a share without a device of its own (g_devices: -1) decodes on */
+static int dec_device_of(const fa_dec_job *jobs, unsigned i, size_t shares, int cur)
+{
+    const int dev = g_devices[dec_share_of(jobs, i, shares)];
+    return dev >= 0 ? dev : cur;
+}
+
 #include "input_convert.inc"
 #include "output_convert.inc"
 #include "distortion.inc"

@@ -1,7 +1,7 @@
 /*
  *  distortion.inc -- how far a decoded frame is from its original, measured in device memory (included by
- *  core_hip.cpp between output_convert.inc, whose loads and clips it uses, and frame_decoder.inc, whose flights
- *  launch it).
+ *  core_hip.cpp between output_convert.inc, whose loads, clips and batch preamble it uses, and frame_decoder.inc, whose
+ *  flights launch it; core_hip.cpp declares what the three share ahead of them: DEC_FLIGHT, decode_frames()).
  *
  *  The device decoder leaves the planes [bands][height][width] of a frame in HBM as 12.4 fixed point; the original
  *  planes of a device-fed frame lie there already, those of a PNM-fed frame are copied up.  ONE launch of
@@ -32,7 +32,7 @@ struct DsPlane {
     unsigned slot;                   /* frame of the launch * 3 + band: where the results go */
 };
 
-enum { DS_SLOTS = 32 * 3 };          /* a decoder flight: 32 frames of three bands */
+enum { DS_SLOTS = DEC_FLIGHT * 3 };  /* a decoder flight: three bands per frame */
 /* the result array of a launch: sums first, then the maxima */
 #define DS_RES_BYTES ((size_t) DS_SLOTS * (sizeof(unsigned long long) + sizeof(unsigned)))
 
@@ -91,8 +91,6 @@ struct DsOut {
     unsigned char      *done;          /* [n] */
 };
 
-static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const DsOut *ds);      /* frame_decoder.inc */
-
 /* the planes of one frame behind tab[0 .. n); k: the frame's number in the launch */
 static void ds_describe(std::vector<DsPlane> &tab, unsigned k, const int16_t *orig, const int16_t *dec, unsigned width, unsigned height, unsigned bands)
 {
@@ -126,54 +124,26 @@ static bool ds_launch(const DsPlane *d_tab, const std::vector<DsPlane> &tab, voi
 extern "C" int fiasco_amd_batch_decode_distortion_device(const fiasco_amd_batch_t *b, unsigned long long *sse, unsigned *maxdiff,
                                                          const fiasco_amd_device_target *targets, void *stream)
 {
-    if (!b || !b->n) { fa_set_error("fiasco_amd_batch_decode_distortion_device: empty batch"); return 0; }
-    if (!sse && !maxdiff && !targets) { fa_set_error("fiasco_amd_batch_decode_distortion_device: no result arrays and no targets"); return 0; }
-    if (!ic_have_device()) return 0;
+    OcBatch B;
+    if (!oc_batch_jobs("fiasco_amd_batch_decode_distortion_device", sse || maxdiff || targets ? nullptr : "no result arrays and no targets", b, targets, B)) return 0;
     const unsigned n = b->n;
-    bool finished = false;
-    for (unsigned i = 0; i < n; i++) finished = finished || (b->jobs[i].status && b->jobs[i].wfa);
-    if (!finished) { fa_set_error("fiasco_amd_batch_decode_distortion_device: the batch has no finished pass"); return 0; }
-    /* the share a job is decoded on is the one fa_core_decode_frames deals it to */
-    resolve_devices();
-    size_t ND = g_devices.size();
-    if (ND > n) ND = n;
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess) { (void) hipGetLastError(); cur = -1; }
-    std::vector<fa_dec_job> d(n);
-    std::vector<fiasco_amd_device_frame> fr(n);
     std::vector<unsigned char> written(n, 0), measured(n, 0);
     std::vector<const int16_t *> orig(n, nullptr);
     std::vector<const fa_image *> image(n, nullptr);
     unsigned wanted = 0;
-    memset(d.data(), 0, n * sizeof(fa_dec_job));
-    memset(fr.data(), 0, n * sizeof(fiasco_amd_device_frame));
     for (unsigned i = 0; i < n; i++) {
-        const fa_job *job = &b->jobs[i];
-        d[i].skip = 1;
-        if (!job->status || !job->wfa || job->frame_type != FA_I_FRAME) continue;
-        const int sdev = g_devices[fa_share_of(0, i, (unsigned) ND)] >= 0 ? g_devices[fa_share_of(0, i, (unsigned) ND)] : cur;
-        if (targets && targets[i].data) {
-            int tdev = -1;
-            if (!oc_check_target(i, &targets[i], job->image->width, job->image->height, job->image->color, &fr[i], &tdev)) return 0;
-            if (tdev != sdev) {
-                fa_set_error("<device target %u>: the target lives on device %d, the frame is decoded on device %d (no peer copy on this path).", i, tdev, sdev);
-                return 0;
-            }
-        }
+        if (B.jobs[i].skip) continue;
         /* the original: where the input conversion left it when that is the device the frame is decoded on, else the
          * host planes (a PNM-fed frame has them, a frame on another device is fetched as the PSNR calls fetch it) */
-        image[i] = job->image;
-        if (job->image->src_dev && job->image->src_dev_id == sdev) orig[i] = job->image->src_dev;
-        d[i].skip = 0;
-        d[i].wfa = job->wfa; d[i].width = job->image->width; d[i].height = job->image->height; d[i].color = job->image->color;
-        d[i].frame_type = FA_I_FRAME;
+        image[i] = b->jobs[i].image;
+        if (image[i]->src_dev && image[i]->src_dev_id == B.device[i]) orig[i] = image[i]->src_dev;
         wanted++;
     }
     if (!wanted) { fa_set_error("fiasco_amd_batch_decode_distortion_device: no frame with a finished intra automaton"); return 0; }
     for (unsigned i = 0; i < n; i++)
-        if (!d[i].skip && !orig[i] && !fa_image_host_planes(image[i])) return 0;
+        if (!B.jobs[i].skip && !orig[i] && !fa_image_host_planes(image[i])) return 0;
     OcOut out;
-    out.target = fr.data(); out.done = written.data(); out.caller = (hipStream_t) stream; out.ready = nullptr;
+    out.target = B.target.data(); out.done = written.data(); out.caller = (hipStream_t) stream; out.ready = nullptr;
     if (targets) {
         out.ready = ic_mark_ready(stream);
         if (!out.ready) return 0;
@@ -182,10 +152,10 @@ extern "C" int fiasco_amd_batch_decode_distortion_device(const fiasco_amd_batch_
     if (maxdiff) memset(maxdiff, 0, (size_t) n * 3 * sizeof *maxdiff);
     DsOut ds;
     ds.orig = orig.data(); ds.image = image.data(); ds.sse = sse; ds.maxdiff = maxdiff; ds.done = measured.data();
-    const int good = decode_frames(n, d.data(), targets ? &out : nullptr, &ds);
+    const int good = decode_frames(n, B.jobs.data(), targets ? &out : nullptr, &ds);
     if (out.ready) (void) hipEventDestroy(out.ready);
     for (unsigned i = 0; i < n; i++)
-        if (!d[i].skip && !measured[i]) fa_set_error("<frame %u>: %s", i, d[i].errmsg[0] ? d[i].errmsg : "decoder failed");
+        if (!B.jobs[i].skip && !measured[i]) fa_set_error("<frame %u>: %s", i, B.jobs[i].errmsg[0] ? B.jobs[i].errmsg : "decoder failed");
     return good;
 }
 

@@ -168,9 +168,30 @@ struct DecFrame {                     /* one frame in flight */
     unsigned S = 0, maxl = 0, mc_maxl = 0, ntops = 0, nmcs = 0;
     bool own_planes = false;          /* planes is an allocation of its own (kept on the device) */
     unsigned long long bytes = 0;     /* algorithmic: 2 bytes per pixel written and per (pixel, term) read */
+    size_t scratch_off = 0;           /* dec_flight_prepare: its scratch_b bytes of the flight's arena */
+    unsigned slot = 0;                /* dec_flight_measure: its place in the result array of the measuring launch */
 };
 
 static void dec_fail(fa_dec_job *j, const char *msg) { snprintf(j->errmsg, sizeof j->errmsg, "%s", msg); j->out = nullptr; }
+
+/* the edges of row r = (state, label) of the automaton; more than six run on into the next rows (fa_wfa_append_edge) */
+static unsigned dec_edges(const fa_wfa *w, size_t r)
+{
+    unsigned e = 0;
+    while (r * 6 + e < (size_t) w->cap * 12 && w->into[r * 6 + e] != FA_NO_EDGE) e++;
+    return e;
+}
+
+/* what a node reads per pixel: its tree child and the edges into other domains than the constant one */
+static unsigned dec_terms(const DecNode &n, const DecEdge *ext)
+{
+    int32_t off = 0;
+    if (n.n > 6) memcpy(&off, &n.e[0], 4);
+    const DecEdge *ed = n.n > 6 ? ext + off : n.e;
+    unsigned terms = n.tree >= 0;
+    for (int e = 0; e < n.n; e++) terms += ed[e].dom != 0;
+    return terms;
+}
 
 /* host side of one frame: the integer automaton, the block lists, the sizes */
 static bool dec_prepare(fa_dec_job *j, DecFrame &D)
@@ -219,24 +240,18 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
     }
     /* edge lists of more than six entries (long bases): behind the nodes */
     size_t next = 0;
-    for (unsigned r = 0; r < S * 2; r++) {
-        size_t e = 0;
-        while ((size_t) r * 6 + e < (size_t) w->cap * 12 && w->into[(size_t) r * 6 + e] != FA_NO_EDGE) e++;
-        if (e > 6) next += e;
-    }
+    for (size_t r = 0; r < (size_t) S * 2; r++) { const unsigned e = dec_edges(w, r); if (e > 6) next += e; }
     const size_t nodes_b = align_up((size_t) S * 2 * sizeof(DecNode) + next * sizeof(DecEdge), 256), tops_b = align_up((tops.size() + 1) * sizeof(DecTop), 256),
                  mcs_b = align_up((mcs.size() + 1) * sizeof(DecMc), 256), img_b = align_up(((size_t) S << maxl) * 2 + 256, 256);      /* levels 0 .. maxl - 1 of every state */
-    std::vector<char> &hostbuf = D.host;
-    hostbuf.assign(nodes_b + tops_b + mcs_b, 0);
-    DecNode *nodes = (DecNode *) hostbuf.data();
+    D.host.assign(nodes_b + tops_b + mcs_b, 0);
+    DecNode *nodes = (DecNode *) D.host.data();
     DecEdge *ext = (DecEdge *) (nodes + (size_t) S * 2);
     int32_t ext_used = 0;
     for (unsigned s = 0; s < S; s++)
         for (unsigned l = 0; l < 2; l++) {
             DecNode &n = nodes[(size_t) s * 2 + l];
             n.tree = FA_TREE(w, s, l) != FA_RANGE ? (int) FA_TREE(w, s, l) : -1;
-            unsigned cnt = 0;
-            while (((size_t) s * 2 + l) * 6 + cnt < (size_t) w->cap * 12 && FA_INTO(w, s, l, cnt) != FA_NO_EDGE) cnt++;
+            const unsigned cnt = dec_edges(w, (size_t) s * 2 + l);
             DecEdge *dst = n.e;
             if (cnt > 6) { memcpy(&n.e[0], &ext_used, 4); dst = ext + ext_used; ext_used += (int32_t) cnt; }
             n.n = (int32_t) cnt;
@@ -247,11 +262,10 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
                                       : (int16_t) ((double) (FA_WEIGHT(w, s, l, e) * 512) + 0.5);
             }
         }
-    if (!tops.empty()) memcpy(hostbuf.data() + nodes_b, tops.data(), tops.size() * sizeof(DecTop));
-    if (!mcs.empty()) memcpy(hostbuf.data() + nodes_b + tops_b, mcs.data(), mcs.size() * sizeof(DecMc));
-    std::vector<int16_t> &px0 = D.px0;
-    px0.resize(S);
-    for (unsigned s = 0; s < S; s++) px0[s] = dec_fixed_of(w->final_distribution[s]);
+    if (!tops.empty()) memcpy(D.host.data() + nodes_b, tops.data(), tops.size() * sizeof(DecTop));
+    if (!mcs.empty()) memcpy(D.host.data() + nodes_b + tops_b, mcs.data(), mcs.size() * sizeof(DecMc));
+    D.px0.resize(S);
+    for (unsigned s = 0; s < S; s++) D.px0[s] = dec_fixed_of(w->final_distribution[s]);
 
     const size_t npix = (size_t) W * H;
     D.plane_bytes = align_up(npix * bands * 2, 256);
@@ -259,83 +273,62 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
     D.S = S; D.maxl = maxl; D.mc_maxl = mc_maxl; D.ntops = (unsigned) tops.size(); D.nmcs = (unsigned) mcs.size();
     D.own_planes = j->keep_dev != 0;
     D.scratch_b = nodes_b + tops_b + mcs_b + img_b + (D.own_planes ? 0 : D.plane_bytes);
-    {
-        unsigned long long terms = 0;
-        for (size_t k = 0; k < (size_t) S * 2; k++) {
-            terms += nodes[k].tree >= 0;
-            int32_t off = 0;
-            if (nodes[k].n > 6) memcpy(&off, &nodes[k].e[0], 4);
-            const DecEdge *ed = nodes[k].n > 6 ? ext + off : nodes[k].e;
-            for (int e = 0; e < nodes[k].n; e++) terms += ed[e].dom != 0;
-        }
-        /* level l < maxl: S * 2^l pixels written, terms * 2^(l-1) read; the top level: the terms of the states shown,
-         * straight into the frame: written once, read by nobody here */
-        unsigned long long top_terms = 0;
-        for (size_t k = 0; k < tops.size(); k++)
-            for (unsigned l = 0; l < 2; l++) {
-                const DecNode &n = nodes[(size_t) tops[k].state * 2 + l];
-                top_terms += n.tree >= 0;
-                int32_t off = 0;
-                if (n.n > 6) memcpy(&off, &n.e[0], 4);
-                const DecEdge *ed = n.n > 6 ? ext + off : n.e;
-                for (int e = 0; e < n.n; e++) top_terms += ed[e].dom != 0;
-            }
-        const unsigned long long lower = maxl ? (((unsigned long long) S << maxl) - 2ull * S) : 0ull;
-        const unsigned long long lower_reads = maxl ? terms * ((1ull << (maxl - 1)) - 1) : 0ull;
-        D.bytes = 2ull * (lower + lower_reads + (maxl ? top_terms << (maxl - 1) : 0ull)) + 2ull * npix * bands;
-    }
+    /* level l < maxl: S * 2^l pixels written, terms * 2^(l-1) read; the top level: the terms of the states shown,
+     * straight into the frame: written once, read by nobody here */
+    unsigned long long terms = 0, top_terms = 0;
+    for (size_t k = 0; k < (size_t) S * 2; k++) terms += dec_terms(nodes[k], ext);
+    for (size_t k = 0; k < tops.size(); k++)
+        for (unsigned l = 0; l < 2; l++) top_terms += dec_terms(nodes[(size_t) tops[k].state * 2 + l], ext);
+    const unsigned long long lower = maxl ? (((unsigned long long) S << maxl) - 2ull * S) : 0ull;
+    const unsigned long long lower_reads = maxl ? terms * ((1ull << (maxl - 1)) - 1) : 0ull;
+    D.bytes = 2ull * (lower + lower_reads + (maxl ? top_terms << (maxl - 1) : 0ull)) + 2ull * npix * bands;
     return true;
 }
 
-/* device side of one frame, queued on `stream`; scratch: D.scratch_b bytes of the flight's arena */
-static bool dec_run(fa_dec_job *j, DecFrame &D, char *scratch, hipStream_t stream, int cur_dev)
+/* device side of one frame, queued on `stream': its automaton, the level-0 images and the zeroed planes;
+ * scratch: D.scratch_b bytes of the flight's arena */
+static bool dec_run(fa_dec_job *j, DecFrame &D, char *scratch, hipStream_t stream)
 {
-    const unsigned S = D.S, maxl = D.maxl, mc_maxl = D.mc_maxl, bands = j->color ? 3 : 1, W = j->width, H = j->height;
-    const size_t nodes_b = D.nodes_b, tops_b = D.tops_b, mcs_b = D.mcs_b, npix = (size_t) W * H;
-    std::vector<char> &hostbuf = D.host;
-    std::vector<int16_t> &px0 = D.px0;
+    const size_t up_b = D.nodes_b + D.tops_b + D.mcs_b;
     D.base = scratch;
     if (D.own_planes) {
         if (hipMalloc((void **) &D.planes, D.plane_bytes) != hipSuccess) { (void) hipGetLastError(); D.planes = nullptr; dec_fail(j, "device decoder: out of device memory"); return false; }
-    } else D.planes = (int16_t *) (scratch + nodes_b + tops_b + mcs_b + D.img_b);
-    int16_t *img = (int16_t *) (D.base + nodes_b + tops_b + mcs_b);
-    bool ok = hipMemcpyAsync(D.base, hostbuf.data(), nodes_b + tops_b + mcs_b, hipMemcpyHostToDevice, stream) == hipSuccess
-              && hipMemcpyAsync(img, px0.data(), (size_t) S * 2, hipMemcpyHostToDevice, stream) == hipSuccess
+    } else D.planes = (int16_t *) (scratch + up_b + D.img_b);
+    bool ok = hipMemcpyAsync(D.base, D.host.data(), up_b, hipMemcpyHostToDevice, stream) == hipSuccess
+              && hipMemcpyAsync(D.base + up_b, D.px0.data(), (size_t) D.S * 2, hipMemcpyHostToDevice, stream) == hipSuccess
               && hipMemsetAsync(D.planes, 0, D.plane_bytes, stream) == hipSuccess;
     if (!ok) { (void) hipGetLastError(); dec_fail(j, "device decoder: HIP error"); }
     return ok;
 }
 
-/* after the level and assembly launches of the flight: motion compensation of a P/B frame */
+/* after the level and assembly launches of the flight: motion compensation of a P/B frame.  restore_mc is called for
+ * every P/B frame: the clipping of the chroma planes too when no block moved */
 static bool dec_run_mc(fa_dec_job *j, DecFrame &D, hipStream_t stream, int cur_dev)
 {
-    const unsigned mc_maxl = D.mc_maxl, bands = j->color ? 3 : 1, W = j->width, H = j->height;
-    const size_t nodes_b = D.nodes_b, tops_b = D.tops_b, npix = (size_t) W * H;
+    const unsigned bands = j->color ? 3 : 1, W = j->width, H = j->height;
+    const size_t npix = (size_t) W * H;
+    const int16_t *refs[2] = { nullptr, nullptr };
+    const fa_image *src[2] = { j->past, j->future };
     bool ok = true;
-    if (ok && j->frame_type != FA_I_FRAME) {
-        /* restore_mc is called for every P/B frame: the clipping of the chroma planes too when no block moved */
-        const int16_t *refs[2] = { nullptr, nullptr };
-        const fa_image *src[2] = { j->past, j->future };
-        for (int r = 0; r < 2 && ok; r++) {
-            if (!src[r]) continue;
-            if (src[r]->width != W || src[r]->height != H || (src[r]->color != 0) != (j->color != 0)) {
-                dec_fail(j, "device decoder: reference frame of another size"); ok = false; break;
-            }
-            if (src[r]->dev && src[r]->dev_id == cur_dev) { refs[r] = (const int16_t *) src[r]->dev; continue; }
-            int16_t *&up = r ? D.future : D.past;
-            if (hipMalloc((void **) &up, D.plane_bytes) != hipSuccess) { (void) hipGetLastError(); dec_fail(j, "device decoder: out of device memory"); ok = false; break; }
-            for (unsigned b = 0; b < bands && ok; b++)
-                ok = hipMemcpyAsync(up + b * npix, src[r]->pixels[b], npix * 2, hipMemcpyHostToDevice, stream) == hipSuccess;
-            refs[r] = up;
+    for (int r = 0; r < 2 && ok; r++) {
+        if (!src[r]) continue;
+        if (src[r]->width != W || src[r]->height != H || (src[r]->color != 0) != (j->color != 0)) {
+            dec_fail(j, "device decoder: reference frame of another size"); ok = false; break;
         }
-        if (ok && D.nmcs) {
-            const size_t n = ((size_t) D.nmcs * bands) << mc_maxl;
-            dec_mc_kernel<<<dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream>>>((const DecMc *) (D.base + nodes_b + tops_b), D.nmcs,
-                                                                                       mc_maxl, D.planes, refs[0], refs[1], W, H, bands);
-        }
-        if (ok && j->color)
-            dec_clip_chroma_kernel<<<dim3((unsigned) ((2 * npix + 255) / 256)), dim3(256), 0, stream>>>(D.planes, npix);
+        if (src[r]->dev && src[r]->dev_id == cur_dev) { refs[r] = (const int16_t *) src[r]->dev; continue; }
+        int16_t *&up = r ? D.future : D.past;
+        if (hipMalloc((void **) &up, D.plane_bytes) != hipSuccess) { (void) hipGetLastError(); dec_fail(j, "device decoder: out of device memory"); ok = false; break; }
+        for (unsigned b = 0; b < bands && ok; b++)
+            ok = hipMemcpyAsync(up + b * npix, src[r]->pixels[b], npix * 2, hipMemcpyHostToDevice, stream) == hipSuccess;
+        refs[r] = up;
     }
+    if (ok && D.nmcs) {
+        const size_t n = ((size_t) D.nmcs * bands) << D.mc_maxl;
+        dec_mc_kernel<<<dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream>>>((const DecMc *) (D.base + D.nodes_b + D.tops_b), D.nmcs,
+                                                                                   D.mc_maxl, D.planes, refs[0], refs[1], W, H, bands);
+    }
+    if (ok && j->color)
+        dec_clip_chroma_kernel<<<dim3((unsigned) ((2 * npix + 255) / 256)), dim3(256), 0, stream>>>(D.planes, npix);
     if (ok && hipGetLastError() != hipSuccess) ok = false;
     if (!ok && !j->errmsg[0]) dec_fail(j, "device decoder: HIP error");
     return ok;
@@ -347,267 +340,329 @@ extern "C" void fa_core_release_dev(void *dev, int dev_id)
     if (dev) (void) hipFree(dev);
 }
 
-/* One share of fa_core_decode_frames: the jobs `mine_idx' on the device share the calling thread is bound to
- * (for_shares / bind_share, core_hip.cpp).  Returns the number of frames decoded.
- * out != NULL (fiasco_amd_batch_decode_device, output_convert.inc): behind the kernels of every flight ONE launch of
- * oc_convert_kernel writes the frames of the flight as 8-bit pixels into out->target[job]; such a frame gets no host
- * image and no copy to the host (jobs[].out stays NULL, out->done[job] says that it was written).
- * ds != NULL (fiasco_amd_batch_decode_distortion_device, distortion.inc): behind the kernels of every flight the result
- * array is zeroed and ONE launch of ds_distortion_kernel compares the frames of the flight with their originals --
- * ds->orig[job] in place, else the host planes of ds->image[job], copied into the arena -- before the pixels are
- * written, if they are (a frame whose target has no data is measured only); 12 bytes per band come back after the
- * flight's synchronisation.  Such a frame gets no host image either; ds->done[job] says that it was measured. */
-static pthread_mutex_t g_dec_stats_lock = PTHREAD_MUTEX_INITIALIZER;
-static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine_idx, const OcOut *out, const DsOut *ds)
+/* ------------------------------------------------------------------ a share of a call, flight by flight */
+
+/* One share of fa_core_decode_frames, on the device the calling thread is bound to (for_shares / bind_share,
+ * core_hip.cpp): what its flights have in common.  The two optional consumers of a flight's planes:
+ * out != NULL (fiasco_amd_batch_decode_device, output_convert.inc): the frames are written as 8-bit pixels into
+ * out->target[job]; such a frame gets no host image and no copy to the host (jobs[].out stays NULL, out->done[job] says
+ * that it was written).
+ * ds != NULL (fiasco_amd_batch_decode_distortion_device, distortion.inc): the frames are compared with their originals
+ * before the pixels are written, if they are (a frame whose target has no data is measured only).  Such a frame gets
+ * no host image either; ds->done[job] says that it was measured. */
+struct DecShare {
+    fa_dec_job  *jobs;
+    const OcOut *out; const DsOut *ds;          /* the optional consumers */
+    int          device = 0;                    /* the current one */
+    hipStream_t  stream = nullptr;
+    hipEvent_t   ev0 = nullptr, ev1 = nullptr;  /* around the device work of a flight: decoder_us */
+    char        *arena = nullptr; size_t arena_b = 0;       /* one per share, grown when a flight needs more */
+    size_t       flight = DEC_FLIGHT;           /* halved when the level images of a flight do not fit (large blocks at a low quality) */
+    int          good = 0;                      /* frames decoded */
+};
+
+/* The frames of one flight.  The level images of a frame (14 MB at 720p colour) live for one flight only, beside the
+ * slabs of a staged batch.  The flight owns what its asynchronous uploads read -- the frames' host buffers and the three
+ * tables -- until dec_flight_wait has drained the stream, and the carve of the arena. */
+struct DecFlight {
+    std::vector<unsigned> job;                  /* [frame] index into the jobs */
+    std::vector<DecFrame> fr;                   /* [frame] */
+    std::vector<size_t>   alive;                /* the frames nothing has failed yet, in order */
+    std::vector<DecDesc>  descs;                /* one per frame alive after the uploads: blockIdx.y of the level launches */
+    std::vector<OcFrame>  octab; std::vector<DsPlane> dstab;    /* the frames written; the planes measured */
+    union { unsigned long long sums[DS_SLOTS]; char bytes[DS_RES_BYTES]; } dsres;      /* sums, then maxima: 8-byte aligned */
+    /* the arena: the scratch of every frame (DecFrame::scratch_off), then */
+    size_t desc_off = 0, oc_off = 0;            /* the tables of DecDesc and OcFrame */
+    size_t ds_off = 0, res_off = 0, orig_off = 0;       /* measuring: the table of DsPlane, the result array, the originals that come from the host */
+    size_t need = 0;                            /* all of it */
+
+    size_t take(size_t bytes) { const size_t at = need; need += align_up(bytes, 256); return at; }
+};
+
+static_assert(DS_SLOTS == DEC_FLIGHT * 3, "the result array of a measuring launch has three slots per frame of a flight");
+
+/* every frame of the flight that is still alive fails with msg */
+static void dec_flight_fail(DecShare &S, DecFlight &F, const char *msg)
 {
-    int good = 0;
-    {
-        int dev = 0;
-        int here = 0;
-        if (hipGetDevice(&here) != hipSuccess) { (void) hipGetLastError(); dev = -2; }
-        hipStream_t stream = nullptr;
-        if (dev != -2 && hipStreamCreate(&stream) != hipSuccess) { (void) hipGetLastError(); dev = -2; }
-        std::vector<unsigned> todo;
-        for (unsigned i : mine_idx) {
-            fa_dec_job *j = &jobs[i];
-            j->out = nullptr; j->errmsg[0] = 0;
-            if (j->skip) continue;
-            if (dev == -2) { dec_fail(j, "libfiasco_amd: no usable HIP device (the decoder runs on the device; there is no CPU path)"); continue; }
-            todo.push_back(i);
-        }
-        /* in flights of 32 frames: the level images of a frame (14 MB at 720p colour) live for one flight only,
-         * beside the slabs of a staged batch */
-        const size_t FLIGHT = 32;
-        size_t flight = FLIGHT;        /* halved when the level images of a flight do not fit (large blocks at a low quality) */
-        char *arena = nullptr;
-        size_t arena_b = 0;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (dev != -2 && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) { (void) hipGetLastError(); }
-        if (ds && stream) {
-            /* originals read in place: the conversion that wrote them may still run on the upload stream of the share
-             * that owns them (ic_fetch waits on the host for the same reason; here the stream waits) */
-            std::vector<const Staged *> seen;
-            for (unsigned i : todo) {
-                const Staged *S = ds->orig[i] ? (const Staged *) ds->image[i]->src_owner : nullptr;
-                if (!S || !S->ev_up || std::find(seen.begin(), seen.end(), S) != seen.end()) continue;
-                seen.push_back(S);
-                if (hipStreamWaitEvent(stream, S->ev_up, 0) != hipSuccess) (void) hipGetLastError();
-            }
-        }
-        for (size_t f0 = 0; f0 < todo.size(); ) {
-            const size_t f1 = f0 + flight < todo.size() ? f0 + flight : todo.size();
-            const size_t f0_next = f1;
-            std::vector<DecFrame> fr(f1 - f0);
-            std::vector<size_t> mine;
-            std::vector<DecDesc> descs;
-            std::vector<OcFrame> octab;                    /* source of an asynchronous upload, like descs */
-            std::vector<DsPlane> dstab;                    /* likewise */
-            union { unsigned long long sums[DS_SLOTS]; char bytes[DS_RES_BYTES]; } dsres;
-            size_t need = 0;
-            for (size_t f = f0; f < f1; f++)
-                if (dec_prepare(&jobs[todo[f]], fr[f - f0])) { mine.push_back(f); need += align_up(fr[f - f0].scratch_b, 256); }
-            const size_t desc_off = need;
-            need += align_up(FLIGHT * sizeof(DecDesc), 256);
-            const size_t oc_off = need;
-            if (out) need += align_up(FLIGHT * sizeof(OcFrame), 256);
-            /* measuring: the table of the planes, the result array, the originals that come from the host */
-            const size_t ds_off = need;
-            if (ds) need += align_up(DS_SLOTS * sizeof(DsPlane), 256);
-            const size_t res_off = need;
-            if (ds) need += align_up(DS_RES_BYTES, 256);
-            const size_t orig_off = need;
-            if (ds) for (size_t f : mine) if (!ds->orig[todo[f]]) need += fr[f - f0].plane_bytes;
-            if (need > arena_b) {                          /* one arena per device, grown when a flight needs more */
-                if (arena) (void) hipFree(arena);
-                arena = nullptr; arena_b = 0;
-                if (hipMalloc((void **) &arena, need) == hipSuccess) arena_b = need;
-                else {
-                    (void) hipGetLastError();
-                    if (flight > 1) {                          /* the same frames again in smaller flights */
-                        flight = flight / 2;
-                        for (size_t f = f0; f < f1; f++) { jobs[todo[f]].out = nullptr; jobs[todo[f]].errmsg[0] = 0; }
-                        continue;
-                    }
-                    for (size_t f : mine) dec_fail(&jobs[todo[f]], "device decoder: out of device memory");
-                    mine.clear();
-                }
-            }
-            (void) hipEventRecord(ev0, stream);
-            {
-                size_t off = 0;
-                std::vector<size_t> run;
-                descs.clear();
-                unsigned lmax = 0;
-                size_t nlev = 0, nasm = 0;
-                for (size_t f : mine) {
-                    DecFrame &D = fr[f - f0];
-                    if (dec_run(&jobs[todo[f]], D, arena + off, stream, here)) {
-                        DecDesc d;
-                        d.nodes = (const DecNode *) D.base; d.img = (int16_t *) (D.base + D.nodes_b + D.tops_b + D.mcs_b);
-                        d.tops = (const DecTop *) (D.base + D.nodes_b); d.planes = D.planes;
-                        d.S = D.S; d.maxl = D.maxl; d.ntops = D.ntops; d.W = jobs[todo[f]].width; d.H = jobs[todo[f]].height;
-                        descs.push_back(d);
-                        run.push_back(f);
-                        if (D.maxl > lmax) lmax = D.maxl;
-                        if (D.S > nlev) nlev = D.S;
-                        if (((size_t) D.ntops << D.maxl) > nasm) nasm = (size_t) D.ntops << D.maxl;
-                    }
-                    off += align_up(D.scratch_b, 256);
-                }
-                mine.swap(run);
-                /* one launch per level for the whole flight (blockIdx.y = frame), one for the assembly */
-                if (!mine.empty() && hipMemcpyAsync(arena + desc_off, descs.data(), descs.size() * sizeof(DecDesc), hipMemcpyHostToDevice, stream) == hipSuccess) {
-                    const DecDesc *dd = (const DecDesc *) (arena + desc_off);
-                    for (unsigned l = 1; l < lmax; l++) {          /* (the largest level of a frame: dec_assemble_kernel) */
-                        const size_t n = nlev << l;             /* largest S of the flight */
-                        dec_level_kernel<<<dim3((unsigned) ((n + 255) / 256), (unsigned) descs.size()), dim3(256), 0, stream>>>(dd, l);
-                    }
-                    if (nasm) dec_assemble_kernel<<<dim3((unsigned) ((nasm + 255) / 256), (unsigned) descs.size()), dim3(256), 0, stream>>>(dd);
-                    run.clear();
-                    for (size_t f : mine)
-                        if (jobs[todo[f]].frame_type == FA_I_FRAME || dec_run_mc(&jobs[todo[f]], fr[f - f0], stream, here)) run.push_back(f);
-                    mine.swap(run);
-                } else if (!mine.empty()) {
-                    (void) hipGetLastError();
-                    for (size_t f : mine) dec_fail(&jobs[todo[f]], "device decoder: HIP error");
-                    mine.clear();
-                }
-                if (ds && !mine.empty()) {
-                    /* the frames of the flight against their originals */
-                    size_t at = orig_off;
-                    bool ok = true;
-                    for (size_t k = 0; k < mine.size() && ok; k++) {
-                        const fa_dec_job *j = &jobs[todo[mine[k]]];
-                        const DecFrame &D = fr[mine[k] - f0];
-                        const unsigned bands = j->color ? 3 : 1;
-                        const size_t npix = (size_t) j->width * j->height;
-                        const int16_t *o = ds->orig[todo[mine[k]]];
-                        if (!o) {
-                            const fa_image *im = ds->image[todo[mine[k]]];
-                            for (unsigned b = 0; b < bands && ok; b++)
-                                ok = hipMemcpyAsync(arena + at + b * npix * 2, im->pixels[b], npix * 2, hipMemcpyHostToDevice, stream) == hipSuccess;
-                            o = (const int16_t *) (arena + at);
-                            at += D.plane_bytes;
-                        }
-                        ds_describe(dstab, (unsigned) k, o, D.planes, j->width, j->height, bands);
-                    }
-                    if (!ok || hipMemsetAsync(arena + res_off, 0, DS_RES_BYTES, stream) != hipSuccess
-                        || hipMemcpyAsync(arena + ds_off, dstab.data(), dstab.size() * sizeof(DsPlane), hipMemcpyHostToDevice, stream) != hipSuccess
-                        || !ds_launch((const DsPlane *) (arena + ds_off), dstab, arena + res_off, oc_cus(), stream)) {
-                        (void) hipGetLastError();
-                        for (size_t f : mine) dec_fail(&jobs[todo[f]], "device decoder: HIP error");
-                        mine.clear();
-                    }
-                }
-                if (out && !mine.empty()) {
-                    /* the frames of the flight into the caller's buffers, once the caller's stream has let go of them */
-                    unsigned long long total = 0;
-                    for (size_t k = 0; k < mine.size(); k++) {
-                        if (!out->target[todo[mine[k]]].data) continue;            /* measured only */
-                        octab.emplace_back();
-                        oc_describe(octab.back(), fr[mine[k] - f0].planes, out->target[todo[mine[k]]], total);
-                    }
-                    if (!octab.empty()
-                        && (hipStreamWaitEvent(stream, out->ready, 0) != hipSuccess
-                            || hipMemcpyAsync(arena + oc_off, octab.data(), octab.size() * sizeof(OcFrame), hipMemcpyHostToDevice, stream) != hipSuccess
-                            || !oc_launch((const OcFrame *) (arena + oc_off), (unsigned) octab.size(), total, oc_cus(), stream))) {
-                        (void) hipGetLastError();
-                        for (size_t f : mine) dec_fail(&jobs[todo[f]], "device decoder: HIP error");
-                        mine.clear();
-                    }
-                }
-            }
-            (void) hipEventRecord(ev1, stream);
-            if (hipStreamSynchronize(stream) != hipSuccess) {
-                (void) hipGetLastError();
-                for (size_t f : mine) dec_fail(&jobs[todo[f]], "device decoder: kernel failed");
-                mine.clear();
-            }
-            if (ds && !mine.empty() && hipMemcpy(dsres.bytes, arena + res_off, DS_RES_BYTES, hipMemcpyDeviceToHost) != hipSuccess) {
-                (void) hipGetLastError();
-                for (size_t f : mine) dec_fail(&jobs[todo[f]], "device decoder: download failed");
-                mine.clear();
-            }
-            {
-                float ms = 0;
-                if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) {
-                    pthread_mutex_lock(&g_dec_stats_lock);
-                    g_stats.decoder_us += (unsigned long long) (ms * 1000.0f);
-                    pthread_mutex_unlock(&g_dec_stats_lock);
-                } else (void) hipGetLastError();
-            }
-            for (size_t k = 0; k < mine.size(); k++) {
-                const size_t f = mine[k];
-                fa_dec_job *j = &jobs[todo[f]];
-                DecFrame &D = fr[f - f0];
-                if (out || ds) {
-                    /* pixels: 2 bytes read per pixel and band, the 8-bit pixel written; measuring: 2 bytes read per side */
-                    const unsigned long long vals = (unsigned long long) j->width * j->height * (j->color ? 3 : 1);
-                    const bool written = out && out->target[todo[f]].data;
-                    if (written) out->done[todo[f]] = 1;
-                    if (ds) {
-                        const unsigned *mx = (const unsigned *) (dsres.bytes + DS_SLOTS * sizeof(unsigned long long));
-                        for (unsigned b = 0; b < (j->color ? 3u : 1u); b++) {
-                            if (ds->sse) ds->sse[(size_t) todo[f] * 3 + b] = dsres.sums[k * 3 + b];
-                            if (ds->maxdiff) ds->maxdiff[(size_t) todo[f] * 3 + b] = mx[k * 3 + b];
-                        }
-                        ds->done[todo[f]] = 1;
-                    }
-                    pthread_mutex_lock(&g_dec_stats_lock);
-                    g_stats.decoder_frames += 1; g_stats.decoder_bytes += D.bytes + (ds ? 4 * vals : 0) + (written ? 3 * vals : 0);
-                    pthread_mutex_unlock(&g_dec_stats_lock);
-                    good++;
-                    continue;
-                }
-                fa_image *im = fa_image_alloc(j->width, j->height, j->color);
-                const size_t npix = (size_t) j->width * j->height;
-                bool ok = im != nullptr;
-                for (int b = 0; ok && b < (j->color ? 3 : 1); b++)
-                    ok = hipMemcpy(im->pixels[b], D.planes + (size_t) b * npix, npix * 2, hipMemcpyDeviceToHost) == hipSuccess;
-                if (!ok) { fa_image_free(im); dec_fail(j, "device decoder: download failed"); continue; }
-                if (D.own_planes) { im->dev = D.planes; im->dev_id = here; D.planes = nullptr; }
-                j->out = im;
-                pthread_mutex_lock(&g_dec_stats_lock);
-                g_stats.decoder_frames += 1; g_stats.decoder_bytes += D.bytes;
-                pthread_mutex_unlock(&g_dec_stats_lock);
-                good++;
-            }
-            for (size_t f = 0; f < fr.size(); f++) {
-                if (fr[f].own_planes && fr[f].planes) (void) hipFree(fr[f].planes);
-                if (fr[f].past) (void) hipFree(fr[f].past);
-                if (fr[f].future) (void) hipFree(fr[f].future);
-            }
-            f0 = f0_next;
-        }
-        if (out && stream) {
-            /* the caller's stream behind the conversions: it may read the pixels without a host synchronisation */
-            hipEvent_t written = nullptr;
-            if (hipEventCreateWithFlags(&written, hipEventDisableTiming) != hipSuccess || hipEventRecord(written, stream) != hipSuccess
-                || hipStreamWaitEvent(out->caller, written, 0) != hipSuccess) (void) hipGetLastError();
-            if (written) (void) hipEventDestroy(written);
-        }
-        if (arena) (void) hipFree(arena);
-        if (ev0) (void) hipEventDestroy(ev0);
-        if (ev1) (void) hipEventDestroy(ev1);
-        if (stream) (void) hipStreamDestroy(stream);
-    }
-    return good;
+    (void) hipGetLastError();
+    for (size_t k : F.alive) dec_fail(&S.jobs[F.job[k]], msg);
+    F.alive.clear();
 }
 
-/* decode n frames.  A job runs on the device share the SEARCH deals it to -- fa_share_of(): by its key where it has
- * one (the GOP of a video), by its index otherwise --, so that the reference frame of a GOP is decoded where the next
- * frame of that GOP is searched and stays in that device's HBM (fa_image.dev).  The shares decode side by side, each
- * on its own host thread (share 0 on the caller's; for_shares, core_hip.cpp).  Returns the number of frames decoded; a
- * failed job has out == NULL and a message. */
+static pthread_mutex_t g_dec_stats_lock = PTHREAD_MUTEX_INITIALIZER;
+static void dec_account(unsigned long long us, unsigned frames, unsigned long long bytes)
+{
+    pthread_mutex_lock(&g_dec_stats_lock);
+    g_stats.decoder_us += us; g_stats.decoder_frames += frames; g_stats.decoder_bytes += bytes;
+    pthread_mutex_unlock(&g_dec_stats_lock);
+}
+
+/* host side of the n frames `idx': their automata as integers, and where everything lies in the arena.  The tables
+ * are sized for a full flight whatever n is */
+static void dec_flight_prepare(DecShare &S, DecFlight &F, const unsigned *idx, size_t n)
+{
+    F.job.assign(idx, idx + n);
+    F.fr.resize(n);
+    for (size_t k = 0; k < n; k++)
+        if (dec_prepare(&S.jobs[F.job[k]], F.fr[k])) { F.alive.push_back(k); F.fr[k].scratch_off = F.take(F.fr[k].scratch_b); }
+    F.desc_off = F.take(DEC_FLIGHT * sizeof(DecDesc));
+    F.oc_off = F.take(S.out ? DEC_FLIGHT * sizeof(OcFrame) : 0);
+    F.ds_off = F.take(S.ds ? DS_SLOTS * sizeof(DsPlane) : 0);
+    F.res_off = F.take(S.ds ? DS_RES_BYTES : 0);
+    F.orig_off = F.need;
+    if (S.ds) for (size_t k : F.alive) if (!S.ds->orig[F.job[k]]) (void) F.take(F.fr[k].plane_bytes);
+}
+
+/* an arena that holds the flight.  false: it cannot be had, the flight size is halved and the caller tries the same
+ * frames again in smaller flights; a single frame that does not fit fails */
+static bool dec_flight_room(DecShare &S, DecFlight &F)
+{
+    if (F.need <= S.arena_b) return true;
+    if (S.arena) (void) hipFree(S.arena);
+    S.arena = nullptr; S.arena_b = 0;
+    if (hipMalloc((void **) &S.arena, F.need) == hipSuccess) { S.arena_b = F.need; return true; }
+    if (S.flight > 1) {
+        (void) hipGetLastError();
+        S.flight = S.flight / 2;
+        for (unsigned i : F.job) { S.jobs[i].out = nullptr; S.jobs[i].errmsg[0] = 0; }
+        return false;
+    }
+    dec_flight_fail(S, F, "device decoder: out of device memory");
+    return true;
+}
+
+/* per frame the automaton, the level-0 images and the zeroed planes; then the descriptors of the frames that got there */
+static void dec_flight_upload(DecShare &S, DecFlight &F)
+{
+    std::vector<size_t> run;
+    for (size_t k : F.alive) {
+        DecFrame &D = F.fr[k];
+        fa_dec_job *j = &S.jobs[F.job[k]];
+        if (!dec_run(j, D, S.arena + D.scratch_off, S.stream)) continue;
+        DecDesc d;
+        d.nodes = (const DecNode *) D.base; d.img = (int16_t *) (D.base + D.nodes_b + D.tops_b + D.mcs_b);
+        d.tops = (const DecTop *) (D.base + D.nodes_b); d.planes = D.planes;
+        d.S = D.S; d.maxl = D.maxl; d.ntops = D.ntops; d.W = j->width; d.H = j->height;
+        F.descs.push_back(d);
+        run.push_back(k);
+    }
+    F.alive.swap(run);
+    if (!F.alive.empty() && hipMemcpyAsync(S.arena + F.desc_off, F.descs.data(), F.descs.size() * sizeof(DecDesc), hipMemcpyHostToDevice, S.stream) != hipSuccess)
+        dec_flight_fail(S, F, "device decoder: HIP error");
+}
+
+/* one launch per level for the whole flight (blockIdx.y = frame), one for the assembly */
+static void dec_flight_levels(DecShare &S, DecFlight &F)
+{
+    if (F.alive.empty()) return;
+    unsigned lmax = 0;
+    size_t nlev = 0, nasm = 0;                         /* the largest S and the most top-level pixels of the flight */
+    for (const DecDesc &d : F.descs) {
+        if (d.maxl > lmax) lmax = d.maxl;
+        if (d.S > nlev) nlev = d.S;
+        if (((size_t) d.ntops << d.maxl) > nasm) nasm = (size_t) d.ntops << d.maxl;
+    }
+    const DecDesc *dd = (const DecDesc *) (S.arena + F.desc_off);
+    for (unsigned l = 1; l < lmax; l++) {              /* (the largest level of a frame: dec_assemble_kernel) */
+        const size_t n = nlev << l;
+        dec_level_kernel<<<dim3((unsigned) ((n + 255) / 256), (unsigned) F.descs.size()), dim3(256), 0, S.stream>>>(dd, l);
+    }
+    if (nasm) dec_assemble_kernel<<<dim3((unsigned) ((nasm + 255) / 256), (unsigned) F.descs.size()), dim3(256), 0, S.stream>>>(dd);
+}
+
+/* the P/B frames of the flight; one that fails drops out alone */
+static void dec_flight_mc(DecShare &S, DecFlight &F)
+{
+    std::vector<size_t> run;
+    for (size_t k : F.alive)
+        if (S.jobs[F.job[k]].frame_type == FA_I_FRAME || dec_run_mc(&S.jobs[F.job[k]], F.fr[k], S.stream, S.device)) run.push_back(k);
+    F.alive.swap(run);
+}
+
+/* the frames of the flight against their originals -- ds->orig[job] in place, else the host planes of ds->image[job],
+ * copied into the arena --: the result array is zeroed and ONE launch of ds_distortion_kernel fills it.  The frames
+ * alive now get the slots; from here on the flight lives or fails as a whole, so a slot stays its frame's */
+static void dec_flight_measure(DecShare &S, DecFlight &F)
+{
+    if (F.alive.empty()) return;
+    size_t at = F.orig_off;
+    unsigned slot = 0; bool ok = true;
+    for (size_t k : F.alive) {
+        const fa_dec_job *j = &S.jobs[F.job[k]];
+        DecFrame &D = F.fr[k];
+        const unsigned bands = j->color ? 3 : 1;
+        const size_t npix = (size_t) j->width * j->height;
+        const int16_t *o = S.ds->orig[F.job[k]];
+        if (!o) {
+            const fa_image *im = S.ds->image[F.job[k]];
+            for (unsigned b = 0; b < bands && ok; b++)
+                ok = hipMemcpyAsync(S.arena + at + b * npix * 2, im->pixels[b], npix * 2, hipMemcpyHostToDevice, S.stream) == hipSuccess;
+            o = (const int16_t *) (S.arena + at);
+            at += D.plane_bytes;
+        }
+        if (!ok) break;
+        D.slot = slot++;
+        ds_describe(F.dstab, D.slot, o, D.planes, j->width, j->height, bands);
+    }
+    if (!ok || hipMemsetAsync(S.arena + F.res_off, 0, DS_RES_BYTES, S.stream) != hipSuccess
+        || hipMemcpyAsync(S.arena + F.ds_off, F.dstab.data(), F.dstab.size() * sizeof(DsPlane), hipMemcpyHostToDevice, S.stream) != hipSuccess
+        || !ds_launch((const DsPlane *) (S.arena + F.ds_off), F.dstab, S.arena + F.res_off, oc_cus(), S.stream))
+        dec_flight_fail(S, F, "device decoder: HIP error");
+}
+
+/* the frames of the flight that have a target into the caller's buffers, once the caller's stream has let go of them:
+ * ONE launch of oc_convert_kernel */
+static void dec_flight_write(DecShare &S, DecFlight &F)
+{
+    unsigned long long total = 0;
+    for (size_t k : F.alive) {
+        if (!S.out->target[F.job[k]].data) continue;            /* measured only */
+        F.octab.emplace_back();
+        oc_describe(F.octab.back(), F.fr[k].planes, S.out->target[F.job[k]], total);
+    }
+    if (!F.octab.empty()
+        && (hipStreamWaitEvent(S.stream, S.out->ready, 0) != hipSuccess
+            || hipMemcpyAsync(S.arena + F.oc_off, F.octab.data(), F.octab.size() * sizeof(OcFrame), hipMemcpyHostToDevice, S.stream) != hipSuccess
+            || !oc_launch((const OcFrame *) (S.arena + F.oc_off), (unsigned) F.octab.size(), total, oc_cus(), S.stream)))
+        dec_flight_fail(S, F, "device decoder: HIP error");
+}
+
+/* the end of the flight's device work; measuring: 12 bytes per band come back */
+static void dec_flight_wait(DecShare &S, DecFlight &F)
+{
+    (void) hipEventRecord(S.ev1, S.stream);
+    if (hipStreamSynchronize(S.stream) != hipSuccess) dec_flight_fail(S, F, "device decoder: kernel failed");
+    if (S.ds && !F.alive.empty() && hipMemcpy(F.dsres.bytes, S.arena + F.res_off, DS_RES_BYTES, hipMemcpyDeviceToHost) != hipSuccess)
+        dec_flight_fail(S, F, "device decoder: download failed");
+}
+
+/* a frame nobody consumed on the device: its planes as a host image, which keeps the device planes of a keep_dev frame */
+static bool dec_download(DecShare &S, fa_dec_job *j, DecFrame &D)
+{
+    fa_image *im = fa_image_alloc(j->width, j->height, j->color);
+    const size_t npix = (size_t) j->width * j->height;
+    bool ok = im != nullptr;
+    for (int b = 0; ok && b < (j->color ? 3 : 1); b++)
+        ok = hipMemcpy(im->pixels[b], D.planes + (size_t) b * npix, npix * 2, hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) { fa_image_free(im); dec_fail(j, "device decoder: download failed"); return false; }
+    if (D.own_planes) { im->dev = D.planes; im->dev_id = S.device; D.planes = nullptr; }
+    j->out = im;
+    return true;
+}
+
+/* what the frames alive at the end get: done[] and the sums, or a host image; and the statistics.  Pixels: 2 bytes
+ * read per pixel and band, the 8-bit pixel written; measuring: 2 bytes read per side */
+static void dec_flight_results(DecShare &S, DecFlight &F)
+{
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, S.ev0, S.ev1) != hipSuccess) { (void) hipGetLastError(); ms = 0; }
+    unsigned frames = 0;
+    unsigned long long bytes = 0;
+    const unsigned *mx = (const unsigned *) (F.dsres.bytes + DS_SLOTS * sizeof(unsigned long long));
+    for (size_t k : F.alive) {
+        const unsigned i = F.job[k];
+        fa_dec_job *j = &S.jobs[i];
+        DecFrame &D = F.fr[k];
+        const unsigned bands = j->color ? 3 : 1;
+        const unsigned long long vals = (unsigned long long) j->width * j->height * bands;
+        const bool written = S.out && S.out->target[i].data;
+        if (written) S.out->done[i] = 1;
+        if (S.ds) {
+            for (unsigned b = 0; b < bands; b++) {
+                if (S.ds->sse) S.ds->sse[(size_t) i * 3 + b] = F.dsres.sums[D.slot * 3 + b];
+                if (S.ds->maxdiff) S.ds->maxdiff[(size_t) i * 3 + b] = mx[D.slot * 3 + b];
+            }
+            S.ds->done[i] = 1;
+        }
+        if (!S.out && !S.ds && !dec_download(S, j, D)) continue;
+        frames++;
+        bytes += D.bytes + (S.ds ? 4 * vals : 0) + (written ? 3 * vals : 0);
+    }
+    dec_account((unsigned long long) (ms * 1000.0f), frames, bytes);
+    S.good += (int) frames;
+}
+
+/* what the frames allocated for themselves, failed or not; the planes a host image took over stay */
+static void dec_flight_release(DecFlight &F)
+{
+    for (DecFrame &D : F.fr) {
+        if (D.own_planes && D.planes) (void) hipFree(D.planes);
+        if (D.past) (void) hipFree(D.past);
+        if (D.future) (void) hipFree(D.future);
+    }
+}
+
+/* originals read in place: the conversion that wrote them may still run on the upload stream of the share that owns
+ * them (ic_fetch waits on the host for the same reason; here the stream waits), once per owner */
+static void dec_share_wait_originals(DecShare &S, const std::vector<unsigned> &todo)
+{
+    std::vector<const Staged *> seen;
+    for (unsigned i : todo) {
+        const Staged *own = S.ds->orig[i] ? (const Staged *) S.ds->image[i]->src_owner : nullptr;
+        if (!own || !own->ev_up || std::find(seen.begin(), seen.end(), own) != seen.end()) continue;
+        seen.push_back(own);
+        if (hipStreamWaitEvent(S.stream, own->ev_up, 0) != hipSuccess) (void) hipGetLastError();
+    }
+}
+
+/* the caller's stream behind the conversions: it may read the pixels without a host synchronisation */
+static void dec_share_release_caller(DecShare &S)
+{
+    hipEvent_t written = nullptr;
+    if (hipEventCreateWithFlags(&written, hipEventDisableTiming) != hipSuccess || hipEventRecord(written, S.stream) != hipSuccess
+        || hipStreamWaitEvent(S.out->caller, written, 0) != hipSuccess) (void) hipGetLastError();
+    if (written) (void) hipEventDestroy(written);
+}
+
+/* the jobs `mine' of a call on this thread's device, in flights.  Returns the number of frames decoded */
+static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine, const OcOut *out, const DsOut *ds)
+{
+    DecShare S;
+    S.jobs = jobs; S.out = out; S.ds = ds;
+    bool usable = hipGetDevice(&S.device) == hipSuccess && hipStreamCreate(&S.stream) == hipSuccess;
+    if (!usable) (void) hipGetLastError();
+    else if (hipEventCreate(&S.ev0) != hipSuccess || hipEventCreate(&S.ev1) != hipSuccess) (void) hipGetLastError();
+    std::vector<unsigned> todo;
+    for (unsigned i : mine) {
+        fa_dec_job *j = &jobs[i];
+        j->out = nullptr; j->errmsg[0] = 0;
+        if (j->skip) continue;
+        if (!usable) { dec_fail(j, "libfiasco_amd: no usable HIP device (the decoder runs on the device; there is no CPU path)"); continue; }
+        todo.push_back(i);
+    }
+    if (ds && S.stream) dec_share_wait_originals(S, todo);
+    for (size_t f0 = 0; f0 < todo.size(); ) {
+        const size_t n = S.flight < todo.size() - f0 ? S.flight : todo.size() - f0;
+        DecFlight F;
+        dec_flight_prepare(S, F, &todo[f0], n);
+        if (!dec_flight_room(S, F)) continue;
+        (void) hipEventRecord(S.ev0, S.stream);
+        dec_flight_upload(S, F);
+        dec_flight_levels(S, F);
+        dec_flight_mc(S, F);
+        if (ds) dec_flight_measure(S, F);
+        if (out) dec_flight_write(S, F);
+        dec_flight_wait(S, F);
+        dec_flight_results(S, F);
+        dec_flight_release(F);
+        f0 += n;
+    }
+    if (out && S.stream) dec_share_release_caller(S);
+    if (S.arena) (void) hipFree(S.arena);
+    if (S.ev0) (void) hipEventDestroy(S.ev0);
+    if (S.ev1) (void) hipEventDestroy(S.ev1);
+    if (S.stream) (void) hipStreamDestroy(S.stream);
+    return S.good;
+}
+
+/* decode n frames: dealt to the shares by the rule of dec_shares / dec_share_of (core_hip.cpp), the shares decode side
+ * by side, each on its own host thread (share 0 on the caller's; for_shares, core_hip.cpp).  Returns the number of
+ * frames decoded; a failed job has out == NULL and a message. */
 static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const DsOut *ds)
 {
-    resolve_devices();
-    size_t ND = g_devices.size();
-    bool keyed = false;
-    for (unsigned i = 0; i < n; i++) keyed = keyed || jobs[i].share_key != 0;
-    if (!keyed && ND > n) ND = n ? n : 1;
+    const size_t ND = dec_shares(n, jobs);
     std::vector<std::vector<unsigned> > deal(ND);
-    for (unsigned i = 0; i < n; i++) deal[fa_share_of(jobs[i].share_key, i, (unsigned) ND)].push_back(i);
+    for (unsigned i = 0; i < n; i++) deal[dec_share_of(jobs, i, ND)].push_back(i);
     std::vector<size_t> share;
     for (size_t k = 0; k < ND; k++) if (!deal[k].empty()) share.push_back(k);
     if (share.empty()) return 0;
@@ -617,7 +672,5 @@ static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const D
     for (size_t k = 0; k < goodv.size(); k++) good += goodv[k];
     return good;
 }
-
-static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out) { return decode_frames(n, jobs, out, nullptr); }
 
 extern "C" int fa_core_decode_frames(unsigned n, fa_dec_job *jobs) { return decode_frames(n, jobs, nullptr, nullptr); }

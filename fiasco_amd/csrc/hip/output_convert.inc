@@ -153,8 +153,6 @@ struct OcOut {
     hipStream_t    caller;                      /* made to wait for the conversions */
 };
 
-static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out);      /* frame_decoder.inc */
-
 static void oc_describe(OcFrame &d, const int16_t *planes, const fiasco_amd_device_frame &t, unsigned long long &total)
 {
     d.src = planes; d.dst = (unsigned char *) t.data;
@@ -216,52 +214,70 @@ static bool oc_check_target(unsigned i, const fiasco_amd_device_target *in, unsi
     return true;
 }
 
-extern "C" int fiasco_amd_batch_decode_device(const fiasco_amd_batch_t *b, const fiasco_amd_device_target *targets, void *stream)
+/* What the two batch entry points (this one and fiasco_amd_batch_decode_distortion_device, distortion.inc) have in
+ * common: the batch has a finished pass; every finished intra frame becomes a job of the decoder, the others are
+ * skipped; a frame with a target (targets may be NULL) has it checked and lives where the frame will be decoded.
+ * who: the entry point, for the messages; refuse: what it holds against its own arguments, if anything. */
+struct OcBatch {
+    std::vector<fa_dec_job> jobs;                         /* [n]; skip = 1: no finished intra frame */
+    std::vector<fiasco_amd_device_frame> target;          /* [n] checked, pitch and plane stride filled in; data == NULL: none */
+    std::vector<int> device;                              /* [n] the device the job is decoded on */
+};
+
+static bool oc_batch_jobs(const char *who, const char *refuse, const fiasco_amd_batch_t *b, const fiasco_amd_device_target *targets, OcBatch &B)
 {
-    if (!b || !b->n) { fa_set_error("fiasco_amd_batch_decode_device: empty batch"); return 0; }
-    if (!targets) { fa_set_error("fiasco_amd_batch_decode_device: no targets"); return 0; }
-    if (!ic_have_device()) return 0;
+    if (!b || !b->n) { fa_set_error("%s: empty batch", who); return false; }
+    if (refuse) { fa_set_error("%s: %s", who, refuse); return false; }
+    if (!ic_have_device()) return false;
     const unsigned n = b->n;
     bool finished = false;
     for (unsigned i = 0; i < n; i++) finished = finished || (b->jobs[i].status && b->jobs[i].wfa);
-    if (!finished) { fa_set_error("fiasco_amd_batch_decode_device: the batch has no finished pass"); return 0; }
-    /* the share a job is decoded on is the one fa_core_decode_frames deals it to */
-    resolve_devices();
-    size_t ND = g_devices.size();
-    if (ND > n) ND = n;
+    if (!finished) { fa_set_error("%s: the batch has no finished pass", who); return false; }
+    B.jobs.assign(n, fa_dec_job()); B.target.assign(n, fiasco_amd_device_frame()); B.device.assign(n, -1);
+    const size_t shares = dec_shares(n, B.jobs.data());
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess) { (void) hipGetLastError(); cur = -1; }
-    std::vector<fa_dec_job> d(n);
-    std::vector<fiasco_amd_device_frame> fr(n);
-    std::vector<unsigned char> done(n, 0);
-    unsigned wanted = 0;
-    memset(d.data(), 0, n * sizeof(fa_dec_job));
-    memset(fr.data(), 0, n * sizeof(fiasco_amd_device_frame));
     for (unsigned i = 0; i < n; i++) {
         const fa_job *job = &b->jobs[i];
-        d[i].skip = 1;
-        if (!job->status || !job->wfa || job->frame_type != FA_I_FRAME || !targets[i].data) continue;
-        int tdev = -1;
-        if (!oc_check_target(i, &targets[i], job->image->width, job->image->height, job->image->color, &fr[i], &tdev)) return 0;
-        const int sdev = g_devices[fa_share_of(0, i, (unsigned) ND)] >= 0 ? g_devices[fa_share_of(0, i, (unsigned) ND)] : cur;
-        if (tdev != sdev) {
-            fa_set_error("<device target %u>: the target lives on device %d, the frame is decoded on device %d (no peer copy on this path).", i, tdev, sdev);
-            return 0;
+        fa_dec_job &d = B.jobs[i];
+        d.skip = 1;
+        if (!job->status || !job->wfa || job->frame_type != FA_I_FRAME) continue;
+        B.device[i] = dec_device_of(B.jobs.data(), i, shares, cur);
+        if (targets && targets[i].data) {
+            int tdev = -1;
+            if (!oc_check_target(i, &targets[i], job->image->width, job->image->height, job->image->color, &B.target[i], &tdev)) return false;
+            if (tdev != B.device[i]) {
+                fa_set_error("<device target %u>: the target lives on device %d, the frame is decoded on device %d (no peer copy on this path).", i, tdev, B.device[i]);
+                return false;
+            }
         }
-        d[i].skip = 0;
-        d[i].wfa = job->wfa; d[i].width = job->image->width; d[i].height = job->image->height; d[i].color = job->image->color;
-        d[i].frame_type = FA_I_FRAME;
-        wanted++;
+        d.skip = 0;
+        d.wfa = job->wfa; d.width = job->image->width; d.height = job->image->height; d.color = job->image->color;
+        d.frame_type = FA_I_FRAME;
+    }
+    return true;
+}
+
+extern "C" int fiasco_amd_batch_decode_device(const fiasco_amd_batch_t *b, const fiasco_amd_device_target *targets, void *stream)
+{
+    OcBatch B;
+    if (!oc_batch_jobs("fiasco_amd_batch_decode_device", targets ? nullptr : "no targets", b, targets, B)) return 0;
+    const unsigned n = b->n;
+    std::vector<unsigned char> done(n, 0);
+    unsigned wanted = 0;
+    for (unsigned i = 0; i < n; i++) {
+        if (!B.target[i].data) B.jobs[i].skip = 1;                 /* a frame without a target is skipped */
+        wanted += !B.jobs[i].skip;
     }
     if (!wanted) { fa_set_error("fiasco_amd_batch_decode_device: no frame with a finished intra automaton and a target"); return 0; }
     OcOut out;
-    out.target = fr.data(); out.done = done.data(); out.caller = (hipStream_t) stream;
+    out.target = B.target.data(); out.done = done.data(); out.caller = (hipStream_t) stream;
     out.ready = ic_mark_ready(stream);
     if (!out.ready) return 0;
-    const int good = decode_frames(n, d.data(), &out);
+    const int good = decode_frames(n, B.jobs.data(), &out, nullptr);
     (void) hipEventDestroy(out.ready);
     for (unsigned i = 0; i < n; i++)
-        if (!d[i].skip && !done[i]) fa_set_error("<device target %u>: %s", i, d[i].errmsg[0] ? d[i].errmsg : "decoder failed");
+        if (!B.jobs[i].skip && !done[i]) fa_set_error("<device target %u>: %s", i, B.jobs[i].errmsg[0] ? B.jobs[i].errmsg : "decoder failed");
     return good;
 }
 

@@ -187,6 +187,42 @@ def test_forty_frames_are_two_flights(gpu):
     o.delete()
 
 
+def test_a_frame_that_drops_out_of_a_flight_shifts_no_result(gpu, inputs):
+    """35 frames, the second of which fails to code (MAXSTATES 103: the 256 x 256 survey image needs one state more): the
+    first flight holds the jobs 0, 2 .. 32 -- from job 2 on a frame's place in the flight, which is its slot in the
+    result array of the measuring launch, is not its job index --, the second the jobs 33 and 34.  Every number and every
+    written target is its own frame's.  (The seeds: every 32 x 32 frame codes under that limit and all 34 sums differ,
+    found with the oracle library; asserted again below.)"""
+    o = gpu.cli_options()
+    pnms = [pnm_of(synth.synth(32, 32, 400 + i)) for i in range(34)]
+    pnms.insert(1, inputs.data("g256"))
+    good = [i for i in range(35) if i != 1]
+    try:
+        gpu.set_limits(103, 22)
+        b = fiasco_amd.Batch(gpu, pnms, 20.0, o)
+        out = b.encode()
+        assert out[1] is None and None not in [out[i] for i in good], gpu.error_message()
+        want = {i: reference_of_batch(b, i) for i in good}
+        sums = set(want[i][0][0] for i in good)
+        assert 0 not in sums and len(sums) >= 20                # distinct frames, distinct numbers
+        big = pattern(18, 40, 40)                               # the targets of the even frames, cut out of a pattern
+        expect = big.clone()
+        targets = [big[i // 2, 4:36, 4:36] if i % 2 == 0 else None for i in range(35)]
+        count, sse, mx, _ = b.decode_distortion_device(targets)
+        torch.cuda.synchronize()
+        assert count == 34
+        for i in good:
+            assert (sse[i], mx[i]) == want[i], i
+        assert sse[1] == [0, 0, 0] and mx[1] == [0, 0, 0]
+        for i in range(0, 35, 2):
+            expect[i // 2, 4:36, 4:36] = to_gpu(np.frombuffer(b.decode_plane(i, 0, 32, 32), dtype=np.uint8).reshape(32, 32))
+        assert torch.equal(big, expect)                         # the frames' bytes inside, the pattern around them
+        b.free()
+    finally:
+        gpu.set_limits(6000, 22)
+        o.delete()
+
+
 # ------------------------------------------------------------------ 6. repeats and partial outputs
 
 def test_a_second_call_gives_the_same_numbers_and_every_output_is_optional(gpu):
