@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = [
     "fiasco_amd_batch_stage_device", "fiasco_amd_batch_upload_device", "fiasco_amd_batch_input_planes",
     "fiasco_amd_batch_decode_device", "fiasco_amd_planes_to_pixels_device",
     "fiasco_amd_batch_decode_distortion_device", "fiasco_amd_planes_distortion_device",
+    "fiasco_amd_batch_decode_planes", "fiasco_amd_batch_smoothing_borders",
 ]
 
 # pixel layouts of a frame in device memory (include/libfiasco_amd_hip.h)
@@ -57,6 +58,12 @@ class DeviceFrame(ctypes.Structure):
     """struct fiasco_amd_device_frame (include/libfiasco_amd_hip.h)."""
     _fields_ = [("data", ctypes.c_void_p), ("pitch", ctypes.c_size_t), ("plane_stride", ctypes.c_size_t),
                 ("width", ctypes.c_uint), ("height", ctypes.c_uint), ("layout", ctypes.c_int)]
+
+
+class Border(ctypes.Structure):
+    """struct fiasco_amd_border (include/libfiasco_amd.h): one border smooth_image blends, 8 bytes."""
+    _fields_ = [("x", ctypes.c_uint16), ("y", ctypes.c_uint16), ("len", ctypes.c_uint16),
+                ("level", ctypes.c_uint8), ("pass_", ctypes.c_uint8)]
 
 
 class DeviceTarget(ctypes.Structure):
@@ -392,6 +399,36 @@ class Batch:
         if not f(self.handle, i, band, buf):
             raise FiascoError(self.lib.error_message())
         return buf.raw
+
+    def decode_planes(self, i):
+        """fiasco_amd_batch_decode_planes: the decoded planes of frame i before any smoothing, int16 [bands, h, w]
+        (12.4 fixed point)."""
+        import numpy
+        c = ctypes
+        f = self.lib.L.fiasco_amd_batch_decode_planes
+        f.argtypes = [c.c_void_p, c.c_uint, c.c_void_p]
+        f.restype = c.c_int
+        w, h, bands = self._geom[i]
+        out = numpy.empty((bands, h, w), dtype=numpy.int16)
+        if not f(self.handle, i, out.ctypes.data):
+            raise FiascoError(self.lib.error_message())
+        return out
+
+    def smoothing_borders(self, i):
+        """fiasco_amd_batch_smoothing_borders: the borders the reference's decoder smooths frame i along, as a list of
+        (x, y, len, level, pass) sorted by pass -- odd level: rows y - 1 and y, columns x .. x + len - 1; even level:
+        columns x - 1 and x, rows y .. y + len - 1.  The borders of one pass share no pixel."""
+        c = ctypes
+        f = self.lib.L.fiasco_amd_batch_smoothing_borders
+        f.argtypes = [c.c_void_p, c.c_uint, c.POINTER(Border), c.c_uint]
+        f.restype = c.c_int
+        n = f(self.handle, i, None, 0)
+        if not n:
+            raise FiascoError(self.lib.error_message())
+        arr = (Border * n)()
+        if f(self.handle, i, arr, n) != n:
+            raise FiascoError(self.lib.error_message())
+        return [(b.x, b.y, b.len, b.level, b.pass_) for b in arr]
 
     def decode_device(self, targets, stream=None):
         """fiasco_amd_batch_decode_device: the frames of the last finished pass, decoded on the device and written as

@@ -502,6 +502,95 @@ int fiasco_amd_batch_input_planes(const fiasco_amd_batch_t *b, unsigned i, int16
     return 1;
 }
 
+/* The decoded planes themselves, before any smoothing: 12.4 fixed point, all bands back to back -- the sibling of
+ * fiasco_amd_batch_input_planes() on the other side of the coder. */
+int fiasco_amd_batch_decode_planes(const fiasco_amd_batch_t *b, unsigned i, int16_t *out)
+{
+    const fa_image *orig;
+    fa_image *dec;
+    size_t npix;
+    int band;
+    if (!b || i >= b->n || !b->jobs[i].status || !b->jobs[i].wfa || !out) {
+        fa_set_error("fiasco_amd_batch_decode_planes: frame %u has no finished automaton", i);
+        return 0;
+    }
+    if (b->jobs[i].frame_type != FA_I_FRAME) {
+        fa_set_error("fiasco_amd_batch_decode_planes: intra frames only (a P/B frame needs its reference frames)");
+        return 0;
+    }
+    orig = b->jobs[i].image;
+    dec = decode_job(&b->jobs[i]);
+    if (!dec) return 0;
+    npix = (size_t) orig->width * orig->height;
+    for (band = 0; band < (orig->color ? 3 : 1); band++) memcpy(out + (size_t) band * npix, dec->pixels[band], npix * 2);
+    fa_image_free(dec);
+    return 1;
+}
+
+/* ---------------------------------------------------------------- smoothing along the partition borders */
+
+/* The borders smooth_image (codec/decoder.c:674-768) blends in a frame of width x height, in an order a parallel
+ * machine can follow.  The reference walks the states basis_states .. bound - 1 in index order and changes the Y plane
+ * in place; bound is the number of states for a gray frame and tree[root][0] for a colour frame, which leaves the Y
+ * band AND the Cb band in (chroma states carry band-relative coordinates, so the luminance plane is smoothed a second
+ * time along the Cb partition) and Cr out.  States are numbered children first, and two borders of one band share
+ * pixels only when one state lies below the other in the tree; borders of one level and band lie inside disjoint
+ * blocks.  So `Y band by ascending level, then Cb band by ascending level' gives the sequential result: one pass per
+ * (band, level) that has a border, borders of a pass in state order.
+ * A state's border lies between the halves of its block, where its label-1 child begins: odd levels are cut
+ * horizontally (rows y - 1 and y, `len' columns from x), even levels vertically (columns x - 1 and x, `len' rows from
+ * y); len is the block's side, clipped at the frame.  Returns the number of borders; out may be NULL (count only);
+ * more than cap: 0 + message. */
+unsigned fa_smoothing_borders(const fa_wfa *w, unsigned width, unsigned height, int color, fiasco_amd_border *out, unsigned cap)
+{
+    unsigned from[2], to[2], phases = 1, phase, n = 0, pass = 0;
+    from[0] = w->basis_states; to[0] = w->states;
+    if (color) {
+        const unsigned join = (unsigned) FA_TREE(w, w->root_state, 0);        /* Y and Cb meet here: the reference's bound */
+        to[0] = (unsigned) FA_TREE(w, join, 0) + 1;                           /* ... the root of Y included */
+        from[1] = to[0]; to[1] = join;
+        phases = 2;
+    }
+    for (phase = 0; phase < phases; phase++) {
+        unsigned level, maxl = 0, s;
+        for (s = from[phase]; s < to[phase]; s++) if (w->level_of_state[s] > maxl) maxl = w->level_of_state[s];
+        for (level = 0; level <= maxl; level++) {
+            const unsigned side = level & 1 ? 1u << (level >> 1) : 1u << ((level + 1) >> 1);   /* width_of_level : height_of_level */
+            unsigned found = 0;
+            for (s = from[phase]; s < to[phase]; s++) {
+                const unsigned x = w->x[s * 2 + 1], y = w->y[s * 2 + 1];
+                unsigned room;
+                if (w->level_of_state[s] != level || y >= height || x >= width) continue;
+                if (level & 1 ? !y : !x) continue;            /* no pixel before the first: no block is cut there */
+                room = level & 1 ? width - x : height - y;
+                if (out) {
+                    if (n >= cap) { fa_set_error("fiasco_amd_batch_smoothing_borders: more than %u borders", cap); return 0; }
+                    out[n].x = (uint16_t) x; out[n].y = (uint16_t) y; out[n].len = (uint16_t) (side < room ? side : room);
+                    out[n].level = (uint8_t) level; out[n].pass = (uint8_t) pass;
+                }
+                n++; found = 1;
+            }
+            pass += found;
+        }
+    }
+    return n;
+}
+
+int fiasco_amd_batch_smoothing_borders(const fiasco_amd_batch_t *b, unsigned i, fiasco_amd_border *out, unsigned cap)
+{
+    const fa_image *im;
+    if (!b || i >= b->n || !b->jobs[i].status || !b->jobs[i].wfa) {
+        fa_set_error("fiasco_amd_batch_smoothing_borders: frame %u has no finished automaton", i);
+        return 0;
+    }
+    if (b->jobs[i].frame_type != FA_I_FRAME) {
+        fa_set_error("fiasco_amd_batch_smoothing_borders: intra frames only");
+        return 0;
+    }
+    im = b->jobs[i].image;
+    return (int) fa_smoothing_borders(b->jobs[i].wfa, im->width, im->height, im->color, out, cap);
+}
+
 void fiasco_amd_batch_free(fiasco_amd_batch_t *b)
 {
     unsigned i;

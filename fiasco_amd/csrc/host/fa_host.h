@@ -184,6 +184,9 @@ typedef struct fa_dec_job {
     char            errmsg[160];
 } fa_dec_job;
 int  fa_core_decode_frames(unsigned n, fa_dec_job *jobs);    /* number of frames decoded */
+/* smoothing along the partition borders (smooth_image, codec/decoder.c:674-768; fa_coder.c): the borders of a frame
+ * in passes (fiasco_amd_batch_smoothing_borders) */
+unsigned fa_smoothing_borders(const fa_wfa *w, unsigned width, unsigned height, int color, fiasco_amd_border *out, unsigned cap);
 void fa_core_release_dev(void *dev, int dev_id);
 
 /* ---------------- stream info (reference codec/wfa.h:65-110 wfa_info_t) ----------- */

@@ -15,6 +15,7 @@
 #define LIBFIASCO_AMD_H 1
 
 #include <stddef.h>
+#include <stdint.h>
 #include <stdio.h>
 
 #ifdef __cplusplus
@@ -166,6 +167,26 @@ int  fiasco_amd_batch_decode_psnr_all(const fiasco_amd_batch_t *batch, double *p
 /* ... and the decoded frame itself: one band as width x height bytes, clip((pixel >> 4) + 128) -- for a gray frame
  * the payload of the PGM `dfiasco -s 0 -o` writes (lib/image.c:449-483). */
 int  fiasco_amd_batch_decode_plane(const fiasco_amd_batch_t *batch, unsigned i, unsigned band, unsigned char *out);
+/* ... and its planes as the decoder leaves them, before any smoothing: int16 in 12.4 fixed point, all bands back to
+ * back (width * height values each; gray: one band) -- the sibling of fiasco_amd_batch_input_planes()
+ * (libfiasco_amd_hip.h) for whoever goes on in fixed point.  Intra frames only.  1 ok / 0 + error message. */
+int  fiasco_amd_batch_decode_planes(const fiasco_amd_batch_t *batch, unsigned i, int16_t *out);
+
+/* Where the reference's decoder smooths a frame (smooth_image, codec/decoder.c:674-768; `dfiasco -s N', N > 0): along
+ * the borders between the two halves of every block of the partition.  A border of an odd level is horizontal: rows
+ * y - 1 and y, columns x .. x + len - 1; one of an even level is vertical: columns x - 1 and x, rows y .. y + len - 1.
+ * len is clipped at the frame; states that lie outside it have no border.  Only the Y plane is smoothed: for a gray
+ * frame along its partition, for a colour frame along the partition of Y and then once more along the partition of
+ * Cb (that is what the reference's loop bound does; Cr is not in it).
+ * The reference blends the pairs of pixels in place, state by state, and borders that cross share pixels, so the
+ * order matters.  The list is sorted by `pass': Y by ascending level, then Cb by ascending level, one pass per
+ * (band, level) that has a border.  The borders of one pass share no pixel and may be blended in any order or side by
+ * side; pass after pass that gives the reference's result.
+ * fiasco_amd_batch_smoothing_borders(): the borders of frame i of the last finished pass into out[0 .. cap); returns
+ * their number.  out == NULL asks for the number alone.  0 + error message: no such frame, no finished intra
+ * automaton, cap too small. */
+typedef struct fiasco_amd_border { uint16_t x, y, len; uint8_t level, pass; } fiasco_amd_border;      /* 8 bytes */
+int  fiasco_amd_batch_smoothing_borders(const fiasco_amd_batch_t *batch, unsigned i, fiasco_amd_border *out, unsigned cap);
 
 /* The model names of the reference's c_options_t (codec/options.h:36-39; registries codec/domain-pool.c:188-236
  * "adaptive", "constant", "basis", "uniform", "rle", "rle-no-chroma" and codec/coeff.c:97-131 "adaptive",
