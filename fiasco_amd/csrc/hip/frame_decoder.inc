@@ -343,7 +343,7 @@ extern "C" void fa_core_release_dev(void *dev, int dev_id)
 /* ------------------------------------------------------------------ a share of a call, flight by flight */
 
 /* One share of fa_core_decode_frames, on the device the calling thread is bound to (for_shares / bind_share,
- * core_hip.cpp): what its flights have in common.  The two optional consumers of a flight's planes:
+ * shares.inc): what its flights have in common.  The two optional consumers of a flight's planes:
  * out != NULL (fiasco_amd_batch_decode_device, output_convert.inc): the frames are written as 8-bit pixels into
  * out->target[job]; such a frame gets no host image and no copy to the host (jobs[].out stays NULL, out->done[job] says
  * that it was written).
@@ -655,8 +655,8 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine, con
     return S.good;
 }
 
-/* decode n frames: dealt to the shares by the rule of dec_shares / dec_share_of (core_hip.cpp), the shares decode side
- * by side, each on its own host thread (share 0 on the caller's; for_shares, core_hip.cpp).  Returns the number of
+/* decode n frames: dealt to the shares by the rule of dec_shares / dec_share_of (shares.inc), the shares decode side
+ * by side, each on its own host thread (share 0 on the caller's; for_shares, shares.inc).  Returns the number of
  * frames decoded; a failed job has out == NULL and a message. */
 static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const DsOut *ds)
 {

@@ -374,7 +374,7 @@ done:
 
 /* what fiasco_amd_batch_upload_device() keeps of one share, to put it back when a share fails */
 struct IcShareUndo {
-    std::vector<fiasco_amd_device_frame> frames;    /* the share's frames in the order of its jobs (several shares) */
+    const fiasco_amd_device_frame       *frames = nullptr;   /* the share's frames in the order of its jobs (Part::frames_of) */
     std::vector<const fa_image *>        image;     /* jobs[].image before */
     std::vector<const int16_t *>         ext_next;  /* slots[].ext_next before */
     bool up_pending = false;
@@ -414,16 +414,14 @@ extern "C" int fiasco_amd_batch_upload_device(fiasco_amd_batch_t *b, const fiasc
          * that has none refuses the upload and the batch is whole), then every share converts.  A device error after
          * that puts the slots and the images back as they were; the planes of an earlier upload that no submit had
          * taken over yet may be overwritten by then, and the error says so. */
-        const bool one = M->parts.size() == 1;
         std::vector<IcShareUndo> sh(M->parts.size());
         for (size_t k = 0; k < M->parts.size(); k++) {
             Staged *S = (Staged *) M->parts[k].staged;
             for (unsigned j = 0; j < S->n; j++) {
-                const unsigned i = one ? j : M->parts[k].idx[j];
                 sh[k].image.push_back(S->jobs[j].image);
-                S->jobs[j].image = nims[i];
-                if (!one) sh[k].frames.push_back(fr[i]);
+                S->jobs[j].image = nims[M->parts[k].job_index(j)];
             }
+            sh[k].frames = M->parts[k].frames_of(fr.data());
             for (size_t j = 0; j < S->slots.size(); j++) sh[k].ext_next.push_back(S->slots[j].ext_next);
             sh[k].up_pending = S->up_pending;
         }
@@ -431,7 +429,7 @@ extern "C" int fiasco_amd_batch_upload_device(fiasco_amd_batch_t *b, const fiasc
         auto all_shares = [&](bool prepare_only) {
             for_each_share(M, [&](size_t k) {
                 Staged *S = (Staged *) M->parts[k].staged;
-                sh[k].good = ic_convert(S, one ? fr.data() : sh[k].frames.data(), S->up_parity ^ 1, ready, true, prepare_only);
+                sh[k].good = ic_convert(S, sh[k].frames, S->up_parity ^ 1, ready, true, prepare_only);
                 if (!sh[k].good) snprintf(sh[k].why, sizeof sh[k].why, "%s", fiasco_get_error_message());
             });
             bool all = true;

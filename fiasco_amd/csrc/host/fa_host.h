@@ -5,7 +5,7 @@
  *  basis automaton, frame driver and the .fco stream writer.  Everything from
  *  subdivide() downwards (partition search, matching pursuit, inner-product tables,
  *  rate models) lives behind fa_core_encode_frames(), which is implemented
- *    - by the HIP device coder (csrc/hip/core_hip.hip) in the product library, and
+ *    - by the HIP device coder (csrc/hip/core_hip.cpp) in the product library, and
  *    - by the CPU restatement (oracle/oracle_core.c) in the test-only oracle library.
  */
 #ifndef FA_HOST_H
@@ -275,7 +275,7 @@ typedef struct fa_job {
                                      frames between them stay on ONE device while other GOPs end */
 } fa_job;
 
-/* Which of `shares' device shares (core_hip.cpp: one per device of the process) takes a job: a pure function of the
+/* Which of `shares' device shares (csrc/hip/shares.inc: one per device of the process) takes a job: a pure function of the
  * job's key when it has one, of its index in the call otherwise (round robin).  The search
  * (fa_core_stage) and the decoder (fa_core_decode_frames) both deal with it, so a keyed job is decoded where its
  * successor is searched. */

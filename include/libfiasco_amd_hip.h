@@ -98,7 +98,7 @@ int fiasco_amd_rccl_gather(void *comm, void *stream, int rank, int world, int ro
  * An id may be listed twice (two shares on one GPU).  Replacement of staged inputs (fiasco_amd_batch_upload) works
  * with several devices too: one pinned host buffer, every share copies the planes of ITS frames.  Threading: the
  * batch entries of ONE process may be called from several host threads, but calls that spread over more than one
- * device share run one after the other (the shares' worker threads belong to the process, core_hip.cpp
+ * device share run one after the other (the shares' worker threads belong to the process, shares.inc
  * for_each_share).  All return 1 on success, 0 + error message. */
 /* workgroups per frame the launcher gives the table passes of `frames` big frames (prediction, P/B frames, -z 1/2)
  * on a chip of `cus` CUs: 1, 2, 4 or 8 (csrc/hip/frame_coder.h FcCoop); pure function */

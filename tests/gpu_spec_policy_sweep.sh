@@ -1,6 +1,6 @@
 #!/bin/bash
 # developer helper (GPU box): frames/s of small 1080p / 4K launches for every number of workgroups per frame the chip
-# can hold -- the table spec_policy() (core_hip.cpp) is tuned by.  usage: tests/gpu_spec_policy_sweep.sh [W H] n ...
+# can hold -- the table spec_policy() (enc_policy.inc) is tuned by.  usage: tests/gpu_spec_policy_sweep.sh [W H] n ...
 cd "$(dirname "$0")/.."
 W=${SWEEP_W:-1920}; H=${SWEEP_H:-1080}
 for n in "$@"; do
