@@ -48,6 +48,8 @@ EXPORTED_SYMBOLS = [
     "fiasco_amd_batch_decode_device", "fiasco_amd_planes_to_pixels_device",
     "fiasco_amd_batch_decode_distortion_device", "fiasco_amd_planes_distortion_device",
     "fiasco_amd_batch_decode_planes", "fiasco_amd_batch_smoothing_borders",
+    "fiasco_amd_magnified_size", "fiasco_amd_batch_decode_device_magnified", "fiasco_amd_batch_decode_planes_magnified",
+    "fiasco_amd_batch_decode_device_thumbnails",
 ]
 
 # pixel layouts of a frame in device memory (include/libfiasco_amd_hip.h)
@@ -400,17 +402,23 @@ class Batch:
             raise FiascoError(self.lib.error_message())
         return buf.raw
 
-    def decode_planes(self, i):
+    def decode_planes(self, i, magnify=0):
         """fiasco_amd_batch_decode_planes: the decoded planes of frame i before any smoothing, int16 [bands, h, w]
-        (12.4 fixed point)."""
+        (12.4 fixed point).  magnify != 0: fiasco_amd_batch_decode_planes_magnified, the frame at 2^magnify times its
+        side length as `dfiasco -m` shows it; h, w are those of magnified_size()."""
         import numpy
         c = ctypes
-        f = self.lib.L.fiasco_amd_batch_decode_planes
-        f.argtypes = [c.c_void_p, c.c_uint, c.c_void_p]
-        f.restype = c.c_int
         w, h, bands = self._geom[i]
+        if magnify:
+            w, h = magnified_size(self.lib, w, h, magnify)
+            f = self.lib.L.fiasco_amd_batch_decode_planes_magnified
+            f.argtypes = [c.c_void_p, c.c_uint, c.c_int, c.c_void_p]
+        else:
+            f = self.lib.L.fiasco_amd_batch_decode_planes
+            f.argtypes = [c.c_void_p, c.c_uint, c.c_void_p]
+        f.restype = c.c_int
         out = numpy.empty((bands, h, w), dtype=numpy.int16)
-        if not f(self.handle, i, out.ctypes.data):
+        if not (f(self.handle, i, magnify, out.ctypes.data) if magnify else f(self.handle, i, out.ctypes.data)):
             raise FiascoError(self.lib.error_message())
         return out
 
@@ -430,23 +438,59 @@ class Batch:
             raise FiascoError(self.lib.error_message())
         return [(b.x, b.y, b.len, b.level, b.pass_) for b in arr]
 
-    def decode_device(self, targets, stream=None):
+    def decode_device(self, targets, stream=None, magnify=0):
         """fiasco_amd_batch_decode_device: the frames of the last finished pass, decoded on the device and written as
         8-bit pixels into `targets` -- the bytes of the PGM / PPM `dfiasco -s 0 -o` writes.  A target is a torch uint8
         tensor on the GPU or any writable object with __cuda_array_interface__, of the frame's size: H x W for a gray
         frame, H x W x 3 or 3 x H x W for a colour frame (pitch and plane stride from the strides, as from_device);
         None skips the frame.  `stream`: the hipStream_t (integer) the targets were last used on; None = torch's
         current stream for torch tensors, else the default stream.  That stream waits for the conversion: what is
-        queued on it afterwards sees the pixels, no host synchronisation needed.  Returns the number of frames written."""
+        queued on it afterwards sees the pixels, no host synchronisation needed.  Returns the number of frames written.
+        magnify != 0: fiasco_amd_batch_decode_device_magnified, the bytes of `dfiasco -s 0 -m magnify -o`; every target
+        has the size magnified_size() gives for its frame."""
         c = ctypes
         targets = list(targets)
         if len(targets) != self.n:
             raise FiascoError("decode_device: %d targets for a batch of %d" % (len(targets), self.n))
         arr = _device_targets(targets)
-        f = self.lib.L.fiasco_amd_batch_decode_device
-        f.argtypes = [c.c_void_p, c.POINTER(DeviceTarget), c.c_void_p]
+        on = _stream_of([t for t in targets if t is not None], stream)
+        if magnify:
+            f = self.lib.L.fiasco_amd_batch_decode_device_magnified
+            f.argtypes = [c.c_void_p, c.c_int, c.POINTER(DeviceTarget), c.c_void_p]
+            f.restype = c.c_int
+            good = f(self.handle, magnify, arr, on)
+        else:
+            f = self.lib.L.fiasco_amd_batch_decode_device
+            f.argtypes = [c.c_void_p, c.POINTER(DeviceTarget), c.c_void_p]
+            f.restype = c.c_int
+            good = f(self.handle, arr, on)
+        if not good:
+            raise FiascoError(self.lib.error_message())
+        return good
+
+    def decode_thumbnails(self, targets, reduce, thumbs, stream=None):
+        """fiasco_amd_batch_decode_device_thumbnails: ONE decode of the frames of the last finished pass that writes
+        every frame into `targets` as decode_device does (None, or a list in which None skips the full-size frame) and
+        the same frame at 1 / 2^reduce of its side length (reduce >= 1) into `thumbs` -- the bytes
+        decode_device(magnify=-reduce) gives; a thumb has the size magnified_size(lib, w, h, -reduce), None skips it.
+        `stream` as decode_device.  Returns the number of frames decoded."""
+        c = ctypes
+        thumbs = list(thumbs)
+        if reduce < 1:
+            raise FiascoError("decode_thumbnails: reduce = %d (1 halves the side length)" % reduce)
+        if len(thumbs) != self.n:
+            raise FiascoError("decode_thumbnails: %d thumbs for a batch of %d" % (len(thumbs), self.n))
+        arr = None
+        if targets is not None:
+            targets = list(targets)
+            if len(targets) != self.n:
+                raise FiascoError("decode_thumbnails: %d targets for a batch of %d" % (len(targets), self.n))
+            arr = _device_targets(targets)
+        tarr = _device_targets(thumbs)
+        f = self.lib.L.fiasco_amd_batch_decode_device_thumbnails
+        f.argtypes = [c.c_void_p, c.POINTER(DeviceTarget), c.c_uint, c.POINTER(DeviceTarget), c.c_void_p]
         f.restype = c.c_int
-        good = f(self.handle, arr, _stream_of([t for t in targets if t is not None], stream))
+        good = f(self.handle, arr, reduce, tarr, _stream_of([t for t in (targets or []) + thumbs if t is not None], stream))
         if not good:
             raise FiascoError(self.lib.error_message())
         return good
@@ -572,6 +616,20 @@ def _device_targets(targets):
         if t is not None and _describe("target", i, t, arr[i]):
             raise FiascoError("target %d is read-only" % i)
     return arr
+
+
+def magnified_size(lib, width, height, magnify):
+    """fiasco_amd_magnified_size: (width, height) at which `dfiasco -m magnify` shows a frame of width x height --
+    << magnify, or >> -magnify rounded up to even.  FiascoError with the reference's limit ("Maximum value is N." /
+    "Minimum value is -N.") where the reference refuses.  A pure function; no device needed."""
+    c = ctypes
+    f = lib.L.fiasco_amd_magnified_size
+    f.argtypes = [c.c_uint, c.c_uint, c.c_int, c.POINTER(c.c_uint), c.POINTER(c.c_uint)]
+    f.restype = c.c_int
+    w, h = c.c_uint(), c.c_uint()
+    if not f(width, height, magnify, w, h):
+        raise FiascoError(lib.error_message())
+    return w.value, h.value
 
 
 def planes_to_pixels_device(lib, planes, target, stream=None):

@@ -26,6 +26,12 @@
  *  those of the states the frame shows and go straight into the planes (dec_assemble_kernel).  The work is
  *  HBM-bound integer adds: one 2-byte read per (pixel, term), coalesced along the pixels of an image.
  *
+ *  Magnification (dfiasco -m M, enlarge_image codec/decoder.c:776-840: 2 M added to the level of every state, the
+ *  coordinates shifted by M): the recursion above never asks for the level of a state, so the frame at magnification M
+ *  is the images of the SAME top states at level maxl + 2 M, placed at their coordinates << M (>> -M), cropped to the
+ *  size of fiasco_amd_magnified_size().  For M = -k the level launches of a full-size decode have written those images on
+ *  their way up: dec_thumb_kernel gathers them into reduced planes and one decode gives the frame and its thumbnail.
+ *
  *  The decoded planes stay on the device (fa_image.dev): the next P/B frame of the sequence takes its
  *  reference frames with a device-to-device copy (upload_reference); the host copy serves every other caller.
  */
@@ -105,6 +111,32 @@ __global__ void __launch_bounds__(256) dec_assemble_kernel(const DecDesc *__rest
     d.planes[(size_t) t.band * W * H + (size_t) y * W + x] = l ? dec_pixel(d.nodes, d.img, S, (unsigned) t.state, l, p) : d.img[t.state];
 }
 
+/* the thumbnails of a flight side by side: blockIdx.y = thumbnail.  img, tops: those of the frame's DecDesc; l: the level
+ * shown, the frame's largest less twice the reduction; W, H: the reduced size */
+struct DecThumb {
+    const int16_t *img;
+    const DecTop  *tops;
+    int16_t       *planes;
+    unsigned       S, l, ntops, W, H, shift;
+};
+
+/* the frame at 1 / 2^shift of its side length: the level-l images of the states the frame shows, which the level
+ * launches have written (level 0: the pixel table), copied to their place >> shift and cropped.  A copy: one 16-bit
+ * load and one 16-bit store per pixel, neighbouring lanes read neighbouring pixels of an image and write neighbouring
+ * pixels of a row of its block */
+__global__ void __launch_bounds__(256) dec_thumb_kernel(const DecThumb *__restrict__ thumbs)
+{
+    const DecThumb d = thumbs[blockIdx.y];
+    const unsigned l = d.l, W = d.W, H = d.H;
+    const size_t idx = (size_t) blockIdx.x * 256 + threadIdx.x;
+    if (idx >= ((size_t) d.ntops << l)) return;
+    const DecTop t = d.tops[idx >> l];
+    const unsigned p = (unsigned) (idx & ((1u << l) - 1)), wl = l >> 1;
+    const unsigned y = ((unsigned) t.y0 >> d.shift) + (p >> wl), x = ((unsigned) t.x0 >> d.shift) + (p & ((1u << wl) - 1));
+    if (x >= W || y >= H) return;                                  /* the crop of decode_image */
+    d.planes[(size_t) t.band * W * H + (size_t) y * W + x] = d.img[(size_t) d.S * ((1u << l) - 1) + ((size_t) t.state << l) + p];
+}
+
 /* 16-bit add with wrap-around into a plane other blocks may be adding to (a block that leaves the frame on
  * the right continues in the next row, like the linear addressing of restore_mc) */
 __device__ __forceinline__ void dec_add16(int16_t *plane, size_t i, unsigned add)
@@ -165,7 +197,11 @@ struct DecFrame {                     /* one frame in flight */
     std::vector<int16_t> px0;
     /* dec_prepare -> dec_run */
     size_t nodes_b = 0, tops_b = 0, mcs_b = 0, img_b = 0, scratch_b = 0;
-    unsigned S = 0, maxl = 0, mc_maxl = 0, ntops = 0, nmcs = 0;
+    unsigned S = 0, maxl = 0, mc_maxl = 0, ntops = 0, nmcs = 0;           /* maxl: the level shown (magnification included) */
+    unsigned W = 0, H = 0;            /* the size shown: the coded one, or fiasco_amd_magnified_size() */
+    int16_t *thumb = nullptr;         /* a thumbnail beside the frame (dec_flight_thumbs): its reduced planes in the arena */
+    size_t thumb_off = 0, thumb_bytes = 0;
+    unsigned tw = 0, th = 0;
     bool own_planes = false;          /* planes is an allocation of its own (kept on the device) */
     unsigned long long bytes = 0;     /* algorithmic: 2 bytes per pixel written and per (pixel, term) read */
     size_t scratch_off = 0;           /* dec_flight_prepare: its scratch_b bytes of the flight's arena */
@@ -197,8 +233,14 @@ static unsigned dec_terms(const DecNode &n, const DecEdge *ext)
 static bool dec_prepare(fa_dec_job *j, DecFrame &D)
 {
     const fa_wfa *w = j->wfa;
-    const unsigned S = w->states, bands = j->color ? 3 : 1, W = j->width, H = j->height;
-    unsigned root[3] = { 0, 0, 0 }, maxl = 0;
+    const unsigned S = w->states, bands = j->color ? 3 : 1;
+    unsigned root[3] = { 0, 0, 0 }, maxl = 0, W = j->width, H = j->height;
+    const int mag = j->magnify;
+    if (mag && j->frame_type != FA_I_FRAME) { dec_fail(j, "device decoder: magnification of intra frames only (the vectors of a P/B frame are not scaled)"); return false; }
+    if (mag && !fiasco_amd_magnified_size(j->width, j->height, mag, &W, &H)) {
+        snprintf(j->errmsg, sizeof j->errmsg, "device decoder: magnification %d is out of range for a frame of %u x %u pixels", mag, j->width, j->height);
+        j->out = nullptr; return false;
+    }
     if (j->color) {
         const unsigned r0 = (unsigned) FA_TREE(w, w->root_state, 0), r1 = (unsigned) FA_TREE(w, w->root_state, 1);
         root[FA_Y] = (unsigned) FA_TREE(w, r0, 0); root[FA_CB] = (unsigned) FA_TREE(w, r0, 1); root[FA_CR] = (unsigned) FA_TREE(w, r1, 0);
@@ -207,6 +249,11 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
         if (FA_INTO(w, s, 0, 0) != FA_NO_EDGE || FA_INTO(w, s, 1, 0) != FA_NO_EDGE)
             if (w->level_of_state[s] > maxl) maxl = w->level_of_state[s];
     if (maxl > 24) { dec_fail(j, "device decoder: level of the linear combinations out of range"); return false; }
+    /* the level shown (the header): the states of level `maxl' at level maxl + 2 mag.  Blocks smaller than the reduction
+     * -- the reference clamps their level at 0 and several land on one pixel -- are refused, not reproduced */
+    if (mag < 0 && maxl < 2u * (unsigned) -mag) { dec_fail(j, "device decoder: the blocks of the frame are smaller than the reduction (level of the linear combinations below twice the reduction)"); return false; }
+    const unsigned shown = (unsigned) ((int) maxl + 2 * mag);
+    if (shown > 24) { dec_fail(j, "device decoder: level of the magnified linear combinations out of range (above 24)"); return false; }
     /* host side of the arithmetic: nodes with integer weights, the lists of blocks */
     std::vector<DecTop> tops;
     std::vector<DecMc> mcs;
@@ -216,6 +263,7 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
         if (w->level_of_state[s] == maxl) {
             DecTop t;
             t.state = (int) s; t.x0 = w->x[s * 2]; t.y0 = w->y[s * 2];
+            if (mag > 0) { t.x0 <<= mag; t.y0 <<= mag; } else if (mag < 0) { t.x0 >>= -mag; t.y0 >>= -mag; }
             t.band = !j->color || s <= root[FA_Y] ? 0 : s > root[FA_CB] ? FA_CR : FA_CB;
             tops.push_back(t);
         }
@@ -242,7 +290,7 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
     size_t next = 0;
     for (size_t r = 0; r < (size_t) S * 2; r++) { const unsigned e = dec_edges(w, r); if (e > 6) next += e; }
     const size_t nodes_b = align_up((size_t) S * 2 * sizeof(DecNode) + next * sizeof(DecEdge), 256), tops_b = align_up((tops.size() + 1) * sizeof(DecTop), 256),
-                 mcs_b = align_up((mcs.size() + 1) * sizeof(DecMc), 256), img_b = align_up(((size_t) S << maxl) * 2 + 256, 256);      /* levels 0 .. maxl - 1 of every state */
+                 mcs_b = align_up((mcs.size() + 1) * sizeof(DecMc), 256), img_b = align_up(((size_t) S << shown) * 2 + 256, 256);      /* levels 0 .. shown - 1 of every state */
     D.host.assign(nodes_b + tops_b + mcs_b, 0);
     DecNode *nodes = (DecNode *) D.host.data();
     DecEdge *ext = (DecEdge *) (nodes + (size_t) S * 2);
@@ -270,7 +318,7 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
     const size_t npix = (size_t) W * H;
     D.plane_bytes = align_up(npix * bands * 2, 256);
     D.nodes_b = nodes_b; D.tops_b = tops_b; D.mcs_b = mcs_b; D.img_b = img_b;
-    D.S = S; D.maxl = maxl; D.mc_maxl = mc_maxl; D.ntops = (unsigned) tops.size(); D.nmcs = (unsigned) mcs.size();
+    D.S = S; D.maxl = shown; D.W = W; D.H = H; D.mc_maxl = mc_maxl; D.ntops = (unsigned) tops.size(); D.nmcs = (unsigned) mcs.size();
     D.own_planes = j->keep_dev != 0;
     D.scratch_b = nodes_b + tops_b + mcs_b + img_b + (D.own_planes ? 0 : D.plane_bytes);
     /* level l < maxl: S * 2^l pixels written, terms * 2^(l-1) read; the top level: the terms of the states shown,
@@ -279,9 +327,9 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
     for (size_t k = 0; k < (size_t) S * 2; k++) terms += dec_terms(nodes[k], ext);
     for (size_t k = 0; k < tops.size(); k++)
         for (unsigned l = 0; l < 2; l++) top_terms += dec_terms(nodes[(size_t) tops[k].state * 2 + l], ext);
-    const unsigned long long lower = maxl ? (((unsigned long long) S << maxl) - 2ull * S) : 0ull;
-    const unsigned long long lower_reads = maxl ? terms * ((1ull << (maxl - 1)) - 1) : 0ull;
-    D.bytes = 2ull * (lower + lower_reads + (maxl ? top_terms << (maxl - 1) : 0ull)) + 2ull * npix * bands;
+    const unsigned long long lower = shown ? (((unsigned long long) S << shown) - 2ull * S) : 0ull;
+    const unsigned long long lower_reads = shown ? terms * ((1ull << (shown - 1)) - 1) : 0ull;
+    D.bytes = 2ull * (lower + lower_reads + (shown ? top_terms << (shown - 1) : 0ull)) + 2ull * npix * bands;
     return true;
 }
 
@@ -346,7 +394,8 @@ extern "C" void fa_core_release_dev(void *dev, int dev_id)
  * shares.inc): what its flights have in common.  The two optional consumers of a flight's planes:
  * out != NULL (fiasco_amd_batch_decode_device, output_convert.inc): the frames are written as 8-bit pixels into
  * out->target[job]; such a frame gets no host image and no copy to the host (jobs[].out stays NULL, out->done[job] says
- * that it was written).
+ * that it was written).  out->thumb != NULL (fiasco_amd_batch_decode_device_thumbnails): frame `job' is written a second
+ * time, at 1 / 2^out->reduce of its side length, into out->thumb[job]; out->thumb_done[job] says so.
  * ds != NULL (fiasco_amd_batch_decode_distortion_device, distortion.inc): the frames are compared with their originals
  * before the pixels are written, if they are (a frame whose target has no data is measured only).  Such a frame gets
  * no host image either; ds->done[job] says that it was measured. */
@@ -370,9 +419,12 @@ struct DecFlight {
     std::vector<size_t>   alive;                /* the frames nothing has failed yet, in order */
     std::vector<DecDesc>  descs;                /* one per frame alive after the uploads: blockIdx.y of the level launches */
     std::vector<OcFrame>  octab; std::vector<DsPlane> dstab;    /* the frames written; the planes measured */
+    std::vector<DecThumb> thtab; std::vector<OcFrame> thoctab;  /* the thumbnails gathered; written */
     union { unsigned long long sums[DS_SLOTS]; char bytes[DS_RES_BYTES]; } dsres;      /* sums, then maxima: 8-byte aligned */
     /* the arena: the scratch of every frame (DecFrame::scratch_off), then */
     size_t desc_off = 0, oc_off = 0;            /* the tables of DecDesc and OcFrame */
+    size_t th_off = 0, thoc_off = 0;            /* thumbnails: the tables of DecThumb and OcFrame, */
+    size_t thumb_first = 0, thumb_all = 0;      /* ... and the reduced planes of all frames, back to back: zeroed with one call */
     size_t ds_off = 0, res_off = 0, orig_off = 0;       /* measuring: the table of DsPlane, the result array, the originals that come from the host */
     size_t need = 0;                            /* all of it */
 
@@ -397,16 +449,39 @@ static void dec_account(unsigned long long us, unsigned frames, unsigned long lo
     pthread_mutex_unlock(&g_dec_stats_lock);
 }
 
+/* a frame that gets a thumbnail beside it: the level shown is the frame's less twice the reduction, which the level
+ * launches write only if it exists; the reduced planes are sized by the target (checked by the entry point) */
+static bool dec_thumb_prepare(DecShare &S, unsigned job, DecFrame &D)
+{
+    const fiasco_amd_device_frame &t = S.out->thumb[job];
+    if (!t.data) return true;
+    if (D.maxl < 2 * S.out->reduce) {
+        dec_fail(&S.jobs[job], "device decoder: the blocks of the frame are smaller than the reduction (level of the linear combinations below twice the reduction)");
+        return false;
+    }
+    D.tw = t.width; D.th = t.height;
+    D.thumb_bytes = align_up((size_t) D.tw * D.th * (S.jobs[job].color ? 3 : 1) * 2, 256);
+    return true;
+}
+
 /* host side of the n frames `idx': their automata as integers, and where everything lies in the arena.  The tables
  * are sized for a full flight whatever n is */
 static void dec_flight_prepare(DecShare &S, DecFlight &F, const unsigned *idx, size_t n)
 {
     F.job.assign(idx, idx + n);
     F.fr.resize(n);
+    const bool thumbs = S.out && S.out->thumb;
     for (size_t k = 0; k < n; k++)
-        if (dec_prepare(&S.jobs[F.job[k]], F.fr[k])) { F.alive.push_back(k); F.fr[k].scratch_off = F.take(F.fr[k].scratch_b); }
+        if (dec_prepare(&S.jobs[F.job[k]], F.fr[k]) && (!thumbs || dec_thumb_prepare(S, F.job[k], F.fr[k]))) {
+            F.alive.push_back(k); F.fr[k].scratch_off = F.take(F.fr[k].scratch_b);
+        }
     F.desc_off = F.take(DEC_FLIGHT * sizeof(DecDesc));
     F.oc_off = F.take(S.out ? DEC_FLIGHT * sizeof(OcFrame) : 0);
+    F.th_off = F.take(thumbs ? DEC_FLIGHT * sizeof(DecThumb) : 0);
+    F.thoc_off = F.take(thumbs ? DEC_FLIGHT * sizeof(OcFrame) : 0);
+    F.thumb_first = F.need;
+    if (thumbs) for (size_t k : F.alive) if (F.fr[k].thumb_bytes) F.fr[k].thumb_off = F.take(F.fr[k].thumb_bytes);
+    F.thumb_all = F.need - F.thumb_first;
     F.ds_off = F.take(S.ds ? DS_SLOTS * sizeof(DsPlane) : 0);
     F.res_off = F.take(S.ds ? DS_RES_BYTES : 0);
     F.orig_off = F.need;
@@ -442,7 +517,7 @@ static void dec_flight_upload(DecShare &S, DecFlight &F)
         DecDesc d;
         d.nodes = (const DecNode *) D.base; d.img = (int16_t *) (D.base + D.nodes_b + D.tops_b + D.mcs_b);
         d.tops = (const DecTop *) (D.base + D.nodes_b); d.planes = D.planes;
-        d.S = D.S; d.maxl = D.maxl; d.ntops = D.ntops; d.W = j->width; d.H = j->height;
+        d.S = D.S; d.maxl = D.maxl; d.ntops = D.ntops; d.W = D.W; d.H = D.H;
         F.descs.push_back(d);
         run.push_back(k);
     }
@@ -479,6 +554,31 @@ static void dec_flight_mc(DecShare &S, DecFlight &F)
     F.alive.swap(run);
 }
 
+/* the thumbnails of the flight, behind its level launches: the reduced planes zeroed, ONE launch of dec_thumb_kernel
+ * (blockIdx.y = thumbnail) gathers the images of the level shown */
+static void dec_flight_thumbs(DecShare &S, DecFlight &F)
+{
+    size_t nmax = 0;
+    for (size_t k : F.alive) {
+        DecFrame &D = F.fr[k];
+        if (!D.thumb_bytes) continue;
+        D.thumb = (int16_t *) (S.arena + D.thumb_off);
+        DecThumb t;
+        t.img = (const int16_t *) (D.base + D.nodes_b + D.tops_b + D.mcs_b); t.tops = (const DecTop *) (D.base + D.nodes_b); t.planes = D.thumb;
+        t.S = D.S; t.l = D.maxl - 2 * S.out->reduce; t.ntops = D.ntops; t.W = D.tw; t.H = D.th; t.shift = S.out->reduce;
+        F.thtab.push_back(t);
+        if (((size_t) t.ntops << t.l) > nmax) nmax = (size_t) t.ntops << t.l;
+    }
+    if (F.thtab.empty()) return;
+    bool ok = hipMemsetAsync(S.arena + F.thumb_first, 0, F.thumb_all, S.stream) == hipSuccess
+              && hipMemcpyAsync(S.arena + F.th_off, F.thtab.data(), F.thtab.size() * sizeof(DecThumb), hipMemcpyHostToDevice, S.stream) == hipSuccess;
+    if (ok && nmax) {
+        dec_thumb_kernel<<<dim3((unsigned) ((nmax + 255) / 256), (unsigned) F.thtab.size()), dim3(256), 0, S.stream>>>((const DecThumb *) (S.arena + F.th_off));
+        ok = hipGetLastError() == hipSuccess;
+    }
+    if (!ok) dec_flight_fail(S, F, "device decoder: HIP error");
+}
+
 /* the frames of the flight against their originals -- ds->orig[job] in place, else the host planes of ds->image[job],
  * copied into the arena --: the result array is zeroed and ONE launch of ds_distortion_kernel fills it.  The frames
  * alive now get the slots; from here on the flight lives or fails as a whole, so a slot stays its frame's */
@@ -511,20 +611,28 @@ static void dec_flight_measure(DecShare &S, DecFlight &F)
 }
 
 /* the frames of the flight that have a target into the caller's buffers, once the caller's stream has let go of them:
- * ONE launch of oc_convert_kernel */
+ * ONE launch of oc_convert_kernel; one more for the thumbnails, if there are any */
 static void dec_flight_write(DecShare &S, DecFlight &F)
 {
-    unsigned long long total = 0;
+    unsigned long long total = 0, thtotal = 0;
     for (size_t k : F.alive) {
-        if (!S.out->target[F.job[k]].data) continue;            /* measured only */
+        if (F.fr[k].thumb) {
+            F.thoctab.emplace_back();
+            oc_describe(F.thoctab.back(), F.fr[k].thumb, S.out->thumb[F.job[k]], thtotal);
+        }
+        if (!S.out->target[F.job[k]].data) continue;            /* measured only, or the thumbnail only */
         F.octab.emplace_back();
         oc_describe(F.octab.back(), F.fr[k].planes, S.out->target[F.job[k]], total);
     }
-    if (!F.octab.empty()
-        && (hipStreamWaitEvent(S.stream, S.out->ready, 0) != hipSuccess
-            || hipMemcpyAsync(S.arena + F.oc_off, F.octab.data(), F.octab.size() * sizeof(OcFrame), hipMemcpyHostToDevice, S.stream) != hipSuccess
-            || !oc_launch((const OcFrame *) (S.arena + F.oc_off), (unsigned) F.octab.size(), total, oc_cus(), S.stream)))
-        dec_flight_fail(S, F, "device decoder: HIP error");
+    if (F.octab.empty() && F.thoctab.empty()) return;
+    bool ok = hipStreamWaitEvent(S.stream, S.out->ready, 0) == hipSuccess;
+    if (ok && !F.octab.empty())
+        ok = hipMemcpyAsync(S.arena + F.oc_off, F.octab.data(), F.octab.size() * sizeof(OcFrame), hipMemcpyHostToDevice, S.stream) == hipSuccess
+             && oc_launch((const OcFrame *) (S.arena + F.oc_off), (unsigned) F.octab.size(), total, oc_cus(), S.stream);
+    if (ok && !F.thoctab.empty())
+        ok = hipMemcpyAsync(S.arena + F.thoc_off, F.thoctab.data(), F.thoctab.size() * sizeof(OcFrame), hipMemcpyHostToDevice, S.stream) == hipSuccess
+             && oc_launch((const OcFrame *) (S.arena + F.thoc_off), (unsigned) F.thoctab.size(), thtotal, oc_cus(), S.stream);
+    if (!ok) dec_flight_fail(S, F, "device decoder: HIP error");
 }
 
 /* the end of the flight's device work; measuring: 12 bytes per band come back */
@@ -539,8 +647,8 @@ static void dec_flight_wait(DecShare &S, DecFlight &F)
 /* a frame nobody consumed on the device: its planes as a host image, which keeps the device planes of a keep_dev frame */
 static bool dec_download(DecShare &S, fa_dec_job *j, DecFrame &D)
 {
-    fa_image *im = fa_image_alloc(j->width, j->height, j->color);
-    const size_t npix = (size_t) j->width * j->height;
+    fa_image *im = fa_image_alloc(D.W, D.H, j->color);
+    const size_t npix = (size_t) D.W * D.H;
     bool ok = im != nullptr;
     for (int b = 0; ok && b < (j->color ? 3 : 1); b++)
         ok = hipMemcpy(im->pixels[b], D.planes + (size_t) b * npix, npix * 2, hipMemcpyDeviceToHost) == hipSuccess;
@@ -564,9 +672,11 @@ static void dec_flight_results(DecShare &S, DecFlight &F)
         fa_dec_job *j = &S.jobs[i];
         DecFrame &D = F.fr[k];
         const unsigned bands = j->color ? 3 : 1;
-        const unsigned long long vals = (unsigned long long) j->width * j->height * bands;
+        const unsigned long long vals = (unsigned long long) D.W * D.H * bands;
         const bool written = S.out && S.out->target[i].data;
         if (written) S.out->done[i] = 1;
+        const unsigned long long tvals = D.thumb ? (unsigned long long) D.tw * D.th * bands : 0ull;     /* gathered: 2 + 2 bytes; written: 2 + 1 */
+        if (D.thumb) S.out->thumb_done[i] = 1;
         if (S.ds) {
             for (unsigned b = 0; b < bands; b++) {
                 if (S.ds->sse) S.ds->sse[(size_t) i * 3 + b] = F.dsres.sums[D.slot * 3 + b];
@@ -576,7 +686,7 @@ static void dec_flight_results(DecShare &S, DecFlight &F)
         }
         if (!S.out && !S.ds && !dec_download(S, j, D)) continue;
         frames++;
-        bytes += D.bytes + (S.ds ? 4 * vals : 0) + (written ? 3 * vals : 0);
+        bytes += D.bytes + (S.ds ? 4 * vals : 0) + (written ? 3 * vals : 0) + 7 * tvals;
     }
     dec_account((unsigned long long) (ms * 1000.0f), frames, bytes);
     S.good += (int) frames;
@@ -640,6 +750,7 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine, con
         dec_flight_upload(S, F);
         dec_flight_levels(S, F);
         dec_flight_mc(S, F);
+        if (out && out->thumb) dec_flight_thumbs(S, F);
         if (ds) dec_flight_measure(S, F);
         if (out) dec_flight_write(S, F);
         dec_flight_wait(S, F);

@@ -151,6 +151,10 @@ struct OcOut {
     unsigned char *done;                        /* [n] */
     hipEvent_t     ready;                       /* what the caller's stream held at the call */
     hipStream_t    caller;                      /* made to wait for the conversions */
+    /* thumbnails beside the frames (fiasco_amd_batch_decode_device_thumbnails): thumb == NULL: none */
+    const fiasco_amd_device_frame *thumb = nullptr;     /* [n] by job index, of the size at magnification -reduce; data == NULL: none */
+    unsigned char *thumb_done = nullptr;                /* [n] */
+    unsigned       reduce = 0;
 };
 
 static void oc_describe(OcFrame &d, const int16_t *planes, const fiasco_amd_device_frame &t, unsigned long long &total)
@@ -187,14 +191,16 @@ static int oc_cus(void)
 /* a caller's target for a frame of width x height (color): ic_check_frame's rules -- device memory, pitch, rows inside
  * the allocation -- and that size and layout are the frame's.  *out: the target with pitch and plane stride filled in */
 static bool oc_check_target(unsigned i, const fiasco_amd_device_target *in, unsigned width, unsigned height, int color,
-                            fiasco_amd_device_frame *out, int *device)
+                            fiasco_amd_device_frame *out, int *device, unsigned coded_w = 0, unsigned coded_h = 0, int magnify = 0)
 {
     fiasco_amd_device_frame t;
     t.data = in->data; t.pitch = in->pitch; t.plane_stride = in->plane_stride;
     t.width = in->width; t.height = in->height; t.layout = in->layout;
     if (!ic_check_frame("device target", i, &t, out)) return false;
     if (in->width != width || in->height != height) {
-        fa_set_error("<device target %u>: %u x %u pixels for a frame of %u x %u.", i, in->width, in->height, width, height);
+        if (magnify) fa_set_error("<device target %u>: %u x %u pixels for a frame of %u x %u at magnification %d: %u x %u.", i, in->width, in->height,
+                                  coded_w, coded_h, magnify, width, height);
+        else fa_set_error("<device target %u>: %u x %u pixels for a frame of %u x %u.", i, in->width, in->height, width, height);
         return false;
     }
     if ((in->layout != FIASCO_AMD_GRAY8) != (color != 0)) {
@@ -217,14 +223,33 @@ static bool oc_check_target(unsigned i, const fiasco_amd_device_target *in, unsi
 /* What the two batch entry points (this one and fiasco_amd_batch_decode_distortion_device, distortion.inc) have in
  * common: the batch has a finished pass; every finished intra frame becomes a job of the decoder, the others are
  * skipped; a frame with a target (targets may be NULL) has it checked and lives where the frame will be decoded.
- * who: the entry point, for the messages; refuse: what it holds against its own arguments, if anything. */
+ * who: the entry point, for the messages; refuse: what it holds against its own arguments, if anything.
+ * magnify: the frames are decoded at that magnification (fa_dec_job.magnify) and the targets have that size; a frame
+ * the size rule refuses at it refuses the call.  thumbs, reduce: NULL, or a second set of targets of the size at
+ * magnification -reduce, checked the same way (B.thumb). */
 struct OcBatch {
     std::vector<fa_dec_job> jobs;                         /* [n]; skip = 1: no finished intra frame */
     std::vector<fiasco_amd_device_frame> target;          /* [n] checked, pitch and plane stride filled in; data == NULL: none */
+    std::vector<fiasco_amd_device_frame> thumb;           /* [n] likewise */
     std::vector<int> device;                              /* [n] the device the job is decoded on */
 };
 
-static bool oc_batch_jobs(const char *who, const char *refuse, const fiasco_amd_batch_t *b, const fiasco_amd_device_target *targets, OcBatch &B)
+/* one target of frame i, to be decoded on device `dev', at `magnify' */
+static bool oc_batch_target(unsigned i, const fiasco_amd_device_target *in, const fa_image *im, int magnify, int dev, fiasco_amd_device_frame *out)
+{
+    unsigned w = im->width, h = im->height;
+    int tdev = -1;
+    if (magnify && !fiasco_amd_magnified_size(im->width, im->height, magnify, &w, &h)) return false;
+    if (!oc_check_target(i, in, w, h, im->color, out, &tdev, im->width, im->height, magnify)) return false;
+    if (tdev != dev) {
+        fa_set_error("<device target %u>: the target lives on device %d, the frame is decoded on device %d (no peer copy on this path).", i, tdev, dev);
+        return false;
+    }
+    return true;
+}
+
+static bool oc_batch_jobs(const char *who, const char *refuse, const fiasco_amd_batch_t *b, const fiasco_amd_device_target *targets, OcBatch &B,
+                          int magnify = 0, const fiasco_amd_device_target *thumbs = nullptr, unsigned reduce = 0)
 {
     if (!b || !b->n) { fa_set_error("%s: empty batch", who); return false; }
     if (refuse) { fa_set_error("%s: %s", who, refuse); return false; }
@@ -233,7 +258,7 @@ static bool oc_batch_jobs(const char *who, const char *refuse, const fiasco_amd_
     bool finished = false;
     for (unsigned i = 0; i < n; i++) finished = finished || (b->jobs[i].status && b->jobs[i].wfa);
     if (!finished) { fa_set_error("%s: the batch has no finished pass", who); return false; }
-    B.jobs.assign(n, fa_dec_job()); B.target.assign(n, fiasco_amd_device_frame()); B.device.assign(n, -1);
+    B.jobs.assign(n, fa_dec_job()); B.target.assign(n, fiasco_amd_device_frame()); B.thumb.assign(n, fiasco_amd_device_frame()); B.device.assign(n, -1);
     const size_t shares = dec_shares(n, B.jobs.data());
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess) { (void) hipGetLastError(); cur = -1; }
@@ -243,42 +268,62 @@ static bool oc_batch_jobs(const char *who, const char *refuse, const fiasco_amd_
         d.skip = 1;
         if (!job->status || !job->wfa || job->frame_type != FA_I_FRAME) continue;
         B.device[i] = dec_device_of(B.jobs.data(), i, shares, cur);
-        if (targets && targets[i].data) {
-            int tdev = -1;
-            if (!oc_check_target(i, &targets[i], job->image->width, job->image->height, job->image->color, &B.target[i], &tdev)) return false;
-            if (tdev != B.device[i]) {
-                fa_set_error("<device target %u>: the target lives on device %d, the frame is decoded on device %d (no peer copy on this path).", i, tdev, B.device[i]);
-                return false;
-            }
-        }
-        d.skip = 0;
+        if (magnify && !fiasco_amd_magnified_size(job->image->width, job->image->height, magnify, nullptr, nullptr)) return false;
+        if (targets && targets[i].data && !oc_batch_target(i, &targets[i], job->image, magnify, B.device[i], &B.target[i])) return false;
+        if (thumbs && thumbs[i].data && !oc_batch_target(i, &thumbs[i], job->image, -(int) reduce, B.device[i], &B.thumb[i])) return false;
+        d.skip = 0; d.magnify = magnify;
         d.wfa = job->wfa; d.width = job->image->width; d.height = job->image->height; d.color = job->image->color;
         d.frame_type = FA_I_FRAME;
     }
     return true;
 }
 
-extern "C" int fiasco_amd_batch_decode_device(const fiasco_amd_batch_t *b, const fiasco_amd_device_target *targets, void *stream)
+/* the three batch entries: the frames with a target (checked, in B) through the decoder, each at the magnification of
+ * its job, and with reduce != 0 the thumbnails of B.thumb beside them */
+static int oc_decode_batch(const char *who, const fiasco_amd_batch_t *b, OcBatch &B, unsigned reduce, void *stream)
 {
-    OcBatch B;
-    if (!oc_batch_jobs("fiasco_amd_batch_decode_device", targets ? nullptr : "no targets", b, targets, B)) return 0;
     const unsigned n = b->n;
-    std::vector<unsigned char> done(n, 0);
+    std::vector<unsigned char> done(n, 0), thumb_done(n, 0);
     unsigned wanted = 0;
     for (unsigned i = 0; i < n; i++) {
-        if (!B.target[i].data) B.jobs[i].skip = 1;                 /* a frame without a target is skipped */
+        if (!B.target[i].data && !B.thumb[i].data) B.jobs[i].skip = 1;     /* a frame without a target is skipped */
         wanted += !B.jobs[i].skip;
     }
-    if (!wanted) { fa_set_error("fiasco_amd_batch_decode_device: no frame with a finished intra automaton and a target"); return 0; }
+    if (!wanted) { fa_set_error("%s: no frame with a finished intra automaton and a target", who); return 0; }
     OcOut out;
     out.target = B.target.data(); out.done = done.data(); out.caller = (hipStream_t) stream;
+    if (reduce) { out.thumb = B.thumb.data(); out.thumb_done = thumb_done.data(); out.reduce = reduce; }
     out.ready = ic_mark_ready(stream);
     if (!out.ready) return 0;
     const int good = decode_frames(n, B.jobs.data(), &out, nullptr);
     (void) hipEventDestroy(out.ready);
     for (unsigned i = 0; i < n; i++)
-        if (!B.jobs[i].skip && !done[i]) fa_set_error("<device target %u>: %s", i, B.jobs[i].errmsg[0] ? B.jobs[i].errmsg : "decoder failed");
+        if (!B.jobs[i].skip && ((B.target[i].data && !done[i]) || (B.thumb[i].data && !thumb_done[i])))
+            fa_set_error("<device target %u>: %s", i, B.jobs[i].errmsg[0] ? B.jobs[i].errmsg : "decoder failed");
     return good;
+}
+
+extern "C" int fiasco_amd_batch_decode_device(const fiasco_amd_batch_t *b, const fiasco_amd_device_target *targets, void *stream)
+{
+    OcBatch B;
+    if (!oc_batch_jobs("fiasco_amd_batch_decode_device", targets ? nullptr : "no targets", b, targets, B)) return 0;
+    return oc_decode_batch("fiasco_amd_batch_decode_device", b, B, 0, stream);
+}
+
+extern "C" int fiasco_amd_batch_decode_device_magnified(const fiasco_amd_batch_t *b, int magnify, const fiasco_amd_device_target *targets, void *stream)
+{
+    OcBatch B;
+    if (!oc_batch_jobs("fiasco_amd_batch_decode_device_magnified", targets ? nullptr : "no targets", b, targets, B, magnify)) return 0;
+    return oc_decode_batch("fiasco_amd_batch_decode_device_magnified", b, B, 0, stream);
+}
+
+extern "C" int fiasco_amd_batch_decode_device_thumbnails(const fiasco_amd_batch_t *b, const fiasco_amd_device_target *targets, unsigned reduce,
+                                                         const fiasco_amd_device_target *thumbs, void *stream)
+{
+    OcBatch B;
+    const char *refuse = !thumbs ? "no thumbnails" : !reduce ? "a reduction of at least 1 (half the side length) is needed" : reduce > 15 ? "reduction out of range" : nullptr;
+    if (!oc_batch_jobs("fiasco_amd_batch_decode_device_thumbnails", refuse, b, targets, B, 0, thumbs, reduce)) return 0;
+    return oc_decode_batch("fiasco_amd_batch_decode_device_thumbnails", b, B, reduce, stream);
 }
 
 extern "C" int fiasco_amd_planes_to_pixels_device(const int16_t *planes, int color, const fiasco_amd_device_target *target, void *stream)

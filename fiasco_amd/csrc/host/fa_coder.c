@@ -527,6 +527,83 @@ int fiasco_amd_batch_decode_planes(const fiasco_amd_batch_t *b, unsigned i, int1
     return 1;
 }
 
+/* ---------------------------------------------------------------- magnification (include/libfiasco_amd_hip.h) */
+
+/* The size `dfiasco -m magnify' shows a frame of width x height at, and whether it decodes it at all: the rules of
+ * fiasco_decoder_new (codec/dfiasco.c:104-137) and of get_next_frame (codec/decoder.c:329-342).  Enlarging stops where a
+ * step passes 2048 x 2048 pixels; reducing stops where a side falls below 32, and the halved sides are rounded up to
+ * even.  A pure function of its arguments.  1 + the size, or 0 + a message that names the limit as the reference's does. */
+int fiasco_amd_magnified_size(unsigned width, unsigned height, int magnify, unsigned *out_w, unsigned *out_h)
+{
+    long n;
+    if (!width || !height || width > 8192 || height > 8192) {
+        fa_set_error("fiasco_amd_magnified_size: no frame of %u x %u pixels", width, height);
+        return 0;
+    }
+    if (magnify >= 0) {
+        const unsigned long long pixels = (unsigned long long) width * height;
+        for (n = 1; n <= magnify; n++)
+            if (pixels << (n << 1) > 2048ull * 2048ull) {      /* stops at n <= 12: the shift stays small */
+                fa_set_error("Magnification factor `%d' is too large for a frame of %u x %u pixels. Maximum value is %ld.",
+                             magnify, width, height, n - 1);
+                return 0;
+            }
+        if (out_w) *out_w = width << magnify;
+        if (out_h) *out_h = height << magnify;
+    } else {
+        const long k = -(long) magnify;
+        unsigned w, h;
+        for (n = 0; n <= k; n++)
+            if (width >> n < 32 || height >> n < 32) {         /* stops at n <= 9 */
+                fa_set_error("Magnification factor `%d' is too small for a frame of %u x %u pixels. Minimum value is %ld.",
+                             magnify, width, height, -(n > 1 ? n - 1 : 0));
+                return 0;
+            }
+        w = width >> k; h = height >> k;
+        if (out_w) *out_w = w + (w & 1);
+        if (out_h) *out_h = h + (h & 1);
+    }
+    return 1;
+}
+
+/* fiasco_amd_batch_decode_planes() at a magnification: the planes have the size of fiasco_amd_magnified_size().  A core
+ * that hands back a frame of another size (the test oracle's host decoder) does not magnify: refused */
+int fiasco_amd_batch_decode_planes_magnified(const fiasco_amd_batch_t *b, unsigned i, int magnify, int16_t *out)
+{
+    const fa_image *orig;
+    fa_dec_job d;
+    unsigned w, h;
+    size_t npix;
+    int band;
+    if (!b || i >= b->n || !b->jobs[i].status || !b->jobs[i].wfa || !out) {
+        fa_set_error("fiasco_amd_batch_decode_planes_magnified: frame %u has no finished automaton", i);
+        return 0;
+    }
+    if (b->jobs[i].frame_type != FA_I_FRAME) {
+        fa_set_error("fiasco_amd_batch_decode_planes_magnified: intra frames only (a P/B frame needs its reference frames)");
+        return 0;
+    }
+    orig = b->jobs[i].image;
+    if (!fiasco_amd_magnified_size(orig->width, orig->height, magnify, &w, &h)) return 0;
+    memset(&d, 0, sizeof d);
+    d.wfa = b->jobs[i].wfa; d.width = orig->width; d.height = orig->height; d.color = orig->color;
+    d.frame_type = FA_I_FRAME; d.magnify = magnify;
+    if (fa_core_decode_frames(1, &d) != 1 || !d.out) {
+        fa_set_error("%s", d.errmsg[0] ? d.errmsg : "decoder failed");
+        return 0;
+    }
+    if (d.out->width != w || d.out->height != h) {
+        fa_set_error("fiasco_amd_batch_decode_planes_magnified: the decoder of this library (%s) does not magnify: %u x %u pixels "
+                     "where magnification %d shows %u x %u", fa_core_name(), d.out->width, d.out->height, magnify, w, h);
+        fa_image_free(d.out);
+        return 0;
+    }
+    npix = (size_t) w * h;
+    for (band = 0; band < (orig->color ? 3 : 1); band++) memcpy(out + (size_t) band * npix, d.out->pixels[band], npix * 2);
+    fa_image_free(d.out);
+    return 1;
+}
+
 /* ---------------------------------------------------------------- smoothing along the partition borders */
 
 /* The borders smooth_image (codec/decoder.c:674-768) blends in a frame of width x height, in an order a parallel

@@ -182,6 +182,9 @@ typedef struct fa_dec_job {
     unsigned        share_key;            /* in: as fa_job.share_key (0 = dealt by index) */
     fa_image       *out;                  /* out: the frame, or NULL + errmsg */
     char            errmsg[160];
+    int             magnify;              /* in: decode at 2^magnify times the side length (dfiasco -m; intra frames; 0 = as coded).
+                                           * out then has the size of fiasco_amd_magnified_size(); the test oracle does not know
+                                           * the field and returns the coded size: callers check the size they get back */
 } fa_dec_job;
 int  fa_core_decode_frames(unsigned n, fa_dec_job *jobs);    /* number of frames decoded */
 /* smoothing along the partition borders (smooth_image, codec/decoder.c:674-768; fa_coder.c): the borders of a frame

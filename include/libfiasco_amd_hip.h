@@ -172,7 +172,7 @@ int fiasco_amd_batch_input_planes(const fiasco_amd_batch_t *b, unsigned i, int16
  * memory (hipPointerGetAttributes) or whose rows leave its allocation; a pitch smaller than a row; a width or height
  * other than the frame's; a layout that contradicts the colour model (GRAY8 <-> gray, the RGB8 layouts <-> colour); a
  * target on a device other than the one the frame's share decodes on (the message names both; there is no peer copy on
- * this path).  Intra frames only; no smoothing (dfiasco -s 0), no magnification.
+ * this path).  Intra frames only; no smoothing (dfiasco -s 0); magnified: fiasco_amd_batch_decode_device_magnified() below.
  * fiasco_amd_planes_to_pixels_device(): the conversion alone, on `stream' itself: planes [bands][height][width] int16
  * (12.4 fixed point, bands = color ? 3 : 1) in device memory -> target.  1 ok / 0 + message. */
 typedef struct fiasco_amd_device_target {
@@ -209,6 +209,47 @@ int fiasco_amd_planes_distortion_device(const int16_t *a, const int16_t *b, int 
                                         unsigned long long sse[3], unsigned maxdiff[3], void *stream);
 /* Refused with a message, nothing written: a pointer that is not device memory, planes that leave their allocation,
  * planes on different devices, a size or a band count out of range. */
+
+/* Magnification: the reference's decoder shows a stream at 2^M times its side length (`dfiasco -m M', enlarge_image,
+ * codec/decoder.c:776-840): M < 0 gives thumbnails, M > 0 enlargements, both computed from the automaton, not scaled
+ * from pixels -- 2 M is added to the level of every state and the coordinates are shifted by M.  The device decoder's
+ * recursion never asks for the level of a state, so the frame at M is the images of the same states at level + 2 M
+ * (csrc/hip/frame_decoder.inc).  Intra frames of staged batches; no smoothing.
+ * fiasco_amd_magnified_size(): the size a frame of width x height is shown at, and whether the reference decodes it
+ * at all (codec/dfiasco.c:104-137, codec/decoder.c:329-342) -- a pure function, no device.
+ *   magnify > 0   width << magnify, height << magnify; refused if width * height << 2 n > 2048 * 2048 for an n in
+ *                 1 .. magnify
+ *   magnify < 0   k = -magnify: width >> k, height >> k, each rounded up to even; refused if width >> n < 32 or
+ *                 height >> n < 32 for an n in 0 .. k
+ * 1 + the size (out_w, out_h may be NULL), or 0 + a message that ends with the largest / smallest value the frame
+ * allows ("Maximum value is 2.", "Minimum value is -1."), as the reference's message does.  The limits are the
+ * reference's although this library codes sides up to 8192: only what the reference decodes can be pinned. */
+int fiasco_amd_magnified_size(unsigned width, unsigned height, int magnify, unsigned *out_w, unsigned *out_h);
+/* fiasco_amd_batch_decode_device() at a magnification: every target has the size of fiasco_amd_magnified_size(); the
+ * bytes are those of `dfiasco -s 0 -m magnify -o'.  magnify == 0 gives the bytes of fiasco_amd_batch_decode_device().
+ * Refused with a message, nothing written: every refusal of that call; a finished intra frame of the batch the size rule
+ * refuses at `magnify'; a target of another size, the coded one included (the message names the target's size, the
+ * coded one and the magnified one).  A frame fails alone, with a message, when its level of linear combinations + 2 magnify
+ * is above 24, or when it is below 0: blocks smaller than the reduction, which the reference shows by clamping their
+ * level at 0 so that several land on one pixel -- refused here, not reproduced.  An enlargement costs 4^magnify times
+ * the level images of the full-size decode, in time and in device memory. */
+int fiasco_amd_batch_decode_device_magnified(const fiasco_amd_batch_t *b, int magnify, const fiasco_amd_device_target *targets, void *stream);
+/* fiasco_amd_batch_decode_planes() (libfiasco_amd.h) at a magnification, the host route: int16 12.4 planes
+ * [bands][height'][width'] of the magnified size.  Refusals as that call's, the size rule's, and the two a frame fails
+ * with above.  A library whose decoder hands back the coded size (the test oracle's) is refused with a message saying
+ * that its backend does not magnify.  1 ok / 0 + message. */
+int fiasco_amd_batch_decode_planes_magnified(const fiasco_amd_batch_t *b, unsigned i, int magnify, int16_t *out);
+/* One decode, the frame and its thumbnail: fiasco_amd_batch_decode_device() into targets[i] -- targets may be NULL, and
+ * targets[i].data may be NULL: the thumbnail alone -- and the frame at magnification -reduce (reduce >= 1) into
+ * thumbs[i] (b->n entries, the size of fiasco_amd_magnified_size(); data == NULL: none for this frame; a frame with
+ * neither is skipped).  The thumbnail consists of the level images the decoder has written on its way to the full frame:
+ * behind the level launches of a flight ONE launch gathers them into reduced planes (dec_thumb_kernel) and one more
+ * conversion launch writes them.  The bytes are those of fiasco_amd_batch_decode_device_magnified(b, -reduce, ...).
+ * Refused with a message, nothing written: every refusal of fiasco_amd_batch_decode_device() for either set of targets;
+ * thumbs == NULL; reduce == 0; a frame with a thumbnail the size rule refuses at -reduce.  A frame whose blocks are smaller
+ * than the reduction fails alone, nothing of it written.  Returns the number of frames decoded. */
+int fiasco_amd_batch_decode_device_thumbnails(const fiasco_amd_batch_t *b, const fiasco_amd_device_target *targets, unsigned reduce,
+                                              const fiasco_amd_device_target *thumbs, void *stream);
 
 /* The launcher keeps the per-frame HBM slabs of finished calls in a process-wide pool
  * (hipMalloc of hundreds of MB per frame is slow); this returns the pool to the driver. */
