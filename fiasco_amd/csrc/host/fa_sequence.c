@@ -199,6 +199,47 @@ void fa_seq_gop_result(const fa_seq *s, unsigned gop, unsigned *carry_out, int *
 const char *fa_seq_gop_error(const fa_seq *s, unsigned gop) { return s->gerr[gop]; }
 const fa_stats *fa_seq_stats(const fa_seq *s, unsigned k) { return s->stats[k]; }
 
+/* tests (FIASCO_AMD_SEQ_RECONST_DIR): a reconstructed frame as files of the directory `dir' --
+ *   d<display>_t<type>.i16  the 12.4 fixed point planes, width * height int16_t each, 1 or 3 bands;
+ *   d<display>.txt          one line: the motion blocks restore_mc applies to it (codec/motion.c:37-229: the
+ *                           states up to the root of the Y band whose block level is at most p_max_level), by type
+ *                           and by level, and the blocks with a vector above p_max_level, which it skips. */
+static void seq_dump_reconst(const char *dir, const fa_image *im, const fa_wfa *w, unsigned display, int type,
+                             int color, unsigned p_max_level)
+{
+    char path[1024];
+    unsigned cnt[32][4], sum[4] = { 0, 0, 0, 0 }, skipped = 0, state, label, level, root;
+    int band;
+    FILE *f;
+    snprintf(path, sizeof path, "%s/d%u_t%d.i16", dir, display, type);
+    if ((f = fopen(path, "wb")) != NULL) {
+        for (band = 0; band < (color ? 3 : 1); band++)
+            fwrite(im->pixels[band], sizeof(int16_t), (size_t) im->width * im->height, f);
+        fclose(f);
+    }
+    memset(cnt, 0, sizeof cnt);
+    root = color ? (unsigned) FA_TREE(w, (unsigned) FA_TREE(w, w->root_state, 0), 0) : w->root_state;
+    for (state = w->basis_states; type != FA_I_FRAME && state <= root; state++)
+        for (label = 0; label < 2; label++) {
+            const fa_mv *mv = &w->mv[state * 2 + label];
+            level = (unsigned) w->level_of_state[state] - 1;
+            if (mv->type == FA_MV_NONE) continue;
+            if (level > p_max_level) { skipped++; continue; }
+            cnt[level < 32 ? level : 31][mv->type]++;
+            sum[mv->type]++;
+        }
+    snprintf(path, sizeof path, "%s/d%u.txt", dir, display);
+    if ((f = fopen(path, "w")) == NULL) return;
+    fprintf(f, "display %u type %d forward %u backward %u interpolated %u skipped %u", display, type,
+            sum[FA_MV_FORWARD], sum[FA_MV_BACKWARD], sum[FA_MV_INTERPOLATED], skipped);
+    for (level = 0; level < 32; level++)
+        if (cnt[level][FA_MV_FORWARD] || cnt[level][FA_MV_BACKWARD] || cnt[level][FA_MV_INTERPOLATED])
+            fprintf(f, " level %u %u %u %u", level, cnt[level][FA_MV_FORWARD], cnt[level][FA_MV_BACKWARD],
+                    cnt[level][FA_MV_INTERPOLATED]);
+    fprintf(f, "\n");
+    fclose(f);
+}
+
 /* per-GOP running state of a sweep */
 typedef struct gop_run {
     unsigned g, pos, n;                    /* GOP, next frame inside it, frames */
@@ -356,7 +397,9 @@ int fa_seq_search(fa_seq *s, const unsigned *carry_in, const uint8_t *todo)
                 s->wfa[k]->frame_type = s->type[k];
                 memcpy(s->stats[k], jobs[b].stats, sizeof jobs[b].stats);
                 q->carry = jobs[b].lc_min_level_out;
-                need[b] = video && step + 1 < q->n;       /* reference for the frames to come (:647-651) */
+                /* reference for the frames to come (:647-651); tests that dump the planes want every frame, as the
+                 * reference decodes every frame it codes, the last of a GOP included */
+                need[b] = video && (step + 1 < q->n || fa_knob("FIASCO_AMD_SEQ_RECONST_DIR"));
             }
             fa_image_free(ims[b]); ims[b] = NULL;
         }
@@ -396,6 +439,11 @@ int fa_seq_search(fa_seq *s, const unsigned *carry_in, const uint8_t *todo)
                         fprintf(lf, "%u %u %d %016llx\n", q->g, step, (int) s->type[s->gfirst[q->g] + step], h);
                         fclose(lf);
                     }
+                }
+                if (q->reconst && fa_knob("FIASCO_AMD_SEQ_RECONST_DIR")) {
+                    const unsigned k = s->gfirst[q->g] + step;
+                    seq_dump_reconst(fa_knob("FIASCO_AMD_SEQ_RECONST_DIR"), q->reconst, s->wfa[k], s->order[k], s->type[k],
+                                     s->color, s->wi.p_max_level);
                 }
                 if (!q->reconst) {
                     snprintf(s->gerr[q->g], 160, "%s", djobs[b].errmsg[0] ? djobs[b].errmsg : "decoder failed");

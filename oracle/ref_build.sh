@@ -161,6 +161,65 @@ if [ -z "${FIASCO_SKIP_REF_Z3:-}" ] && { [ ! -x "$OUT/cfiasco_ref_z3" ] || [ "$0
     echo "ref_build: built $OUT/cfiasco_ref_z3 (-z 3 with defined reads)"
 fi
 
+# ---- the coder's own reconstructed frames: cfiasco_ref_recon ----
+# video_coder() decodes every frame it has coded (decode_image + restore_mc, codec/coder.c:647-651) and predicts the
+# next P / B frame from that image; nothing of the reference ever writes it out, and its decoder front end is no
+# substitute (dfiasco drifts from these frames on some videos).  This DECLARED variant writes them: ONE
+# throw-away copy of codec/coder.c under /tmp, <stdlib.h> / <stdio.h> added (the build uses -w: an undeclared getenv
+# would be taken to return int and its pointer cut in half), and one block behind the single restore_mc line -- which
+# is the lone statement of an `if', so the block runs for every frame, intra frames included.  If FIASCO_REF_RECONST_DIR
+# names a directory the block writes r<display number>_t<type>.i16 there: the reconst->pixels[] planes, width * height
+# word_t each, 1 or 3 bands (FORMAT_4_4_4).  Same flags, linked with the stock objects.  Without the variable it writes
+# the stock coder's stream (checked when tests/golden/RECONST.json is made, tests/golden/make_reconst.py).
+if [ -z "${FIASCO_SKIP_REF_RECON:-}" ] && { [ ! -x "$OUT/cfiasco_ref_recon" ] || [ "$0" -nt "$OUT/cfiasco_ref_recon" ]; }; then
+    mkdir -p "$OUT/obj_recon"
+    TMPC=$(mktemp /tmp/fiasco_coder_XXXXXX.c)
+    python3 - "$REF/codec/coder.c" "$TMPC" <<'PY' || { echo "ref_build: the reconstructed-frames patch did not apply" >&2; rm -f "$TMPC"; exit 1; }
+import sys
+src = open(sys.argv[1], encoding="latin-1").read()
+anchor = "restore_mc (0, reconst, c->mt->past, c->mt->future, wfa);\n"
+include = '#include "config.h"\n'
+if src.count(anchor) != 1 or src.count(include) != 1:
+    sys.exit("ref_build: codec/coder.c has %d restore_mc lines and %d config.h lines, expected one of each"
+             % (src.count(anchor), src.count(include)))
+block = """      { /* fiasco_amd_recon_dump */
+         const char *dir_ = getenv ("FIASCO_REF_RECONST_DIR");
+         if (dir_)
+         {
+            char name_ [1024];
+            FILE *f_;
+            int  b_;
+            snprintf (name_, sizeof name_, "%s/r%d_t%d.i16", dir_, frame, (int) type);
+            f_ = fopen (name_, "wb");
+            if (f_)
+            {
+               for (b_ = 0; b_ < (reconst->color ? 3 : 1); b_++)
+                  fwrite (reconst->pixels [b_], sizeof (word_t), (size_t) reconst->width * reconst->height, f_);
+               fclose (f_);
+            }
+         }
+      }
+"""
+src = src.replace(include, include + "#include <stdlib.h>\n#include <stdio.h>\n").replace(anchor, anchor + block)
+open(sys.argv[2], "w", encoding="latin-1").write(src)
+PY
+    # the patch must have taken exactly once (a changed upstream file must not give a silently stock build), and
+    # nothing but added lines: 2 includes + the block
+    [ "$(grep -c 'fiasco_amd_recon_dump' "$TMPC")" = 1 ] && [ "$(grep -c 'getenv ("FIASCO_REF_RECONST_DIR")' "$TMPC")" = 1 ] \
+        && [ "$(diff "$REF/codec/coder.c" "$TMPC" | grep -c '^<')" = 0 ] && [ "$(diff "$REF/codec/coder.c" "$TMPC" | grep -c '^>')" = 19 ] \
+        || { echo "ref_build: the reconstructed-frames patch did not apply" >&2; rm -f "$TMPC"; exit 1; }
+    gcc $CFLAGS -c "$TMPC" -o "$OUT/obj_recon/codec_coder.o" || { rm -f "$TMPC"; exit 1; }
+    rm -f "$TMPC"
+    robjs=()
+    for o in "${objs[@]}"; do
+        case "$o" in */codec_coder.o) robjs+=("$OUT/obj_recon/codec_coder.o");; *) robjs+=("$o");; esac
+    done
+    gcc -shared -fcommon -o "$OUT/libfiasco_ref_recon.so" "${robjs[@]}" -lm
+    gcc -fcommon -o "$OUT/cfiasco_ref_recon" "${cli[@]}" -L"$OUT" -lfiasco_ref_recon -Wl,-rpath,'$ORIGIN' -lm
+    echo "recon_variant: codec/coder.c writes reconst->pixels[] of every frame to \$FIASCO_REF_RECONST_DIR (a block behind the restore_mc line of a /tmp copy)" >> "$OUT/BUILD_INFO"
+    echo "ref_build: built $OUT/cfiasco_ref_recon (writes its reconstructed frames)"
+fi
+
 # ---- limits extension: patched throw-away copy, same flags ----
 if [ -z "${FIASCO_SKIP_REF_BIG:-}" ] && { [ ! -x "$OUT/cfiasco_ref_big" ] || [ "$0" -nt "$OUT/cfiasco_ref_big" ]; }; then
     TMPSRC=$(mktemp -d /tmp/fiasco_ref_big.XXXXXX)
