@@ -23,35 +23,6 @@ FIASCO_TILING_VARIANCE_ASC, FIASCO_TILING_VARIANCE_DSC = 2, 3
 FIASCO_RPF_RANGE_0_75, FIASCO_RPF_RANGE_1_00, FIASCO_RPF_RANGE_1_50, FIASCO_RPF_RANGE_2_00 = 0, 1, 2, 3
 FIASCO_PROGRESS_NONE, FIASCO_PROGRESS_BAR, FIASCO_PROGRESS_PERCENT = 0, 1, 2
 
-# every symbol include/libfiasco_amd.h and include/libfiasco_amd_hip.h declare
-EXPORTED_SYMBOLS = [
-    "fiasco_get_error_message", "fiasco_set_verbosity", "fiasco_get_verbosity", "fiasco_coder",
-    "fiasco_c_options_new", "fiasco_c_options_delete", "fiasco_c_options_set_smoothing",
-    "fiasco_c_options_set_frame_pattern", "fiasco_c_options_set_tiling",
-    "fiasco_c_options_set_basisfile", "fiasco_c_options_set_chroma_quality",
-    "fiasco_c_options_set_optimizations", "fiasco_c_options_set_prediction",
-    "fiasco_c_options_set_video_param", "fiasco_c_options_set_quantization",
-    "fiasco_c_options_set_progress_meter", "fiasco_c_options_set_comment",
-    "fiasco_c_options_set_title", "fiasco_calloc", "open_file", "fiasco_amd_set_limits",
-    "fiasco_amd_get_limits", "fiasco_amd_encode_batch", "fiasco_amd_free",
-    "fiasco_amd_get_stats", "fiasco_amd_reset_stats", "fiasco_amd_spec_workgroups", "fiasco_amd_core_name", "fiasco_amd_rccl_gather", "fiasco_amd_set_device",
-    "fiasco_amd_batch_stage", "fiasco_amd_batch_encode", "fiasco_amd_batch_free",
-    "fiasco_amd_batch_submit", "fiasco_amd_batch_collect", "fiasco_amd_batch_stats", "fiasco_amd_batch_decode_psnr", "fiasco_amd_batch_decode_psnr_all", "fiasco_amd_coop_workgroups", "fiasco_amd_share_of", "fiasco_amd_spec_append_helpers", "fiasco_amd_batch_decode_plane", "fiasco_amd_c_options_set_models",
-    "fiasco_amd_release_memory", "fiasco_amd_batch_upload", "fiasco_amd_set_devices", "fiasco_amd_device_count",
-    "fiasco_amd_selftest_log2", "fiasco_amd_selftest_log2_patched",
-    "fiasco_amd_selftest_log2_max_ulp",
-    "fiasco_amd_seq_open", "fiasco_amd_seq_free", "fiasco_amd_seq_gops", "fiasco_amd_seq_frames",
-    "fiasco_amd_seq_gop_of", "fiasco_amd_seq_ycol_size", "fiasco_amd_seq_initial_level",
-    "fiasco_amd_seq_search", "fiasco_amd_seq_gop_result", "fiasco_amd_seq_ycol", "fiasco_amd_seq_write",
-    "fiasco_amd_seq_probe",
-    "fiasco_amd_batch_stage_device", "fiasco_amd_batch_upload_device", "fiasco_amd_batch_input_planes",
-    "fiasco_amd_batch_decode_device", "fiasco_amd_planes_to_pixels_device",
-    "fiasco_amd_batch_decode_distortion_device", "fiasco_amd_planes_distortion_device",
-    "fiasco_amd_batch_decode_planes", "fiasco_amd_batch_smoothing_borders",
-    "fiasco_amd_magnified_size", "fiasco_amd_batch_decode_device_magnified", "fiasco_amd_batch_decode_planes_magnified",
-    "fiasco_amd_batch_decode_device_thumbnails",
-]
-
 # pixel layouts of a frame in device memory (include/libfiasco_amd_hip.h)
 FIASCO_AMD_GRAY8, FIASCO_AMD_RGB8_INTERLEAVED, FIASCO_AMD_RGB8_PLANAR = 0, 1, 2
 
@@ -70,8 +41,7 @@ class Border(ctypes.Structure):
 
 class DeviceTarget(ctypes.Structure):
     """struct fiasco_amd_device_target (include/libfiasco_amd_hip.h): a DeviceFrame whose memory is written."""
-    _fields_ = [("data", ctypes.c_void_p), ("pitch", ctypes.c_size_t), ("plane_stride", ctypes.c_size_t),
-                ("width", ctypes.c_uint), ("height", ctypes.c_uint), ("layout", ctypes.c_int)]
+    _fields_ = DeviceFrame._fields_
 
 
 class Stats(ctypes.Structure):
@@ -100,6 +70,105 @@ class Stats(ctypes.Structure):
                 ("spec_app_rows", ctypes.c_ulonglong), ("spec_app_wait", ctypes.c_ulonglong)]
 
 
+def _abi():
+    """name -> (restype, [argtypes]) of every function include/libfiasco_amd.h and include/libfiasco_amd_hip.h declare.
+    Handles (options, batches, sequences), streams and planes travel as void pointers; buffers the callers make with
+    create_string_buffer, and names, as char pointers."""
+    c = ctypes
+    P, ptr, cstr, i, u, f32, size, ull = c.POINTER, c.c_void_p, c.c_char_p, c.c_int, c.c_uint, c.c_float, c.c_size_t, c.c_ulonglong
+    pnm = [P(cstr), P(size)]                   # raw PNM buffers and their lengths
+    streams = [P(ptr), P(size)]                # the .fco byte strings a call hands back, and their lengths
+    frames, targets = P(DeviceFrame), P(DeviceTarget)
+    return {
+        # the reference's interface (fiasco.h) and the two symbols its CLI objects import
+        "fiasco_get_error_message": (cstr, []),
+        "fiasco_set_verbosity": (None, [i]),
+        "fiasco_get_verbosity": (i, []),
+        "fiasco_coder": (i, [P(cstr), cstr, f32, ptr]),
+        "fiasco_c_options_new": (ptr, []),
+        "fiasco_c_options_delete": (None, [ptr]),
+        "fiasco_c_options_set_smoothing": (i, [ptr, i]),
+        "fiasco_c_options_set_frame_pattern": (i, [ptr, cstr]),
+        "fiasco_c_options_set_tiling": (i, [ptr, i, u]),
+        "fiasco_c_options_set_basisfile": (i, [ptr, cstr]),
+        "fiasco_c_options_set_chroma_quality": (i, [ptr, f32, u]),
+        "fiasco_c_options_set_optimizations": (i, [ptr, u, u, u, u, u]),
+        "fiasco_c_options_set_prediction": (i, [ptr, i, u, u]),
+        "fiasco_c_options_set_video_param": (i, [ptr, u, i, i, i]),
+        "fiasco_c_options_set_quantization": (i, [ptr, u, i, u, i]),
+        "fiasco_c_options_set_progress_meter": (i, [ptr, i]),
+        "fiasco_c_options_set_comment": (i, [ptr, cstr]),
+        "fiasco_c_options_set_title": (i, [ptr, cstr]),
+        "fiasco_calloc": (ptr, [size, size]),
+        "open_file": (ptr, [cstr, cstr, i]),
+        # limits, models, batches of stills
+        "fiasco_amd_set_limits": (i, [u, u]),
+        "fiasco_amd_get_limits": (None, [P(u), P(u)]),
+        "fiasco_amd_c_options_set_models": (i, [ptr, cstr, cstr, cstr, cstr]),
+        "fiasco_amd_encode_batch": (i, [u] + pnm + [f32, ptr] + streams),
+        "fiasco_amd_free": (None, [ptr]),
+        "fiasco_amd_batch_stage": (ptr, [u] + pnm + [f32, ptr]),
+        "fiasco_amd_batch_encode": (i, [ptr] + streams),
+        "fiasco_amd_batch_submit": (i, [ptr]),
+        "fiasco_amd_batch_collect": (i, [ptr] + streams + [i]),
+        "fiasco_amd_batch_upload": (i, [ptr] + pnm),
+        "fiasco_amd_batch_stats": (i, [ptr, u, u, P(f32), P(f32), P(u), P(u)]),
+        "fiasco_amd_batch_free": (None, [ptr]),
+        # the decoder's outlets on a finished batch
+        "fiasco_amd_batch_decode_psnr": (i, [ptr, u, P(c.c_double), P(c.c_double)]),
+        "fiasco_amd_batch_decode_psnr_all": (i, [ptr, P(c.c_double), P(c.c_double)]),
+        "fiasco_amd_batch_decode_plane": (i, [ptr, u, u, cstr]),
+        "fiasco_amd_batch_decode_planes": (i, [ptr, u, ptr]),
+        "fiasco_amd_batch_decode_planes_magnified": (i, [ptr, u, i, ptr]),
+        "fiasco_amd_magnified_size": (i, [u, u, i, P(u), P(u)]),
+        "fiasco_amd_batch_smoothing_borders": (i, [ptr, u, P(Border), u]),
+        # sequences across processes
+        "fiasco_amd_seq_open": (ptr, [u] + pnm + [f32, ptr, u, u]),
+        "fiasco_amd_seq_free": (None, [ptr]),
+        "fiasco_amd_seq_gops": (u, [ptr]),
+        "fiasco_amd_seq_frames": (u, [ptr]),
+        "fiasco_amd_seq_gop_of": (u, [ptr, u]),
+        "fiasco_amd_seq_ycol_size": (u, [ptr]),
+        "fiasco_amd_seq_initial_level": (u, [ptr]),
+        "fiasco_amd_seq_probe": (i, [ptr, P(u)]),
+        "fiasco_amd_seq_search": (i, [ptr, P(u), P(c.c_ubyte)]),
+        "fiasco_amd_seq_gop_result": (i, [ptr, u, P(u), P(i)]),
+        "fiasco_amd_seq_ycol": (ptr, [ptr, u]),
+        "fiasco_amd_seq_write": (i, [ptr, u, cstr] + streams),
+        # the device core: counters, launch policy, devices
+        "fiasco_amd_get_stats": (None, [P(Stats)]),
+        "fiasco_amd_reset_stats": (None, []),
+        "fiasco_amd_release_memory": (None, []),
+        "fiasco_amd_core_name": (cstr, []),
+        "fiasco_amd_spec_workgroups": (i, [u, i, i, i, i]),
+        "fiasco_amd_spec_append_helpers": (i, [u, i, i, i]),
+        "fiasco_amd_coop_workgroups": (u, [u, i]),
+        "fiasco_amd_share_of": (u, [u, u, u]),
+        "fiasco_amd_set_device": (i, [i]),
+        "fiasco_amd_set_devices": (i, [P(i), i]),
+        "fiasco_amd_device_count": (i, []),
+        "fiasco_amd_rccl_gather": (i, [ptr, ptr, i, i, i, u] + pnm + [P(P(ptr)), P(P(size)), P(u)]),
+        "fiasco_amd_selftest_log2": (i, [u, u, P(ull), P(ull), P(ull), P(f32)]),
+        "fiasco_amd_selftest_log2_patched": (i, [u, u, P(ull), P(ull), P(ull)]),
+        "fiasco_amd_selftest_log2_max_ulp": (ull, []),
+        # frames in device memory, in and out
+        "fiasco_amd_batch_stage_device": (ptr, [u, frames, ptr, f32, ptr]),
+        "fiasco_amd_batch_upload_device": (i, [ptr, frames, ptr]),
+        "fiasco_amd_batch_input_planes": (i, [ptr, u, ptr]),
+        "fiasco_amd_batch_decode_device": (i, [ptr, targets, ptr]),
+        "fiasco_amd_batch_decode_device_magnified": (i, [ptr, i, targets, ptr]),
+        "fiasco_amd_batch_decode_device_thumbnails": (i, [ptr, targets, u, targets, ptr]),
+        "fiasco_amd_planes_to_pixels_device": (i, [ptr, i, targets, ptr]),
+        "fiasco_amd_batch_decode_distortion_device": (i, [ptr, P(ull), P(u), targets, ptr]),
+        "fiasco_amd_planes_distortion_device": (i, [ptr, ptr, i, u, u, P(ull), P(u), ptr]),
+    }
+
+
+_SIGNATURES = _abi()
+# every symbol include/libfiasco_amd.h and include/libfiasco_amd_hip.h declare
+EXPORTED_SYMBOLS = list(_SIGNATURES)
+
+
 def build(verbose=False):
     """Compile libfiasco_amd.so (gcc for the host C, hipcc --offload-arch=gfx950 for the
     device coder).  Works without a GPU (cross compilation)."""
@@ -120,41 +189,11 @@ class Library:
         if not os.path.exists(path):
             raise FiascoError("%s is missing: run fiasco_amd.build() (there is no fallback)" % path)
         self.path = path
-        L = self.L = ctypes.CDLL(path)
-        c = ctypes
-        L.fiasco_get_error_message.restype = c.c_char_p
-        L.fiasco_set_verbosity.argtypes = [c.c_int]
-        L.fiasco_get_verbosity.restype = c.c_int
-        L.fiasco_c_options_new.restype = c.c_void_p
-        L.fiasco_c_options_delete.argtypes = [c.c_void_p]
-        L.fiasco_coder.argtypes = [c.POINTER(c.c_char_p), c.c_char_p, c.c_float, c.c_void_p]
-        L.fiasco_coder.restype = c.c_int
-        L.fiasco_amd_c_options_set_models.argtypes = [c.c_void_p, c.c_char_p, c.c_char_p, c.c_char_p, c.c_char_p]
-        L.fiasco_amd_c_options_set_models.restype = c.c_int
-        for name, args in [
-            ("set_smoothing", [c.c_int]), ("set_frame_pattern", [c.c_char_p]),
-            ("set_tiling", [c.c_int, c.c_uint]), ("set_basisfile", [c.c_char_p]),
-            ("set_chroma_quality", [c.c_float, c.c_uint]),
-            ("set_optimizations", [c.c_uint] * 5), ("set_prediction", [c.c_int, c.c_uint, c.c_uint]),
-            ("set_video_param", [c.c_uint, c.c_int, c.c_int, c.c_int]),
-            ("set_quantization", [c.c_uint, c.c_int, c.c_uint, c.c_int]),
-            ("set_progress_meter", [c.c_int]), ("set_comment", [c.c_char_p]),
-            ("set_title", [c.c_char_p]),
-        ]:
-            fn = getattr(L, "fiasco_c_options_" + name)
-            fn.argtypes = [c.c_void_p] + args
-            fn.restype = c.c_int
-        L.fiasco_amd_set_limits.argtypes = [c.c_uint, c.c_uint]
-        L.fiasco_amd_set_limits.restype = c.c_int
-        L.fiasco_amd_get_limits.argtypes = [c.POINTER(c.c_uint), c.POINTER(c.c_uint)]
-        L.fiasco_amd_encode_batch.argtypes = [c.c_uint, c.POINTER(c.c_char_p), c.POINTER(c.c_size_t),
-                                              c.c_float, c.c_void_p, c.POINTER(c.c_void_p),
-                                              c.POINTER(c.c_size_t)]
-        L.fiasco_amd_encode_batch.restype = c.c_int
-        L.fiasco_amd_free.argtypes = [c.c_void_p]
-        L.fiasco_amd_core_name.restype = c.c_char_p
-        if hasattr(L, "fiasco_amd_get_stats"):
-            L.fiasco_amd_get_stats.argtypes = [c.POINTER(Stats)]
+        self.L = ctypes.CDLL(path)
+        for name, (restype, argtypes) in _SIGNATURES.items():      # the one place that declares the ABI to ctypes
+            if hasattr(self.L, name):
+                fn = getattr(self.L, name)
+                fn.restype, fn.argtypes = restype, argtypes
 
     # -- misc ------------------------------------------------------------------
     def error_message(self):
@@ -178,7 +217,6 @@ class Library:
     def set_devices(self, ids):
         """fiasco_amd_set_devices: the devices the batch entries spread their frames over ([] = automatic)."""
         arr = (ctypes.c_int * max(len(ids), 1))(*ids)
-        self.L.fiasco_amd_set_devices.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
         if not self.L.fiasco_amd_set_devices(arr, len(ids)):
             raise FiascoError(self.error_message())
 
@@ -186,7 +224,6 @@ class Library:
         return self.L.fiasco_amd_device_count()
 
     def set_device(self, device):
-        self.L.fiasco_amd_set_device.argtypes = [ctypes.c_int]
         if not self.L.fiasco_amd_set_device(device):
             raise FiascoError(self.error_message())
 
@@ -237,42 +274,33 @@ class Library:
         n = len(pnm_list)
         bufs = (ctypes.c_char_p * n)(*pnm_list)
         lens = (ctypes.c_size_t * n)(*[len(b) for b in pnm_list])
-        outs = (ctypes.c_void_p * n)()
-        olen = (ctypes.c_size_t * n)()
-        self.L.fiasco_amd_encode_batch(n, bufs, lens, ctypes.c_float(quality),
-                                       options.handle if options else None, outs, olen)
-        res = []
-        for i in range(n):
-            if outs[i]:
-                res.append(ctypes.string_at(outs[i], olen[i]))
-                self.L.fiasco_amd_free(outs[i])
-            else:
-                res.append(None)
-        return res
+        return _streams(self.L, n, lambda outs, olen: self.L.fiasco_amd_encode_batch(
+            n, bufs, lens, ctypes.c_float(quality), options.handle if options else None, outs, olen))
+
+
+def _streams(L, n, call):
+    """The n streams call(outs, olen) leaves in the two arrays, as bytes (None for a frame that failed); the C side's
+    copies are freed."""
+    outs = (ctypes.c_void_p * n)()
+    olen = (ctypes.c_size_t * n)()
+    call(outs, olen)
+    res = []
+    for i in range(n):
+        if outs[i]:
+            res.append(ctypes.string_at(outs[i], olen[i]))
+            L.fiasco_amd_free(outs[i])
+        else:
+            res.append(None)
+    return res
 
 
 class Batch:
     """Staged batch (fiasco_amd_batch_stage / _encode / _free): inputs stay resident in HBM
     between encode() calls."""
 
-    @staticmethod
-    def _bind(L):
-        c = ctypes
-        L.fiasco_amd_batch_stage.argtypes = [c.c_uint, c.POINTER(c.c_char_p), c.POINTER(c.c_size_t),
-                                             c.c_float, c.c_void_p]
-        L.fiasco_amd_batch_stage.restype = c.c_void_p
-        L.fiasco_amd_batch_encode.argtypes = [c.c_void_p, c.POINTER(c.c_void_p), c.POINTER(c.c_size_t)]
-        L.fiasco_amd_batch_encode.restype = c.c_int
-        L.fiasco_amd_batch_free.argtypes = [c.c_void_p]
-        L.fiasco_amd_batch_submit.argtypes = [c.c_void_p]
-        L.fiasco_amd_batch_submit.restype = c.c_int
-        L.fiasco_amd_batch_collect.argtypes = [c.c_void_p, c.POINTER(c.c_void_p), c.POINTER(c.c_size_t), c.c_int]
-        L.fiasco_amd_batch_collect.restype = c.c_int
-
     def __init__(self, lib, pnm_list, quality=20.0, options=None):
         c = ctypes
         L = lib.L
-        self._bind(L)
         self.lib = lib
         self._keep = None
         self.n = len(pnm_list)
@@ -298,11 +326,8 @@ class Batch:
         frames = list(frames)
         self.n = len(frames)
         arr = _device_frames(frames)
-        f = lib.L.fiasco_amd_batch_stage_device
-        f.argtypes = [c.c_uint, c.POINTER(DeviceFrame), c.c_void_p, c.c_float, c.c_void_p]
-        f.restype = c.c_void_p
-        cls._bind(lib.L)
-        self.handle = f(self.n, arr, _stream_of(frames, stream), c.c_float(quality), options.handle if options else None)
+        self.handle = lib.L.fiasco_amd_batch_stage_device(self.n, arr, _stream_of(frames, stream), c.c_float(quality),
+                                                          options.handle if options else None)
         if not self.handle:
             raise FiascoError(lib.error_message())
         self._keep = frames
@@ -312,28 +337,20 @@ class Batch:
     def upload_device(self, frames, stream=None):
         """fiasco_amd_batch_upload_device: new frames for every slot, converted on the device from where they lie
         (see from_device); not waited for, the next submit / collect(resubmit=True) encodes them."""
-        c = ctypes
         frames = list(frames)
         if len(frames) != self.n:
             raise FiascoError("upload_device: %d frames for a batch of %d" % (len(frames), self.n))
         arr = _device_frames(frames)
-        f = self.lib.L.fiasco_amd_batch_upload_device
-        f.argtypes = [c.c_void_p, c.POINTER(DeviceFrame), c.c_void_p]
-        f.restype = c.c_int
-        if not f(self.handle, arr, _stream_of(frames, stream)):
+        if not self.lib.L.fiasco_amd_batch_upload_device(self.handle, arr, _stream_of(frames, stream)):
             raise FiascoError(self.lib.error_message())
         self._keep = frames
 
     def input_planes(self, i):
         """fiasco_amd_batch_input_planes: the planes the coder sees for frame i, int16 [bands, h, w] (12.4 fixed point)."""
         import numpy
-        c = ctypes
-        f = self.lib.L.fiasco_amd_batch_input_planes
-        f.argtypes = [c.c_void_p, c.c_uint, c.c_void_p]
-        f.restype = c.c_int
         w, h, bands = self._geom[i]          # replacement frames keep the size and colour model of the batch
         out = numpy.empty((bands, h, w), dtype=numpy.int16)
-        if not f(self.handle, i, out.ctypes.data):
+        if not self.lib.L.fiasco_amd_batch_input_planes(self.handle, i, out.ctypes.data):
             raise FiascoError(self.lib.error_message())
         return out
 
@@ -342,12 +359,9 @@ class Batch:
         HBM, not waited for); the next submit / collect(resubmit=True) encodes them."""
         c = ctypes
         assert len(pnm_list) == self.n
-        f = self.lib.L.fiasco_amd_batch_upload
-        f.argtypes = [c.c_void_p, c.POINTER(c.c_char_p), c.POINTER(c.c_size_t)]
-        f.restype = c.c_int
         bufs = (c.c_char_p * self.n)(*pnm_list)
         lens = (c.c_size_t * self.n)(*[len(b) for b in pnm_list])
-        if not f(self.handle, bufs, lens):
+        if not self.lib.L.fiasco_amd_batch_upload(self.handle, bufs, lens):
             raise FiascoError(self.lib.error_message())
 
     def submit(self):
@@ -357,36 +371,20 @@ class Batch:
     def collect(self, resubmit=False):
         """fiasco_amd_batch_collect: streams of the submitted pass; with resubmit the next pass
         is started before the host writes them (writer of pass i overlaps search of pass i+1)."""
-        return self._run(lambda outs, olen: self.lib.L.fiasco_amd_batch_collect(
-            self.handle, outs, olen, 1 if resubmit else 0))
+        L = self.lib.L
+        return _streams(L, self.n, lambda outs, olen: L.fiasco_amd_batch_collect(self.handle, outs, olen, 1 if resubmit else 0))
 
     def encode(self):
-        return self._run(lambda outs, olen: self.lib.L.fiasco_amd_batch_encode(self.handle, outs, olen))
-
-    def _run(self, call):
-        outs = (ctypes.c_void_p * self.n)()
-        olen = (ctypes.c_size_t * self.n)()
-        call(outs, olen)
-        res = []
-        for i in range(self.n):
-            if outs[i]:
-                res.append(ctypes.string_at(outs[i], olen[i]))
-                self.lib.L.fiasco_amd_free(outs[i])
-            else:
-                res.append(None)
-        return res
+        L = self.lib.L
+        return _streams(L, self.n, lambda outs, olen: L.fiasco_amd_batch_encode(self.handle, outs, olen))
 
     def stats(self, i, band=0):
         """fiasco_amd_batch_stats: root-range costs / squared error of frame i (band 0..2) of the
         last finished pass and the coder-side PSNR the reference reports (codec/coder.c:918-923)."""
         import math
         c = ctypes
-        f = self.lib.L.fiasco_amd_batch_stats
-        f.argtypes = [c.c_void_p, c.c_uint, c.c_uint, c.POINTER(c.c_float), c.POINTER(c.c_float),
-                      c.POINTER(c.c_uint), c.POINTER(c.c_uint)]
-        f.restype = c.c_int
         costs, err, w, h = c.c_float(), c.c_float(), c.c_uint(), c.c_uint()
-        if not f(self.handle, i, band, costs, err, w, h):
+        if not self.lib.L.fiasco_amd_batch_stats(self.handle, i, band, costs, err, w, h):
             return None
         mse = err.value / w.value / h.value
         return {"costs": costs.value, "err": err.value, "width": w.value, "height": h.value,
@@ -394,11 +392,8 @@ class Batch:
 
     def decode_plane(self, i, band, width, height):
         """fiasco_amd_batch_decode_plane: the decoded band as bytes (the payload of dfiasco -s 0's PGM for gray)."""
-        f = self.lib.L.fiasco_amd_batch_decode_plane
-        f.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_uint, ctypes.c_char_p]
-        f.restype = ctypes.c_int
         buf = ctypes.create_string_buffer(width * height)
-        if not f(self.handle, i, band, buf):
+        if not self.lib.L.fiasco_amd_batch_decode_plane(self.handle, i, band, buf):
             raise FiascoError(self.lib.error_message())
         return buf.raw
 
@@ -407,18 +402,13 @@ class Batch:
         (12.4 fixed point).  magnify != 0: fiasco_amd_batch_decode_planes_magnified, the frame at 2^magnify times its
         side length as `dfiasco -m` shows it; h, w are those of magnified_size()."""
         import numpy
-        c = ctypes
+        L = self.lib.L
         w, h, bands = self._geom[i]
         if magnify:
             w, h = magnified_size(self.lib, w, h, magnify)
-            f = self.lib.L.fiasco_amd_batch_decode_planes_magnified
-            f.argtypes = [c.c_void_p, c.c_uint, c.c_int, c.c_void_p]
-        else:
-            f = self.lib.L.fiasco_amd_batch_decode_planes
-            f.argtypes = [c.c_void_p, c.c_uint, c.c_void_p]
-        f.restype = c.c_int
         out = numpy.empty((bands, h, w), dtype=numpy.int16)
-        if not (f(self.handle, i, magnify, out.ctypes.data) if magnify else f(self.handle, i, out.ctypes.data)):
+        if not (L.fiasco_amd_batch_decode_planes_magnified(self.handle, i, magnify, out.ctypes.data) if magnify
+                else L.fiasco_amd_batch_decode_planes(self.handle, i, out.ctypes.data)):
             raise FiascoError(self.lib.error_message())
         return out
 
@@ -426,10 +416,7 @@ class Batch:
         """fiasco_amd_batch_smoothing_borders: the borders the reference's decoder smooths frame i along, as a list of
         (x, y, len, level, pass) sorted by pass -- odd level: rows y - 1 and y, columns x .. x + len - 1; even level:
         columns x - 1 and x, rows y .. y + len - 1.  The borders of one pass share no pixel."""
-        c = ctypes
         f = self.lib.L.fiasco_amd_batch_smoothing_borders
-        f.argtypes = [c.c_void_p, c.c_uint, c.POINTER(Border), c.c_uint]
-        f.restype = c.c_int
         n = f(self.handle, i, None, 0)
         if not n:
             raise FiascoError(self.lib.error_message())
@@ -448,22 +435,15 @@ class Batch:
         queued on it afterwards sees the pixels, no host synchronisation needed.  Returns the number of frames written.
         magnify != 0: fiasco_amd_batch_decode_device_magnified, the bytes of `dfiasco -s 0 -m magnify -o`; every target
         has the size magnified_size() gives for its frame."""
-        c = ctypes
         targets = list(targets)
         if len(targets) != self.n:
             raise FiascoError("decode_device: %d targets for a batch of %d" % (len(targets), self.n))
         arr = _device_targets(targets)
         on = _stream_of([t for t in targets if t is not None], stream)
         if magnify:
-            f = self.lib.L.fiasco_amd_batch_decode_device_magnified
-            f.argtypes = [c.c_void_p, c.c_int, c.POINTER(DeviceTarget), c.c_void_p]
-            f.restype = c.c_int
-            good = f(self.handle, magnify, arr, on)
+            good = self.lib.L.fiasco_amd_batch_decode_device_magnified(self.handle, magnify, arr, on)
         else:
-            f = self.lib.L.fiasco_amd_batch_decode_device
-            f.argtypes = [c.c_void_p, c.POINTER(DeviceTarget), c.c_void_p]
-            f.restype = c.c_int
-            good = f(self.handle, arr, on)
+            good = self.lib.L.fiasco_amd_batch_decode_device(self.handle, arr, on)
         if not good:
             raise FiascoError(self.lib.error_message())
         return good
@@ -474,7 +454,6 @@ class Batch:
         the same frame at 1 / 2^reduce of its side length (reduce >= 1) into `thumbs` -- the bytes
         decode_device(magnify=-reduce) gives; a thumb has the size magnified_size(lib, w, h, -reduce), None skips it.
         `stream` as decode_device.  Returns the number of frames decoded."""
-        c = ctypes
         thumbs = list(thumbs)
         if reduce < 1:
             raise FiascoError("decode_thumbnails: reduce = %d (1 halves the side length)" % reduce)
@@ -487,10 +466,8 @@ class Batch:
                 raise FiascoError("decode_thumbnails: %d targets for a batch of %d" % (len(targets), self.n))
             arr = _device_targets(targets)
         tarr = _device_targets(thumbs)
-        f = self.lib.L.fiasco_amd_batch_decode_device_thumbnails
-        f.argtypes = [c.c_void_p, c.POINTER(DeviceTarget), c.c_uint, c.POINTER(DeviceTarget), c.c_void_p]
-        f.restype = c.c_int
-        good = f(self.handle, arr, reduce, tarr, _stream_of([t for t in (targets or []) + thumbs if t is not None], stream))
+        good = self.lib.L.fiasco_amd_batch_decode_device_thumbnails(
+            self.handle, arr, reduce, tarr, _stream_of([t for t in (targets or []) + thumbs if t is not None], stream))
         if not good:
             raise FiascoError(self.lib.error_message())
         return good
@@ -512,11 +489,9 @@ class Batch:
             if len(targets) != n:
                 raise FiascoError("decode_distortion_device: %d targets for a batch of %d" % (len(targets), n))
             arr = _device_targets(targets)
-        f = self.lib.L.fiasco_amd_batch_decode_distortion_device
-        f.argtypes = [c.c_void_p, c.POINTER(c.c_ulonglong), c.POINTER(c.c_uint), c.POINTER(DeviceTarget), c.c_void_p]
-        f.restype = c.c_int
         s, m = (c.c_ulonglong * (3 * n))(), (c.c_uint * (3 * n))()
-        good = f(self.handle, s, m, arr, _stream_of([t for t in targets or [] if t is not None], stream))
+        good = self.lib.L.fiasco_amd_batch_decode_distortion_device(
+            self.handle, s, m, arr, _stream_of([t for t in targets or [] if t is not None], stream))
         if not good:
             raise FiascoError(self.lib.error_message())
         psnr = []
@@ -529,22 +504,16 @@ class Batch:
     def decode_psnr_all(self):
         """fiasco_amd_batch_decode_psnr_all: (n decoded, [[psnr dB per band]], [[mse per band]]) of all frames,
         decoded by one call of the device decoder."""
-        f = self.lib.L.fiasco_amd_batch_decode_psnr_all
         n = self.n
-        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-        f.restype = ctypes.c_int
         p = (ctypes.c_double * (3 * n))(); m = (ctypes.c_double * (3 * n))()
-        good = f(self.handle, p, m)
+        good = self.lib.L.fiasco_amd_batch_decode_psnr_all(self.handle, p, m)
         return good, [list(p[3 * i:3 * i + 3]) for i in range(n)], [list(m[3 * i:3 * i + 3]) for i in range(n)]
 
     def decode_psnr(self, i):
         """fiasco_amd_batch_decode_psnr: decoded PSNR in dB per band of frame i (what `dfiasco -s 0` +
         `pnmpsnr` print for a gray frame), and the mean squared errors."""
-        f = self.lib.L.fiasco_amd_batch_decode_psnr
-        f.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-        f.restype = ctypes.c_int
         ps, ms = (ctypes.c_double * 3)(), (ctypes.c_double * 3)()
-        if not f(self.handle, i, ps, ms):
+        if not self.lib.L.fiasco_amd_batch_decode_psnr(self.handle, i, ps, ms):
             raise FiascoError(self.lib.error_message())
         return list(ps), list(ms)
 
@@ -622,12 +591,8 @@ def magnified_size(lib, width, height, magnify):
     """fiasco_amd_magnified_size: (width, height) at which `dfiasco -m magnify` shows a frame of width x height --
     << magnify, or >> -magnify rounded up to even.  FiascoError with the reference's limit ("Maximum value is N." /
     "Minimum value is -N.") where the reference refuses.  A pure function; no device needed."""
-    c = ctypes
-    f = lib.L.fiasco_amd_magnified_size
-    f.argtypes = [c.c_uint, c.c_uint, c.c_int, c.POINTER(c.c_uint), c.POINTER(c.c_uint)]
-    f.restype = c.c_int
-    w, h = c.c_uint(), c.c_uint()
-    if not f(width, height, magnify, w, h):
+    w, h = ctypes.c_uint(), ctypes.c_uint()
+    if not lib.L.fiasco_amd_magnified_size(width, height, magnify, w, h):
         raise FiascoError(lib.error_message())
     return w.value, h.value
 
@@ -636,23 +601,27 @@ def planes_to_pixels_device(lib, planes, target, stream=None):
     """fiasco_amd_planes_to_pixels_device: the decoder's last step alone.  `planes`: a packed int16 array on the GPU
     (12.4 fixed point), H x W for gray or 3 x H x W for Y, Cb, Cr; `target`: as Batch.decode_device.  The conversion
     runs on `stream` (default as decode_device)."""
-    c = ctypes
-    cai = getattr(planes, "__cuda_array_interface__", None)
-    if cai is None:
-        raise FiascoError("the planes are not in device memory (no __cuda_array_interface__)")
-    shape = tuple(int(v) for v in cai["shape"])
-    if cai["typestr"] not in ("<i2", "=i2") or len(shape) not in (2, 3) or (len(shape) == 3 and shape[0] != 3):
-        raise FiascoError("planes: int16 H x W or 3 x H x W expected, not %s %s" % (cai["typestr"], shape))
-    if cai.get("strides") is not None and tuple(int(v) for v in cai["strides"]) != tuple(2 * v for v in _packed_strides(shape)):
-        raise FiascoError("planes: strides %s are not those of a packed array" % (tuple(cai["strides"]),))
+    address, shape = _packed_planes(None, planes)
     arr = _device_targets([target])
     if (arr[0].height, arr[0].width) != shape[-2:]:
         raise FiascoError("target of %d x %d pixels for planes of %d x %d" % (arr[0].width, arr[0].height, shape[-1], shape[-2]))
-    f = lib.L.fiasco_amd_planes_to_pixels_device
-    f.argtypes = [c.c_void_p, c.c_int, c.POINTER(DeviceTarget), c.c_void_p]
-    f.restype = c.c_int
-    if not f(int(cai["data"][0]), 1 if len(shape) == 3 else 0, arr, _stream_of([target], stream)):
+    if not lib.L.fiasco_amd_planes_to_pixels_device(address, 1 if len(shape) == 3 else 0, arr, _stream_of([target], stream)):
         raise FiascoError(lib.error_message())
+
+
+def _packed_planes(name, p):
+    """(address, shape) of packed int16 planes on the GPU, H x W or 3 x H x W; `name' tells the planes of a call apart in
+    the refusals (None: it has one set)."""
+    what = "planes" if name is None else "planes `%s'" % name
+    cai = getattr(p, "__cuda_array_interface__", None)
+    if cai is None:
+        raise FiascoError("the %s are not in device memory (no __cuda_array_interface__)" % what)
+    shape = tuple(int(v) for v in cai["shape"])
+    if cai["typestr"] not in ("<i2", "=i2") or len(shape) not in (2, 3) or (len(shape) == 3 and shape[0] != 3):
+        raise FiascoError("%s: int16 H x W or 3 x H x W expected, not %s %s" % (what, cai["typestr"], shape))
+    if cai.get("strides") is not None and tuple(int(v) for v in cai["strides"]) != tuple(2 * v for v in _packed_strides(shape)):
+        raise FiascoError("%s: strides %s are not those of a packed array" % (what, tuple(cai["strides"])))
+    return int(cai["data"][0]), shape
 
 
 def planes_distortion_device(lib, a, b, stream=None):
@@ -660,26 +629,12 @@ def planes_distortion_device(lib, a, b, stream=None):
     on the GPU (12.4 fixed point; torch tensors or anything with __cuda_array_interface__), H x W or 3 x H x W.  Returns
     (sse, maxdiff), three integers each (0 for bands the planes do not have).  Runs on `stream` (default as
     decode_device) and waits for the result."""
-    c = ctypes
-    cais = []
-    for name, p in (("a", a), ("b", b)):
-        cai = getattr(p, "__cuda_array_interface__", None)
-        if cai is None:
-            raise FiascoError("the planes `%s' are not in device memory (no __cuda_array_interface__)" % name)
-        shape = tuple(int(v) for v in cai["shape"])
-        if cai["typestr"] not in ("<i2", "=i2") or len(shape) not in (2, 3) or (len(shape) == 3 and shape[0] != 3):
-            raise FiascoError("planes `%s': int16 H x W or 3 x H x W expected, not %s %s" % (name, cai["typestr"], shape))
-        if cai.get("strides") is not None and tuple(int(v) for v in cai["strides"]) != tuple(2 * v for v in _packed_strides(shape)):
-            raise FiascoError("planes `%s': strides %s are not those of a packed array" % (name, tuple(cai["strides"])))
-        cais.append((int(cai["data"][0]), shape))
-    if cais[0][1] != cais[1][1]:
-        raise FiascoError("planes of %s against planes of %s" % (cais[0][1], cais[1][1]))
-    shape = cais[0][1]
-    f = lib.L.fiasco_amd_planes_distortion_device
-    f.argtypes = [c.c_void_p, c.c_void_p, c.c_int, c.c_uint, c.c_uint, c.POINTER(c.c_ulonglong), c.POINTER(c.c_uint), c.c_void_p]
-    f.restype = c.c_int
-    s, m = (c.c_ulonglong * 3)(), (c.c_uint * 3)()
-    if not f(cais[0][0], cais[1][0], 3 if len(shape) == 3 else 1, shape[-1], shape[-2], s, m, _stream_of([a], stream)):
+    (pa, shape), (pb, shape_b) = _packed_planes("a", a), _packed_planes("b", b)
+    if shape != shape_b:
+        raise FiascoError("planes of %s against planes of %s" % (shape, shape_b))
+    s, m = (ctypes.c_ulonglong * 3)(), (ctypes.c_uint * 3)()
+    if not lib.L.fiasco_amd_planes_distortion_device(pa, pb, 3 if len(shape) == 3 else 1, shape[-1], shape[-2], s, m,
+                                                     _stream_of([a], stream)):
         raise FiascoError(lib.error_message())
     return list(s), list(m)
 
@@ -712,21 +667,6 @@ class Sequence:
         c = ctypes
         L = self.L = lib.L
         self.lib = lib
-        L.fiasco_amd_seq_open.argtypes = [c.c_uint, c.POINTER(c.c_char_p), c.POINTER(c.c_size_t), c.c_float,
-                                          c.c_void_p, c.c_uint, c.c_uint]
-        L.fiasco_amd_seq_open.restype = c.c_void_p
-        L.fiasco_amd_seq_free.argtypes = [c.c_void_p]
-        for name in ("gops", "frames", "ycol_size", "initial_level"):
-            f = getattr(L, "fiasco_amd_seq_" + name)
-            f.argtypes = [c.c_void_p]; f.restype = c.c_uint
-        L.fiasco_amd_seq_gop_of.argtypes = [c.c_void_p, c.c_uint]; L.fiasco_amd_seq_gop_of.restype = c.c_uint
-        L.fiasco_amd_seq_search.argtypes = [c.c_void_p, c.POINTER(c.c_uint), c.POINTER(c.c_ubyte)]
-        L.fiasco_amd_seq_search.restype = c.c_int
-        L.fiasco_amd_seq_gop_result.argtypes = [c.c_void_p, c.c_uint, c.POINTER(c.c_uint), c.POINTER(c.c_int)]
-        L.fiasco_amd_seq_gop_result.restype = c.c_int
-        L.fiasco_amd_seq_ycol.argtypes = [c.c_void_p, c.c_uint]; L.fiasco_amd_seq_ycol.restype = c.c_void_p
-        L.fiasco_amd_seq_write.argtypes = [c.c_void_p, c.c_uint, c.c_char_p, c.POINTER(c.c_void_p), c.POINTER(c.c_size_t)]
-        L.fiasco_amd_seq_write.restype = c.c_int
         self._keep = (list(pnm_list), options)                      # borrowed by the C side
         n = len(pnm_list)
         self._bufs = (c.c_char_p * n)(*pnm_list)
@@ -746,10 +686,7 @@ class Sequence:
 
     def probe(self):
         """Level to speculate for the GOPs behind the first: what frame 0 alone leaves."""
-        c = ctypes
-        self.L.fiasco_amd_seq_probe.argtypes = [c.c_void_p, c.POINTER(c.c_uint)]
-        self.L.fiasco_amd_seq_probe.restype = c.c_int
-        lv = c.c_uint()
+        lv = ctypes.c_uint()
         if not self.L.fiasco_amd_seq_probe(self.handle, lv):
             raise FiascoError(self.lib.error_message())
         return lv.value

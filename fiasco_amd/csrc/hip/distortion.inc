@@ -8,7 +8,7 @@
  *  ds_distortion_kernel per decoder flight compares the two for all frames of the flight and leaves, per frame and
  *  band, the sum of the squared errors and the largest absolute error: 12 bytes per band cross to the host, no plane.
  *
- *  Arithmetic: both sides as the bytes psnr_of() (host/fa_coder.c) and fiasco_amd_batch_decode_plane() form,
+ *  Arithmetic: both sides as the bytes psnr_of() (host/fa_batch_decode.c) and fiasco_amd_batch_decode_plane() form,
  *    a = clip255((orig >> 4) + 128), c = clip255((dec >> 4) + 128)      arithmetic shift, lib/image.c gray_write
  *    d = a - c,  sse += d * d,  maxdiff = max(maxdiff, |d|)
  *  Colour compares Y, Cb and Cr as planes, as psnr_of() does.  Everything is an integer: the sum is exact, the order

@@ -27,14 +27,15 @@ __global__ void selftest_log2_kernel(unsigned first_bits, unsigned n, double *ou
     out[i] = v;
 }
 
-struct L2Task { const double *dev; unsigned first_bits, n, t, nt; unsigned long long dd, df; unsigned bad;
+/* share t of the comparison on the host (fa_fan_out): what it found */
+struct L2Task { const double *dev; unsigned first_bits, n; unsigned long long dd, df; unsigned bad;
                 unsigned long long max_ulp;
                 std::vector<std::pair<unsigned, double>> *collect; };
 
-static void *l2_thread(void *arg)
+static void l2_share(void *ctx, unsigned t, unsigned nt)
 {
-    L2Task *k = (L2Task *) arg;
-    for (unsigned i = k->t; i < k->n; i += k->nt) {
+    L2Task *k = (L2Task *) ctx + t;
+    for (unsigned i = t; i < k->n; i += nt) {
         unsigned bits = k->first_bits + i;
         float p; memcpy(&p, &bits, 4);
         double h = log2((double) p), d = k->dev[i];
@@ -48,7 +49,6 @@ static void *l2_thread(void *arg)
             if ((float) -h != (float) -d) { if (!k->df) k->bad = bits; k->df++; }
         }
     }
-    return nullptr;
 }
 
 /* the table of host log2 values the kernels use (DevFrame.l2_*), per process */
@@ -85,16 +85,10 @@ static int log2_compare(unsigned exp_lo, unsigned exp_hi, bool use_table, unsign
             return 0;
         }
         enum { NT = 16 };
-        pthread_t th[NT];
         L2Task task[NT];
         std::vector<std::pair<unsigned, double>> part[NT];
-        int started[NT] = { 0 };
-        for (unsigned t = 0; t < NT; t++) {
-            task[t] = L2Task{ h_out, first, n, t, NT, 0, 0, 0, 0, collect ? &part[t] : nullptr };
-            if (t) started[t] = pthread_create(&th[t], nullptr, l2_thread, &task[t]) == 0;
-        }
-        l2_thread(&task[0]);
-        for (unsigned t = 1; t < NT; t++) { if (started[t]) pthread_join(th[t], nullptr); else l2_thread(&task[t]); }
+        for (unsigned t = 0; t < NT; t++) task[t] = L2Task{ h_out, first, n, 0, 0, 0, 0, collect ? &part[t] : nullptr };
+        fa_fan_out(NT, l2_share, task);
         for (unsigned t = 0; t < NT; t++) {
             dd += task[t].dd;
             if (task[t].max_ulp > g_l2_max_ulp) g_l2_max_ulp = task[t].max_ulp;

@@ -265,15 +265,12 @@ static bool oc_batch_jobs(const char *who, const char *refuse, const fiasco_amd_
     for (unsigned i = 0; i < n; i++) {
         const fa_job *job = &b->jobs[i];
         fa_dec_job &d = B.jobs[i];
-        d.skip = 1;
-        if (!job->status || !job->wfa || job->frame_type != FA_I_FRAME) continue;
+        fa_dec_job_of(job, magnify, &d);
+        if (d.skip) continue;
         B.device[i] = dec_device_of(B.jobs.data(), i, shares, cur);
         if (magnify && !fiasco_amd_magnified_size(job->image->width, job->image->height, magnify, nullptr, nullptr)) return false;
         if (targets && targets[i].data && !oc_batch_target(i, &targets[i], job->image, magnify, B.device[i], &B.target[i])) return false;
         if (thumbs && thumbs[i].data && !oc_batch_target(i, &thumbs[i], job->image, -(int) reduce, B.device[i], &B.thumb[i])) return false;
-        d.skip = 0; d.magnify = magnify;
-        d.wfa = job->wfa; d.width = job->image->width; d.height = job->image->height; d.color = job->image->color;
-        d.frame_type = FA_I_FRAME;
     }
     return true;
 }

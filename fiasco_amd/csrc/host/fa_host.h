@@ -52,6 +52,14 @@ void fa_message(const char *fmt, ...);
 void fa_debug(const char *fmt, ...);
 void fa_progress(const char *fmt, ...);
 
+/* ---------------- host threads (fa_threads.c) ---------------- */
+#define FA_FAN_MAX 32
+unsigned fa_online_cpus(void);   /* sysconf(_SC_NPROCESSORS_ONLN), at least 1 */
+/* share(ctx, t, nt) for t = 0 .. nt - 1, nt clamped to 1 .. FA_FAN_MAX: share 0 on the caller, the others on threads (on
+ * the caller where no thread starts); returns when all are done.  A share takes items t, t + nt, ... and leaves what
+ * the caller needs of it in arrays of ctx indexed by t */
+void fa_fan_out(unsigned nt, void (*share)(void *ctx, unsigned t, unsigned nt), void *ctx);
+
 /* ---------------- reduced precision format (reference lib/rpf.h) ---------------- */
 typedef struct fa_rpf {
     unsigned mantissa_bits;
@@ -187,8 +195,8 @@ typedef struct fa_dec_job {
                                            * the field and returns the coded size: callers check the size they get back */
 } fa_dec_job;
 int  fa_core_decode_frames(unsigned n, fa_dec_job *jobs);    /* number of frames decoded */
-/* smoothing along the partition borders (smooth_image, codec/decoder.c:674-768; fa_coder.c): the borders of a frame
- * in passes (fiasco_amd_batch_smoothing_borders) */
+/* smoothing along the partition borders (smooth_image, codec/decoder.c:674-768; fa_batch_decode.c): the borders of a
+ * frame in passes (fiasco_amd_batch_smoothing_borders) */
 unsigned fa_smoothing_borders(const fa_wfa *w, unsigned width, unsigned height, int color, fiasco_amd_border *out, unsigned cap);
 void fa_core_release_dev(void *dev, int dev_id);
 
@@ -371,6 +379,9 @@ struct fiasco_amd_batch {
     int        normal_domains, delta_domains, prediction;
     void      *staged;        /* core handle: inputs resident where the core computes */
 };
+/* a finished job as a job of the decoder, at magnification `magnify' (fa_batch_decode.c): the one place that fills it.
+ * A job that is not a finished intra frame gives skip = 1 and nothing else */
+void fa_dec_job_of(const fa_job *job, int magnify, fa_dec_job *d);
 /* the job of one still: the automaton with the initial basis loaded (1 ok / 0 + message) */
 int fa_prepare_job(fa_job *job, const fa_image *im, const fa_cparams *cp, const char *basis);
 unsigned fa_image_level(unsigned width, unsigned height);      /* codec/coder.c:247-255 */

@@ -26,9 +26,7 @@
 #include <string.h>
 #include <ctype.h>
 #include <math.h>
-#include <pthread.h>
 #include <time.h>
-#include <unistd.h>
 #include "fa_host.h"
 
 /* developer aid: FIASCO_AMD_SEQ_TIMING=1 prints where a sweep spends its time (stderr) */
@@ -248,21 +246,20 @@ typedef struct gop_run {
     unsigned carry;
 } gop_run;
 
-/* parsing the inputs of one step: share `first, first + stride, ...' of the running GOPs */
-#define PARSE_THREADS 16
+/* parsing the inputs of one step: share `t, t + nt, ...' of the running GOPs */
 typedef struct parsed { fa_image *im; char err[160]; } parsed;
-typedef struct parse_share {
+typedef struct parse_task {
     fa_seq *s;
     const gop_run *run;
     parsed *pre;
-    unsigned nrun, step, first, stride;
-} parse_share;
-static void *parse_thread(void *arg)
+    unsigned nrun, step;
+} parse_task;
+static void parse_share(void *ctx, unsigned t, unsigned nt)
 {
-    parse_share *p = (parse_share *) arg;
+    parse_task *p = (parse_task *) ctx;
     fa_seq *s = p->s;
     unsigned r;
-    for (r = p->first; r < p->nrun; r += p->stride) {
+    for (r = t; r < p->nrun; r += nt) {
         const gop_run *q = &p->run[r];
         unsigned k;
         p->pre[r].im = NULL; p->pre[r].err[0] = 0;
@@ -271,7 +268,6 @@ static void *parse_thread(void *arg)
         p->pre[r].im = fa_image_from_pnm(s->bufs[s->order[k]], s->lens[s->order[k]], s->names ? s->names[s->order[k]] : "<memory>");
         if (!p->pre[r].im) snprintf(p->pre[r].err, sizeof p->pre[r].err, "%s", fiasco_get_error_message());   /* this thread's message */
     }
-    return NULL;
 }
 
 /* Partition search of the GOPs of this rank marked in todo[], each starting from carry_in[g].
@@ -306,16 +302,12 @@ int fa_seq_search(fa_seq *s, const unsigned *carry_in, const uint8_t *todo)
         unsigned nb = 0, b, predone = 0;
         /* the inputs of this step: PNM -> planes of every GOP's frame side by side on the host's cores */
         {
-            parse_share sh[PARSE_THREADS];
-            pthread_t th[PARSE_THREADS];
-            int started[PARSE_THREADS] = { 0 };
-            long ncpu = sysconf(_SC_NPROCESSORS_ONLN);
-            unsigned nt = ncpu > PARSE_THREADS ? PARSE_THREADS : ncpu < 1 ? 1 : (unsigned) ncpu, t;
-            if (nt > nrun) nt = nrun ? nrun : 1;
-            for (t = 0; t < nt; t++) { sh[t].s = s; sh[t].run = run; sh[t].pre = pre; sh[t].nrun = nrun; sh[t].step = step; sh[t].first = t; sh[t].stride = nt; }
-            for (t = 1; t < nt; t++) started[t] = pthread_create(&th[t], NULL, parse_thread, &sh[t]) == 0;
-            parse_thread(&sh[0]);
-            for (t = 1; t < nt; t++) { if (started[t]) pthread_join(th[t], NULL); else parse_thread(&sh[t]); }
+            parse_task task;
+            unsigned nt = fa_online_cpus();
+            if (nt > 16) nt = 16;
+            if (nt > nrun) nt = nrun;
+            task.s = s; task.run = run; task.pre = pre; task.nrun = nrun; task.step = step;
+            fa_fan_out(nt, parse_share, &task);
         }
         for (r = 0; r < nrun; r++) {
             gop_run *q = &run[r];
@@ -525,26 +517,23 @@ int fa_seq_write(fa_seq *s, unsigned k, const uint8_t *ycol, fa_bitw *out)
                           s->op->delta_domains, out);
 }
 
-/* the streams of the frames `first, first + stride, ...', each into a writer of its own */
-#define WR_THREADS 16
-typedef struct wr_share {
+/* the streams of the frames `t, t + nt, ...', each into a writer of its own */
+typedef struct wr_task {
     fa_seq *s;
     fa_bitw *fb;
     uint8_t *ok;
     char (*err)[160];
-    unsigned first, stride;
-} wr_share;
-static void *wr_frames_thread(void *arg)
+} wr_task;
+static void wr_frames_share(void *ctx, unsigned t, unsigned nt)
 {
-    wr_share *w = (wr_share *) arg;
+    wr_task *w = (wr_task *) ctx;
     fa_seq *s = w->s;
     unsigned k;
-    for (k = w->first; k < s->ncoded; k += w->stride) {
+    for (k = t; k < s->ncoded; k += nt) {
         fa_bw_init(&w->fb[k]);
         w->ok[k] = (uint8_t) (fa_seq_write(s, k, NULL, &w->fb[k]) != 0);
         if (!w->ok[k]) snprintf(w->err[k], 160, "%s", fiasco_get_error_message());
     }
-    return NULL;
 }
 
 /* Everything in one process: search with speculation until every GOP started from what its
@@ -590,11 +579,8 @@ int fa_seq_encode_all(fa_seq *s, fa_bitw *out, void (*report)(const fa_wfa *, co
          * last section is flushed (lib/arith.c:86-115) --, and then what a fresh writer produced for the next frame
          * IS what the shared one would have appended.  Should a frame end inside a byte (no edges at all), the rest
          * is written the sequential way. */
-        wr_share sh[WR_THREADS];
-        pthread_t th[WR_THREADS];
-        int started[WR_THREADS] = { 0 };
-        long ncpu = sysconf(_SC_NPROCESSORS_ONLN);
-        unsigned nt = ncpu > WR_THREADS ? WR_THREADS : ncpu < 1 ? 1 : (unsigned) ncpu, t;
+        wr_task task;
+        unsigned nt = fa_online_cpus();
         fa_bitw *fb = (fa_bitw *) calloc(s->ncoded ? s->ncoded : 1, sizeof *fb);
         uint8_t *okv = (uint8_t *) calloc(s->ncoded ? s->ncoded : 1, 1);
         char (*errv)[160] = (char (*)[160]) calloc(s->ncoded ? s->ncoded : 1, 160);
@@ -608,11 +594,10 @@ int fa_seq_encode_all(fa_seq *s, fa_bitw *out, void (*report)(const fa_wfa *, co
             }
             if (report) report(s->wfa[k], s->stats[k], &s->wi);
         }
-        if (nt > s->ncoded) nt = s->ncoded ? s->ncoded : 1;
-        for (t = 0; t < nt; t++) { sh[t].s = s; sh[t].fb = fb; sh[t].ok = okv; sh[t].err = errv; sh[t].first = t; sh[t].stride = nt; }
-        for (t = 1; t < nt; t++) started[t] = pthread_create(&th[t], NULL, wr_frames_thread, &sh[t]) == 0;
-        wr_frames_thread(&sh[0]);
-        for (t = 1; t < nt; t++) { if (started[t]) pthread_join(th[t], NULL); else wr_frames_thread(&sh[t]); }
+        if (nt > 16) nt = 16;
+        if (nt > s->ncoded) nt = s->ncoded;
+        task.s = s; task.fb = fb; task.ok = okv; task.err = errv;
+        fa_fan_out(nt, wr_frames_share, &task);
         for (k = 0; k < s->ncoded && !failed; k++) {
             const int aligned = out->bitpos == 0 || out->nbits == 0;
             if (!okv[k]) { fa_set_error("%s", errv[k]); failed = 1; break; }

@@ -2,7 +2,7 @@
 tests/test_gpu_device_distortion.py; pinned to the oracle's decode_psnr without a GPU by
 tests/test_device_distortion_api.py.
 
-Both sides as the bytes psnr_of() (csrc/host/fa_coder.c) and fiasco_amd_batch_decode_plane() form --
+Both sides as the bytes psnr_of() (csrc/host/fa_batch_decode.c) and fiasco_amd_batch_decode_plane() form --
 clip255((p >> 4) + 128) with an arithmetic shift on the int16 12.4 values -- then per band the exact integer sum of
 the squared differences and the largest absolute difference."""
 import numpy as np

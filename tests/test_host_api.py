@@ -321,6 +321,95 @@ def test_upload_on_oracle_seam(oracle, inputs):
     check_upload_replaces_inputs(oracle, inputs)
 
 
+def check_batch_threads(lib, oracle):
+    """The threaded paths of the batch API (csrc/host/fa_batch.c, fa_batch_decode.c over fa_fan_out): 34 frames are
+    the smallest batch with more than one upload thread (n / 8 = 4) and more than one writer thread (n / 16 = 2)
+    where the host has the cores.  Every stream is compared with the oracle's stream of that frame coded alone, so a
+    wrong stride shows; frame 5 of the refused upload belongs to worker thread 1, which has to hand its message back."""
+    import fiasco_amd
+    import synth
+    n = 34
+    sets = [[synth.pgm_bytes(synth.synth(96, 64, 100 * k + i)) for i in range(n)] for k in range(2)]
+    oo = oracle.cli_options()
+    want = [[oracle.encode_batch([f], 20.0, oo)[0] for f in s] for s in sets]
+    oo.delete()
+    assert None not in want[0] + want[1] and len(set(want[0] + want[1])) == 2 * n      # pairwise distinct
+    o = lib.cli_options()
+    b = fiasco_amd.Batch(lib, sets[0], 20.0, o)
+    assert b.encode() == want[0], lib.error_message()
+    bad = list(sets[1]); bad[5] = synth.pgm_bytes(synth.synth(64, 64, 1))
+    with pytest.raises(fiasco_amd.FiascoError) as e:
+        b.upload(bad)
+    assert "size" in str(e.value)
+    assert b.encode() == want[0]                      # the batch kept its frames
+    b.upload(sets[1])
+    assert b.encode() == want[1]
+    good, psnr, mse = b.decode_psnr_all()
+    assert good == n
+    assert [(psnr[i], mse[i]) for i in range(n)] == [b.decode_psnr(i) for i in range(n)]
+    b.free(); o.delete()
+
+
+def test_batch_threads_on_oracle_seam(oracle):
+    check_batch_threads(oracle, oracle)
+
+
+@pytest.mark.parametrize("sanitizer", ["thread", "address,undefined"])
+def test_fan_out_helper_under_sanitizers(sanitizer, tmp_path):
+    """fa_fan_out (csrc/host/fa_threads.c) alone in a program of its own, tests/fan_out_check.c, built with a
+    sanitizer: every item once, every per-share slot written by one share, nt clamped, shares whose thread does not
+    start run on the caller -- and no report."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "fan_out_check")
+    r = subprocess.run(["gcc", "-std=gnu99", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=" + sanitizer, "-fno-sanitize-recover=all",
+                        "-I" + os.path.join(root, "fiasco_amd", "csrc", "host"), "-I" + os.path.join(root, "include"),
+                        "-o", exe, os.path.join(root, "tests", "fan_out_check.c"), "-lpthread"], capture_output=True, text=True)
+    if r.returncode != 0 and ("cannot find" in r.stderr or "unrecognized" in r.stderr):
+        pytest.skip("no %s sanitizer runtime on this machine" % sanitizer)
+    assert r.returncode == 0 and not r.stderr, r.stderr
+    out = subprocess.run([exe], capture_output=True, text=True)
+    if "unexpected memory mapping" in out.stderr:          # the runtime cannot place its shadow memory in this address space
+        pytest.skip("the %s sanitizer runtime does not start on this machine" % sanitizer)
+    assert out.returncode == 0 and "fan_out_check: ok" in out.stdout and not out.stderr, out.stdout[-2000:] + out.stderr[-4000:]
+
+
+def _declared_functions():
+    """name -> number of parameters of every function include/libfiasco_amd.h and include/libfiasco_amd_hip.h declare
+    (comment stripper and name pattern of test_headers_and_symbol_list_agree)."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    decl = {}
+    for h in ("libfiasco_amd.h", "libfiasco_amd_hip.h"):
+        src = open(os.path.join(root, "include", h)).read()
+        src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+        for name, params in re.findall(r"\b((?:fiasco_|fa_core_|open_file)\w*)\s*\(([^;{]*?)\)\s*;", src):
+            assert "(" not in params, name              # no function-pointer parameter: the commas count parameters
+            decl[name] = 0 if params.strip() == "void" else params.count(",") + 1
+    return decl
+
+
+def test_signatures_cover_the_headers():
+    """fiasco_amd._SIGNATURES, the one place the Python binding declares the C ABI: an entry for every function the
+    headers declare, with as many argument types as the declaration has parameters."""
+    decl = _declared_functions()
+    assert len(decl) == 75
+    assert set(decl) == set(fiasco_amd._SIGNATURES)
+    assert {n: len(fiasco_amd._SIGNATURES[n][1]) for n in decl} == decl
+    assert fiasco_amd.EXPORTED_SYMBOLS == list(fiasco_amd._SIGNATURES)
+    for name in ("fiasco_calloc", "open_file", "fiasco_amd_seq_ycol", "fiasco_amd_batch_stage", "fiasco_amd_batch_stage_device",
+                 "fiasco_amd_seq_open", "fiasco_c_options_new"):
+        assert fiasco_amd._SIGNATURES[name][0] is ctypes.c_void_p, name        # pointers, not ctypes' int default
+
+
+def test_binding_declares_the_abi_in_one_place():
+    """fiasco_amd/__init__.py assigns argtypes / restype only where Library.__init__ applies _SIGNATURES: no method
+    declares a signature of its own."""
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.abspath(fiasco_amd.__file__)), "__init__.py")).read()
+    lines = [l.strip() for l in src.splitlines() if re.search(r"\.(argtypes|restype)\b", l)]
+    assert lines == ["fn.restype, fn.argtypes = restype, argtypes"], lines
+
+
 # root-range figures printed by the real reference (`cfiasco -V 2`, codec/coder.c:918-923) for
 # two committed inputs: (squared error, total costs) per band
 REFERENCE_STATS = {
