@@ -44,6 +44,13 @@ class DeviceTarget(ctypes.Structure):
     _fields_ = DeviceFrame._fields_
 
 
+class SeqOutputs(ctypes.Structure):
+    """struct fiasco_amd_seq_outputs (include/libfiasco_amd_video.h)."""
+    _fields_ = [("targets", ctypes.POINTER(DeviceTarget)), ("sse", ctypes.POINTER(ctypes.c_ulonglong)),
+                ("maxdiff", ctypes.POINTER(ctypes.c_uint)), ("written", ctypes.POINTER(ctypes.c_ubyte)),
+                ("stream", ctypes.c_void_p)]
+
+
 class Stats(ctypes.Structure):
     """struct fiasco_amd_stats (include/libfiasco_amd_hip.h)."""
     _fields_ = [("kernel_ms", ctypes.c_double), ("launches", ctypes.c_ulonglong),
@@ -164,7 +171,24 @@ def _abi():
     }
 
 
+def _video_abi():
+    """the same for include/libfiasco_amd_video.h: the whole stream of a sequence in one call and its reconstructed frames
+    on the host (every build of the library), videos in device memory in and out (the HIP library)"""
+    c = ctypes
+    P, ptr, i, u, f32, size = c.POINTER, c.c_void_p, c.c_int, c.c_uint, c.c_float, c.c_size_t
+    return {
+        "fiasco_amd_seq_encode": (i, [ptr, P(ptr), P(size)]),
+        "fiasco_amd_seq_keep_reconstructed": (i, [ptr, i]),
+        "fiasco_amd_seq_reconstructed_planes": (i, [ptr, u, ptr, P(i)]),
+        "fiasco_amd_seq_open_device": (ptr, [u, P(DeviceFrame), ptr, f32, ptr, u, u]),
+        "fiasco_amd_seq_set_outputs_device": (i, [ptr, P(SeqOutputs)]),
+    }
+
+
 _SIGNATURES = _abi()
+_VIDEO_SIGNATURES = _video_abi()
+# every symbol include/libfiasco_amd_video.h declares
+VIDEO_SYMBOLS = list(_VIDEO_SIGNATURES)
 # every symbol include/libfiasco_amd.h and include/libfiasco_amd_hip.h declare
 EXPORTED_SYMBOLS = list(_SIGNATURES)
 
@@ -190,7 +214,7 @@ class Library:
             raise FiascoError("%s is missing: run fiasco_amd.build() (there is no fallback)" % path)
         self.path = path
         self.L = ctypes.CDLL(path)
-        for name, (restype, argtypes) in _SIGNATURES.items():      # the one place that declares the ABI to ctypes
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VIDEO_SIGNATURES.items()):      # the one place that declares the ABI to ctypes
             if hasattr(self.L, name):
                 fn = getattr(self.L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -675,11 +699,109 @@ class Sequence:
                                             options.handle if options else None, rank, world)
         if not self.handle:
             raise FiascoError(lib.error_message())
+        self._geom = _pnm_geometry(pnm_list[0])
+        self._opened(n, rank, world)
+
+    def _opened(self, n, rank, world):
+        L = self.L
+        self.n = n                                                  # frames in display order
         self.rank, self.world = rank, world
         self.gops = L.fiasco_amd_seq_gops(self.handle)
         self.frames = L.fiasco_amd_seq_frames(self.handle)
         self.ycol_size = L.fiasco_amd_seq_ycol_size(self.handle)
         self.initial_level = L.fiasco_amd_seq_initial_level(self.handle)
+        self._outputs = None                                        # what set_outputs lent to the C side
+
+    @classmethod
+    def from_device(cls, lib, frames, quality=20.0, options=None, rank=0, world=1, stream=None):
+        """fiasco_amd_seq_open_device: a video whose frames already live in device memory, in display order; frames
+        as Batch.from_device takes them (torch uint8 tensors or anything with __cuda_array_interface__; pitch and
+        plane stride come from the strides).  Open converts the frames this rank searches and waits for that: the
+        sources may be overwritten right after the call.  The objects are kept alive until free()."""
+        if not hasattr(lib.L, "fiasco_amd_seq_open_device"):
+            raise FiascoError("%s has no fiasco_amd_seq_open_device: videos in device memory need the HIP library" % lib.path)
+        self = cls.__new__(cls)
+        self.L, self.lib = lib.L, lib
+        frames = list(frames)
+        arr = _device_frames(frames)
+        self._keep = (frames, options)
+        self.handle = lib.L.fiasco_amd_seq_open_device(len(frames), arr, _stream_of(frames, stream), ctypes.c_float(quality),
+                                                       options.handle if options else None, rank, world)
+        if not self.handle:
+            raise FiascoError(lib.error_message())
+        self._geom = (arr[0].width, arr[0].height, 1 if arr[0].layout == FIASCO_AMD_GRAY8 else 3)
+        self._opened(len(frames), rank, world)
+        return self
+
+    def set_outputs(self, targets=None, distortion=False, stream=None):
+        """fiasco_amd_seq_set_outputs_device: from now on every search reconstructs every frame of the GOPs it searches
+        and delivers it on the device.  targets: one writable GPU array per display frame as Batch.decode_device takes
+        them (None entries: not this frame), or None; distortion: measure every frame against its original
+        (distortion() hands the sums out).  Neither: no outputs again.  The arrays live in this object."""
+        import numpy
+        if not hasattr(self.L, "fiasco_amd_seq_set_outputs_device"):
+            raise FiascoError("%s has no fiasco_amd_seq_set_outputs_device: device outputs need the HIP library" % self.lib.path)
+        if targets is None and not distortion:
+            if not self.L.fiasco_amd_seq_set_outputs_device(self.handle, None):
+                raise FiascoError(self.lib.error_message())
+            self._outputs = None
+            return
+        c = ctypes
+        o = SeqOutputs()
+        keep = {"struct": o, "targets": None, "arr": None, "sse": None, "maxdiff": None}
+        if targets is not None:
+            targets = list(targets)
+            if len(targets) != self.n:
+                raise FiascoError("set_outputs: %d targets for a sequence of %d frames" % (len(targets), self.n))
+            keep["targets"], keep["arr"] = targets, _device_targets(targets)
+            o.targets = keep["arr"]
+        if distortion:
+            keep["sse"] = numpy.zeros((self.n, 3), dtype=numpy.uint64)
+            keep["maxdiff"] = numpy.zeros((self.n, 3), dtype=numpy.uint32)
+            o.sse = keep["sse"].ctypes.data_as(c.POINTER(c.c_ulonglong))
+            o.maxdiff = keep["maxdiff"].ctypes.data_as(c.POINTER(c.c_uint))
+        keep["written"] = numpy.zeros(self.n, dtype=numpy.uint8)
+        o.written = keep["written"].ctypes.data_as(c.POINTER(c.c_ubyte))
+        st = _stream_of([t for t in (targets or []) if t is not None], stream)
+        o.stream = st.value if st is not None else None
+        if not self.L.fiasco_amd_seq_set_outputs_device(self.handle, c.byref(o)):
+            raise FiascoError(self.lib.error_message())        # nothing was set: what was lent before stays lent
+        self._outputs = keep
+
+    def distortion(self):
+        """(sse, maxdiff, written) of the last searches: numpy arrays [n, 3], [n, 3] and [n] by display frame (copies).
+        sse and maxdiff are None unless set_outputs(distortion=True)."""
+        if self._outputs is None:
+            raise FiascoError("distortion: no outputs are set (set_outputs)")
+        k = self._outputs
+        return (None if k["sse"] is None else k["sse"].copy(), None if k["maxdiff"] is None else k["maxdiff"].copy(),
+                k["written"].copy())
+
+    def encode(self):
+        """fiasco_amd_seq_encode: probe, search, verify and write in one process (world == 1); the whole stream, the
+        bytes fiasco_coder() writes."""
+        c = ctypes
+        out, n = c.c_void_p(), c.c_size_t()
+        if not self.L.fiasco_amd_seq_encode(self.handle, out, n):
+            raise FiascoError(self.lib.error_message())
+        data = c.string_at(out, n.value)
+        self.L.fiasco_amd_free(out)
+        return data
+
+    def keep_reconstructed(self, keep=True):
+        """fiasco_amd_seq_keep_reconstructed: the searches keep the coder's reconstruction of every frame on the host."""
+        if not self.L.fiasco_amd_seq_keep_reconstructed(self.handle, 1 if keep else 0):
+            raise FiascoError(self.lib.error_message())
+
+    def reconstructed_planes(self, display):
+        """fiasco_amd_seq_reconstructed_planes: (int16 [bands, h, w] 12.4 fixed point, frame type 0 I / 1 P / 2 B)."""
+        import numpy
+        w, h, bands = self._geom
+        out = numpy.empty((bands, h, w), dtype=numpy.int16)
+        t = ctypes.c_int(-1)
+        if not self.L.fiasco_amd_seq_reconstructed_planes(self.handle, display, out.ctypes.data, t):
+            raise FiascoError(self.lib.error_message())
+        return out, t.value
 
     def gop_of(self, frame):
         return self.L.fiasco_amd_seq_gop_of(self.handle, frame)

@@ -30,11 +30,13 @@
 #include <sys/stat.h>
 #include <sys/types.h>
 #include <algorithm>
+#include <string>
 #include <utility>
 #include <vector>
 #include "fa_host.h"
 #include "frame_coder.h"
 #include "libfiasco_amd_hip.h"
+#include "libfiasco_amd_video.h"
 
 /* Developer and test switches (FIASCO_AMD_SPEC, _NO_WIDE, _FORCE_TRI, _CAP_GUESS, _QUEUE_SLABS, _TRACE, ...)
  * are honoured only when FIASCO_AMD_DEBUG is set to something other than 0: a drop-in library must not
@@ -153,7 +155,7 @@ enum { DEC_FLIGHT = 32 };
 
 struct OcOut;                                   /* output_convert.inc */
 struct DsOut;                                   /* distortion.inc */
-static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const DsOut *ds);      /* frame_decoder.inc */
+static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const DsOut *ds, bool images = false);      /* frame_decoder.inc */
 
 #include "input_convert.inc"
 #include "output_convert.inc"

@@ -650,6 +650,26 @@ static void *core1_stage(unsigned n, fa_job *jobs, const fiasco_amd_device_frame
     }
     for (unsigned i = 0; i < n; i++)
         if (device_supported(&jobs[i], jobs[i].errmsg, sizeof jobs[i].errmsg)) S->slots.push_back(first_guess(S, i));
+    if (!frames) {
+        /* frames of a video that was opened from device memory (input_convert.inc, fiasco_amd_seq_open_device): the
+         * planes are read where open left them when that is this device; a frame on another device -- the device list
+         * changed after open -- goes through its host planes */
+        int here = -1;
+        if (hipGetDevice(&here) != hipSuccess) { (void) hipGetLastError(); here = -1; }
+        std::vector<FrameSlot> keep;
+        for (FrameSlot &fs : S->slots) {
+            const fa_image *im = jobs[fs.job].image;
+            if (im->src_dev && !im->pixels[0]) {
+                if (im->src_dev_id == here) fs.ext_pix = im->src_dev;
+                else if (!fa_image_host_planes(im)) {
+                    snprintf(jobs[fs.job].errmsg, sizeof jobs[fs.job].errmsg, "%s", fiasco_get_error_message());
+                    continue;
+                }
+            }
+            keep.push_back(fs);
+        }
+        S->slots.swap(keep);
+    }
     if (frames && !S->slots.empty()) {
         /* the planes never pass through the host: converted into the buffer the first pass reads, before any slot is
          * staged (a slot with ext_pix uploads no pixels) */

@@ -206,6 +206,7 @@ struct DecFrame {                     /* one frame in flight */
     unsigned long long bytes = 0;     /* algorithmic: 2 bytes per pixel written and per (pixel, term) read */
     size_t scratch_off = 0;           /* dec_flight_prepare: its scratch_b bytes of the flight's arena */
     unsigned slot = 0;                /* dec_flight_measure: its place in the result array of the measuring launch */
+    bool measured = false;            /* ... which it has only if it has an original (DsOut) */
 };
 
 static void dec_fail(fa_dec_job *j, const char *msg) { snprintf(j->errmsg, sizeof j->errmsg, "%s", msg); j->out = nullptr; }
@@ -402,6 +403,8 @@ extern "C" void fa_core_release_dev(void *dev, int dev_id)
 struct DecShare {
     fa_dec_job  *jobs;
     const OcOut *out; const DsOut *ds;          /* the optional consumers */
+    bool         images = false;                /* ... beside the host images, not instead of them (the frames of a video: the
+                                                 * sequence engine goes on with the image, fa_dec_job's consumer fields) */
     int          device = 0;                    /* the current one */
     hipStream_t  stream = nullptr;
     hipEvent_t   ev0 = nullptr, ev1 = nullptr;  /* around the device work of a flight: decoder_us */
@@ -485,7 +488,7 @@ static void dec_flight_prepare(DecShare &S, DecFlight &F, const unsigned *idx, s
     F.ds_off = F.take(S.ds ? DS_SLOTS * sizeof(DsPlane) : 0);
     F.res_off = F.take(S.ds ? DS_RES_BYTES : 0);
     F.orig_off = F.need;
-    if (S.ds) for (size_t k : F.alive) if (!S.ds->orig[F.job[k]]) (void) F.take(F.fr[k].plane_bytes);
+    if (S.ds) for (size_t k : F.alive) if (!S.ds->orig[F.job[k]] && S.ds->image[F.job[k]]) (void) F.take(F.fr[k].plane_bytes);
 }
 
 /* an arena that holds the flight.  false: it cannot be had, the flight size is halved and the caller tries the same
@@ -593,6 +596,7 @@ static void dec_flight_measure(DecShare &S, DecFlight &F)
         const unsigned bands = j->color ? 3 : 1;
         const size_t npix = (size_t) j->width * j->height;
         const int16_t *o = S.ds->orig[F.job[k]];
+        if (!o && !S.ds->image[F.job[k]]) continue;             /* a frame nobody measures */
         if (!o) {
             const fa_image *im = S.ds->image[F.job[k]];
             for (unsigned b = 0; b < bands && ok; b++)
@@ -601,9 +605,10 @@ static void dec_flight_measure(DecShare &S, DecFlight &F)
             at += D.plane_bytes;
         }
         if (!ok) break;
-        D.slot = slot++;
+        D.slot = slot++; D.measured = true;
         ds_describe(F.dstab, D.slot, o, D.planes, j->width, j->height, bands);
     }
+    if (ok && F.dstab.empty()) return;
     if (!ok || hipMemsetAsync(S.arena + F.res_off, 0, DS_RES_BYTES, S.stream) != hipSuccess
         || hipMemcpyAsync(S.arena + F.ds_off, F.dstab.data(), F.dstab.size() * sizeof(DsPlane), hipMemcpyHostToDevice, S.stream) != hipSuccess
         || !ds_launch((const DsPlane *) (S.arena + F.ds_off), F.dstab, S.arena + F.res_off, oc_cus(), S.stream))
@@ -620,7 +625,7 @@ static void dec_flight_write(DecShare &S, DecFlight &F)
             F.thoctab.emplace_back();
             oc_describe(F.thoctab.back(), F.fr[k].thumb, S.out->thumb[F.job[k]], thtotal);
         }
-        if (!S.out->target[F.job[k]].data) continue;            /* measured only, or the thumbnail only */
+        if (!S.out->target[F.job[k]].data) continue;            /* measured only, the thumbnail only, or not this frame */
         F.octab.emplace_back();
         oc_describe(F.octab.back(), F.fr[k].planes, S.out->target[F.job[k]], total);
     }
@@ -640,7 +645,7 @@ static void dec_flight_wait(DecShare &S, DecFlight &F)
 {
     (void) hipEventRecord(S.ev1, S.stream);
     if (hipStreamSynchronize(S.stream) != hipSuccess) dec_flight_fail(S, F, "device decoder: kernel failed");
-    if (S.ds && !F.alive.empty() && hipMemcpy(F.dsres.bytes, S.arena + F.res_off, DS_RES_BYTES, hipMemcpyDeviceToHost) != hipSuccess)
+    if (S.ds && !F.alive.empty() && !F.dstab.empty() && hipMemcpy(F.dsres.bytes, S.arena + F.res_off, DS_RES_BYTES, hipMemcpyDeviceToHost) != hipSuccess)
         dec_flight_fail(S, F, "device decoder: download failed");
 }
 
@@ -677,14 +682,14 @@ static void dec_flight_results(DecShare &S, DecFlight &F)
         if (written) S.out->done[i] = 1;
         const unsigned long long tvals = D.thumb ? (unsigned long long) D.tw * D.th * bands : 0ull;     /* gathered: 2 + 2 bytes; written: 2 + 1 */
         if (D.thumb) S.out->thumb_done[i] = 1;
-        if (S.ds) {
+        if (S.ds && D.measured) {
             for (unsigned b = 0; b < bands; b++) {
                 if (S.ds->sse) S.ds->sse[(size_t) i * 3 + b] = F.dsres.sums[D.slot * 3 + b];
                 if (S.ds->maxdiff) S.ds->maxdiff[(size_t) i * 3 + b] = mx[D.slot * 3 + b];
             }
             S.ds->done[i] = 1;
         }
-        if (!S.out && !S.ds && !dec_download(S, j, D)) continue;
+        if ((S.images || (!S.out && !S.ds)) && !dec_download(S, j, D)) continue;
         frames++;
         bytes += D.bytes + (S.ds ? 4 * vals : 0) + (written ? 3 * vals : 0) + 7 * tvals;
     }
@@ -725,10 +730,10 @@ static void dec_share_release_caller(DecShare &S)
 }
 
 /* the jobs `mine' of a call on this thread's device, in flights.  Returns the number of frames decoded */
-static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine, const OcOut *out, const DsOut *ds)
+static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine, const OcOut *out, const DsOut *ds, bool images)
 {
     DecShare S;
-    S.jobs = jobs; S.out = out; S.ds = ds;
+    S.jobs = jobs; S.out = out; S.ds = ds; S.images = images;
     bool usable = hipGetDevice(&S.device) == hipSuccess && hipStreamCreate(&S.stream) == hipSuccess;
     if (!usable) (void) hipGetLastError();
     else if (hipEventCreate(&S.ev0) != hipSuccess || hipEventCreate(&S.ev1) != hipSuccess) (void) hipGetLastError();
@@ -769,7 +774,7 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine, con
 /* decode n frames: dealt to the shares by the rule of dec_shares / dec_share_of (shares.inc), the shares decode side
  * by side, each on its own host thread (share 0 on the caller's; for_shares, shares.inc).  Returns the number of
  * frames decoded; a failed job has out == NULL and a message. */
-static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const DsOut *ds)
+static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const DsOut *ds, bool images)
 {
     const size_t ND = dec_shares(n, jobs);
     std::vector<std::vector<unsigned> > deal(ND);
@@ -778,10 +783,77 @@ static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const D
     for (size_t k = 0; k < ND; k++) if (!deal[k].empty()) share.push_back(k);
     if (share.empty()) return 0;
     std::vector<int> goodv(share.size(), 0);
-    for_shares(share, [&](size_t part) { goodv[part] = decode_share(jobs, deal[share[part]], out, ds); });
+    for_shares(share, [&](size_t part) { goodv[part] = decode_share(jobs, deal[share[part]], out, ds, images); });
     int good = 0;
     for (size_t k = 0; k < goodv.size(); k++) good += goodv[k];
     return good;
 }
 
-extern "C" int fa_core_decode_frames(unsigned n, fa_dec_job *jobs) { return decode_frames(n, jobs, nullptr, nullptr); }
+/* The seam.  Jobs that name consumers (fa_host.h: target, sse, maxdiff -- the outputs of a sequence) get them attached to
+ * the steps their flights have anyway: dec_flight_write and dec_flight_measure.  Such a frame is written, measured AND
+ * handed back as an image: the sequence engine predicts the next frame from it.  Targets were checked when they were
+ * set (fiasco_amd_seq_set_outputs_device).  The original is read in place where it lies on the device the job is decoded
+ * on, else copied up from its host planes (a PNM-fed frame has them, a frame on another device fetches them). */
+extern "C" int fa_core_decode_frames(unsigned n, fa_dec_job *jobs)
+{
+    bool pixels = false, sums = false;
+    void *caller = nullptr;
+    for (unsigned i = 0; i < n; i++) {
+        jobs[i].delivered = 0;
+        if (jobs[i].skip) continue;
+        const fiasco_amd_device_target *t = (const fiasco_amd_device_target *) jobs[i].target;
+        if (t && t->data) { pixels = true; caller = jobs[i].consumer_stream; }
+        if ((jobs[i].sse || jobs[i].maxdiff) && jobs[i].orig) sums = true;
+    }
+    if (!pixels && !sums) return decode_frames(n, jobs, nullptr, nullptr, false);
+    std::vector<fiasco_amd_device_frame> target(n, fiasco_amd_device_frame());
+    std::vector<unsigned char> written(n, 0), measured(n, 0);
+    std::vector<const int16_t *> orig(n, nullptr);
+    std::vector<const fa_image *> image(n, nullptr);
+    std::vector<unsigned long long> sse((size_t) n * 3, 0);
+    std::vector<unsigned> maxdiff((size_t) n * 3, 0);
+    const size_t shares = dec_shares(n, jobs);
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) { (void) hipGetLastError(); cur = -1; }
+    for (unsigned i = 0; i < n; i++) {
+        fa_dec_job *j = &jobs[i];
+        if (j->skip) continue;
+        const fiasco_amd_device_target *t = (const fiasco_amd_device_target *) j->target;
+        if (t && t->data) {
+            fiasco_amd_device_frame &f = target[i];
+            f.data = t->data; f.pitch = t->pitch; f.plane_stride = t->plane_stride; f.width = t->width; f.height = t->height; f.layout = t->layout;
+            if (!f.pitch) f.pitch = ic_row_bytes(f);
+            if (!f.plane_stride) f.plane_stride = f.pitch * f.height;
+        }
+        if ((j->sse || j->maxdiff) && j->orig) {
+            image[i] = j->orig;
+            if (j->orig->src_dev && j->orig->src_dev_id == dec_device_of(jobs, i, shares, cur)) orig[i] = j->orig->src_dev;
+            else if (!fa_image_host_planes(j->orig)) image[i] = nullptr;       /* decoded, not measured: not delivered */
+        }
+    }
+    OcOut out;
+    out.target = target.data(); out.done = written.data(); out.caller = (hipStream_t) caller; out.ready = nullptr;
+    if (pixels) {
+        out.ready = ic_mark_ready(caller);
+        if (!out.ready) {
+            for (unsigned i = 0; i < n; i++) if (!jobs[i].skip) dec_fail(&jobs[i], fiasco_get_error_message());
+            return 0;
+        }
+    }
+    DsOut ds;
+    ds.orig = orig.data(); ds.image = image.data(); ds.sse = sse.data(); ds.maxdiff = maxdiff.data(); ds.done = measured.data();
+    const int good = decode_frames(n, jobs, pixels ? &out : nullptr, sums ? &ds : nullptr, true);
+    if (out.ready) (void) hipEventDestroy(out.ready);
+    for (unsigned i = 0; i < n; i++) {
+        fa_dec_job *j = &jobs[i];
+        if (j->skip || !j->out) continue;
+        const bool wants_pixels = target[i].data != nullptr, wants_sums = image[i] != nullptr;
+        if ((wants_pixels && !written[i]) || (wants_sums && !measured[i]) || (!wants_pixels && !wants_sums)) continue;
+        for (unsigned b = 0; wants_sums && b < 3; b++) {
+            if (j->sse) j->sse[b] = sse[(size_t) i * 3 + b];
+            if (j->maxdiff) j->maxdiff[b] = maxdiff[(size_t) i * 3 + b];
+        }
+        j->delivered = 1;
+    }
+    return good;
+}

@@ -147,6 +147,27 @@ static size_t ic_extent(const fiasco_amd_device_frame &f)
     return (f.layout == FIASCO_AMD_RGB8_PLANAR ? 2 * f.plane_stride : 0) + (size_t) (f.height - 1) * f.pitch + ic_row_bytes(f);
 }
 
+/* the entry of the descriptor table for frame f, read at src (f.data, or where a copy of its bytes lies) and written to
+ * dst; total: the work items of the frames before it, moved on */
+static void ic_describe(IcFrame &d, const fiasco_amd_device_frame &f, const void *src, int16_t *dst, unsigned long long &total)
+{
+    d.src = (const unsigned char *) src; d.dst = dst;
+    d.pitch = f.pitch; d.plane_stride = f.plane_stride; d.first = total;
+    d.width = f.width; d.height = f.height; d.layout = (unsigned) f.layout; d.cpr = (f.width + 15) / 16;
+    total += (unsigned long long) d.cpr * f.height;
+}
+
+/* ONE launch for the n frames of the table at d_tab (device memory) on `stream': eight workgroups of four waves per CU,
+ * fewer when the work is less */
+static bool ic_launch(const IcFrame *d_tab, unsigned n, unsigned long long total, int ncu, hipStream_t stream)
+{
+    unsigned long long grid = (unsigned long long) (ncu > 0 ? ncu : 256) * 8, tiles = (total + 255) / 256;
+    if (grid > tiles) grid = tiles;
+    if (!grid || !n) return true;
+    ic_convert_kernel<<<dim3((unsigned) grid), dim3(256), 0, stream>>>(d_tab, n, total);
+    return hipGetLastError() == hipSuccess;
+}
+
 /* The planes of every slot's frame into up_dev[parity], by one kernel launch on the upload stream after `ready'.
  * frames[j] belongs to jobs[j]; pitch and plane_stride are filled in and everything was checked (ic_check_frame).
  * next: the frames of the NEXT pass (ext_next, taken over by the next submit), else of the first pass (ext_pix).
@@ -197,26 +218,19 @@ static bool ic_convert(Staged *S, const fiasco_amd_device_frame *frames, int par
             const fa_image *im = S->jobs[S->slots[k].job].image;
             const fiasco_amd_device_frame &f = frames[S->slots[k].job];
             IcFrame &d = S->ic_tab[k];
-            d.src = (const unsigned char *) f.data;
+            const void *src = f.data;
             if (srcdev[k] != here) {
                 /* a source on another device: its bytes, rows and gaps as they lie, over the peer link first */
                 if (hipMemcpyPeerAsync(S->peer_buf + peer_at, here, f.data, srcdev[k], ic_extent(f), S->ustream) != hipSuccess) goto hip_failed;
-                d.src = (const unsigned char *) S->peer_buf + peer_at;
+                src = S->peer_buf + peer_at;
                 peer_at += align_up(ic_extent(f), 256);
             }
-            d.dst = (int16_t *) (S->up_dev[parity] + at);
-            d.pitch = f.pitch; d.plane_stride = f.plane_stride; d.first = total;
-            d.width = f.width; d.height = f.height; d.layout = (unsigned) f.layout; d.cpr = (f.width + 15) / 16;
-            total += (unsigned long long) d.cpr * f.height;
+            ic_describe(d, f, src, (int16_t *) (S->up_dev[parity] + at), total);
             at += align_up((size_t) im->width * im->height * (im->color ? 3 : 1) * 2, 256);
         }
         if (hipMemcpyAsync(S->d_ic, S->ic_tab, ns * sizeof(IcFrame), hipMemcpyHostToDevice, S->ustream) != hipSuccess
             || hipEventRecord(S->ev_ic, S->ustream) != hipSuccess) goto hip_failed;
-        /* eight workgroups of four waves per CU, fewer when the work is less */
-        unsigned long long grid = (unsigned long long) S->ncu * 8, tiles = (total + 255) / 256;
-        if (grid > tiles) grid = tiles;
-        ic_convert_kernel<<<dim3((unsigned) grid), dim3(256), 0, S->ustream>>>(S->d_ic, (unsigned) ns, total);
-        if (hipGetLastError() != hipSuccess || hipEventRecord(S->ev_up, S->ustream) != hipSuccess) goto hip_failed;
+        if (!ic_launch(S->d_ic, (unsigned) ns, total, S->ncu, S->ustream) || hipEventRecord(S->ev_up, S->ustream) != hipSuccess) goto hip_failed;
         for (size_t k = 0; k < ns; k++) {
             FrameSlot &fs = S->slots[k];
             fa_image *im = (fa_image *) S->jobs[fs.job].image;
@@ -467,4 +481,159 @@ extern "C" int fiasco_amd_batch_upload_device(fiasco_amd_batch_t *b, const fiasc
     b->ims = nims;
     for (unsigned i = 0; i < b->n; i++) b->jobs[i].image = nims[i];
     return 1;
+}
+
+/* ------------------------------------------------------------------ videos in device memory
+ *
+ * fiasco_amd_seq_open_device(): the frames of a video as they lie in device memory.  Open converts ONCE every frame this
+ * rank will ever search -- the frames of its groups of pictures and display frame 0, which fa_seq_probe searches on
+ * every rank -- into int16 planes in a buffer the sequence owns, on the device of the share that searches the frame's
+ * GOP (fa_share_of(gop + 1, ., shares); frame 0: share 0, where the probe runs and where GOP 0 is searched).  One launch
+ * of ic_convert_kernel per share.  Open waits on the host for the conversions: the searches that follow have no ordering
+ * question left, and the caller's stream is made to wait as well.  A search then stages the planes in place
+ * (FrameSlot::ext_pix, core1_stage). */
+struct SeqPlanes { std::vector<std::pair<int, void *> > bufs; };     /* (device, allocation) */
+
+static void seq_planes_release(void *ctx)
+{
+    SeqPlanes *P = (SeqPlanes *) ctx;
+    if (!P) return;
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) { (void) hipGetLastError(); cur = -1; }
+    for (size_t k = 0; k < P->bufs.size(); k++) {
+        if (P->bufs[k].first >= 0 && P->bufs[k].first != cur) (void) hipSetDevice(P->bufs[k].first);
+        (void) hipFree(P->bufs[k].second);
+        if (P->bufs[k].first >= 0 && P->bufs[k].first != cur && cur >= 0) (void) hipSetDevice(cur);
+    }
+    delete P;
+}
+
+extern "C" fiasco_amd_seq_t *fiasco_amd_seq_open_device(unsigned n, const fiasco_amd_device_frame *frames, void *stream, float quality,
+                                                        const fiasco_c_options_t *options, unsigned rank, unsigned world)
+{
+    if (!n || !frames) { fa_set_error("No frames to open."); return nullptr; }
+    if (quality <= 0) { fa_set_error("Compression quality has to be positive."); return nullptr; }
+    if (world == 0 || rank >= world) { fa_set_error("rank %d of %d?", (int) rank, (int) world); return nullptr; }
+    if (!ic_have_device()) return nullptr;
+    std::vector<fiasco_amd_device_frame> fr(n);
+    std::vector<int> srcdev(n, -1);
+    for (unsigned i = 0; i < n; i++) {
+        if (!ic_check_frame("device frame", i, &frames[i], &fr[i])) return nullptr;
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, fr[i].data) == hipSuccess) srcdev[i] = at.device; else (void) hipGetLastError();
+    }
+    fiasco_c_options_t *defaults = nullptr;
+    const fa_options *op;
+    if (options) { op = fa_cast_options(options); if (!op) return nullptr; }
+    else { defaults = fiasco_c_options_new(); if (!defaults) return nullptr; op = fa_cast_options(defaults); }
+    /* the sequence engine: sizes and colour models, the coding order, the groups of pictures (nothing on a device yet) */
+    fa_image **images = (fa_image **) calloc(n, sizeof *images);
+    bool ok = images != nullptr;
+    for (unsigned i = 0; ok && i < n; i++) {
+        images[i] = (fa_image *) calloc(1, sizeof(fa_image));           /* no host planes: fa_image_host_planes */
+        if (!images[i]) { ok = false; break; }
+        images[i]->width = fr[i].width; images[i]->height = fr[i].height; images[i]->color = fr[i].layout != FIASCO_AMD_GRAY8;
+        images[i]->src_dev_id = -1;
+    }
+    if (!ok) {
+        for (unsigned i = 0; images && i < n; i++) fa_image_free(images[i]);
+        free(images);
+        if (defaults) fiasco_c_options_delete(defaults);
+        fa_set_error("Out of memory!");
+        return nullptr;
+    }
+    fa_seq *s = fa_seq_open_images(op, quality, n, images, rank, world);       /* takes the images, also when it refuses */
+    fiasco_amd_seq_t *q = s ? fa_seq_handle(s, defaults) : nullptr;
+    if (!q) {
+        fa_seq_free(s);
+        if (defaults) fiasco_c_options_delete(defaults);
+        return nullptr;
+    }
+    /* which frames, on which share */
+    resolve_devices();
+    const size_t D = g_devices.size();
+    std::vector<std::vector<unsigned> > mine(D);
+    std::vector<unsigned char> taken(n, 0);
+    for (unsigned k = 0; k < fa_seq_frames(s); k++) {
+        const unsigned g = fa_seq_gop_of(s, k), d = fa_seq_display_of(s, k);
+        if (!fa_seq_is_mine(s, g) && d != 0) continue;
+        if (taken[d]) continue;
+        taken[d] = 1;
+        mine[fa_share_of(g + 1, 0, (unsigned) D)].push_back(d);
+    }
+    const size_t frame_b = align_up((size_t) fr[0].width * fr[0].height * (fr[0].layout != FIASCO_AMD_GRAY8 ? 3 : 1) * 2, 256);
+    SeqPlanes *P = new SeqPlanes;
+    hipEvent_t ready = ic_mark_ready(stream);
+    std::vector<size_t> share;
+    for (size_t k = 0; k < D; k++) if (!mine[k].empty()) share.push_back(k);
+    std::vector<std::string> why(share.size());
+    std::vector<void *> got(share.size(), nullptr);
+    std::vector<int> gotdev(share.size(), -1);
+    std::vector<hipEvent_t> done(share.size(), nullptr);
+    if (ready)
+        for_shares(share, [&](size_t part) {
+            const std::vector<unsigned> &ds = mine[share[part]];
+            int here = -1, ncu = 0;
+            hipStream_t st = nullptr;
+            char *buf = nullptr;
+            IcFrame *d_tab = nullptr;
+            std::vector<IcFrame> tab(ds.size());
+            unsigned long long total = 0;
+            auto fail = [&](const char *msg) { why[part] = msg; (void) hipGetLastError(); };
+            if (hipGetDevice(&here) != hipSuccess) { fail("HIP error: no current device"); return; }
+            for (unsigned d : ds)
+                if (srcdev[d] != here) {
+                    char msg[200];
+                    snprintf(msg, sizeof msg, "<device frame %u>: the pixels live on device %d, its group of pictures is searched on device %d "
+                             "(no peer copy on this path).", d, srcdev[d], here);
+                    why[part] = msg;
+                    return;
+                }
+            if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, here) != hipSuccess || ncu <= 0) { (void) hipGetLastError(); ncu = 256; }
+            if (hipMalloc((void **) &buf, frame_b * ds.size()) != hipSuccess) {
+                char msg[200];
+                snprintf(msg, sizeof msg, "out of HBM: no room for %.1f MiB of frames", frame_b * ds.size() / 1048576.0);
+                (void) hipGetLastError();
+                why[part] = msg;
+                return;
+            }
+            got[part] = buf; gotdev[part] = here;
+            for (size_t j = 0; j < ds.size(); j++) ic_describe(tab[j], fr[ds[j]], fr[ds[j]].data, (int16_t *) (buf + j * frame_b), total);
+            bool fine = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess
+                        && hipEventCreateWithFlags(&done[part], hipEventDisableTiming) == hipSuccess
+                        && hipMalloc((void **) &d_tab, tab.size() * sizeof(IcFrame)) == hipSuccess
+                        && hipStreamWaitEvent(st, ready, 0) == hipSuccess
+                        && hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(IcFrame), hipMemcpyHostToDevice, st) == hipSuccess
+                        && ic_launch(d_tab, (unsigned) tab.size(), total, ncu, st)
+                        && hipEventRecord(done[part], st) == hipSuccess
+                        && hipStreamSynchronize(st) == hipSuccess;          /* the one host wait of open */
+            if (!fine) { why[part] = std::string("HIP error: ") + hipGetErrorString(hipGetLastError()); }
+            if (d_tab) (void) hipFree(d_tab);
+            if (st) (void) hipStreamDestroy(st);
+            if (fine)
+                for (size_t j = 0; j < ds.size(); j++) {
+                    fa_image *im = fa_seq_image(s, ds[j]);
+                    im->src_dev = (const int16_t *) (buf + j * frame_b); im->src_dev_id = here; im->src_owner = nullptr;
+                }
+        });
+    ok = ready != nullptr;
+    for (size_t k = 0; k < share.size(); k++) {
+        if (got[k]) P->bufs.push_back(std::make_pair(gotdev[k], got[k]));
+        if (done[k]) {
+            /* the caller's stream behind the conversions: the sources may be overwritten or freed in stream order */
+            if (hipStreamWaitEvent((hipStream_t) stream, done[k], 0) != hipSuccess) (void) hipGetLastError();
+            (void) hipEventDestroy(done[k]);
+        }
+        if (!why[k].empty()) { fa_set_error("%s", why[k].c_str()); ok = false; }
+    }
+    if (ready) (void) hipEventDestroy(ready);
+    fa_seq_on_free(s, seq_planes_release, P);
+    fa_image_fetch = ic_fetch;
+    if (!ok) {
+        std::string msg = fiasco_get_error_message();
+        fiasco_amd_seq_free(q);                     /* gives the buffers back */
+        fa_set_error("%s", msg.c_str());
+        return nullptr;
+    }
+    return q;
 }

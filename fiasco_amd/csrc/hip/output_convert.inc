@@ -367,3 +367,38 @@ extern "C" int fiasco_amd_planes_to_pixels_device(const int16_t *planes, int col
     if (cur >= 0 && cur != tdev) (void) hipSetDevice(cur);
     return ok ? 1 : 0;
 }
+
+/* ------------------------------------------------------------------ the outputs of a video
+ *
+ * fiasco_amd_seq_set_outputs_device(): from now on every search of the sequence reconstructs every frame of the GOPs it
+ * searches and the decoder's flights deliver it (fa_dec_job's consumer fields, frame_decoder.inc).  Every target is
+ * checked here, before any launch, by the rules of fiasco_amd_batch_decode_device(); the device it must live on is the
+ * one of the share that decodes the frame's group of pictures. */
+extern "C" int fiasco_amd_seq_set_outputs_device(fiasco_amd_seq_t *seq, const fiasco_amd_seq_outputs *o)
+{
+    fa_seq *s = fa_seq_of_handle(seq);
+    if (!s) { fa_set_error("fiasco_amd_seq_set_outputs_device: no sequence"); return 0; }
+    if (!o || (!o->targets && !o->sse && !o->maxdiff)) { fa_seq_set_outputs(s, nullptr, 0, nullptr, nullptr, nullptr, nullptr); return 1; }
+    if (!ic_have_device()) return 0;
+    unsigned w = 0, h = 0;
+    int color = 0, cur = -1;
+    fa_seq_size(s, &w, &h, &color);
+    resolve_devices();
+    const size_t D = g_devices.size();
+    if (hipGetDevice(&cur) != hipSuccess) { (void) hipGetLastError(); cur = -1; }
+    for (unsigned k = 0; o->targets && k < fa_seq_frames(s); k++) {
+        const unsigned d = fa_seq_display_of(s, k);
+        if (!o->targets[d].data) continue;
+        fiasco_amd_device_frame checked;
+        int tdev = -1, dev = g_devices[fa_share_of(fa_seq_gop_of(s, k) + 1, 0, (unsigned) D)];
+        if (dev < 0) dev = cur;
+        if (!oc_check_target(d, &o->targets[d], w, h, color, &checked, &tdev)) return 0;
+        if (tdev != dev) {
+            fa_set_error("<device target %u>: the target lives on device %d, the frame is decoded on device %d (no peer copy on this path).", d, tdev, dev);
+            return 0;
+        }
+    }
+    if (o->written) memset(o->written, 0, fa_seq_nframes(s));
+    fa_seq_set_outputs(s, o->targets, sizeof(fiasco_amd_device_target), o->sse, o->maxdiff, o->written, o->stream);
+    return 1;
+}

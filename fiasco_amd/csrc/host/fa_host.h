@@ -193,6 +193,17 @@ typedef struct fa_dec_job {
     int             magnify;              /* in: decode at 2^magnify times the side length (dfiasco -m; intra frames; 0 = as coded).
                                            * out then has the size of fiasco_amd_magnified_size(); the test oracle does not know
                                            * the field and returns the coded size: callers check the size they get back */
+    /* Consumers on the device beside `out' (the outputs of a sequence, fiasco_amd_seq_set_outputs_device): behind the
+     * kernels of the job's flight the frame is written as 8-bit pixels and measured against its original, as the batch
+     * entries fiasco_amd_batch_decode_device() / _decode_distortion_device() do.  The test oracle does not know the
+     * fields and ignores them, as it does magnify: delivered stays 0 */
+    const void     *target;               /* in: a checked fiasco_amd_device_target on the device the job is decoded on (its
+                                           * data may be NULL: not written), or NULL */
+    unsigned long long *sse;              /* in: [3] result slots per band on the host, or NULL */
+    unsigned       *maxdiff;              /* in: [3], or NULL */
+    const fa_image *orig;                 /* in: the original the frame is measured against (sse or maxdiff given) */
+    void           *consumer_stream;      /* in: the caller's hipStream_t, as fiasco_amd_batch_decode_device() takes it */
+    int             delivered;            /* out: 1 once every consumer the job names has had the frame */
 } fa_dec_job;
 int  fa_core_decode_frames(unsigned n, fa_dec_job *jobs);    /* number of frames decoded */
 /* smoothing along the partition borders (smooth_image, codec/decoder.c:674-768; fa_batch_decode.c): the borders of a
@@ -349,6 +360,24 @@ int16_t *fa_compute_hits(unsigned from, unsigned to, unsigned n, const fa_wfa *w
 typedef struct fa_seq fa_seq;
 fa_seq *fa_seq_open(const fa_options *op, float quality, unsigned nframes, const unsigned char *const *bufs,
                     const size_t *lens, char const *const *names, unsigned rank, unsigned world);
+/* the same for frames that are images already (display order; no host planes needed: fa_image.src_dev): the sequence
+ * takes images[] and its entries over, also when it refuses them.  release(ctx) runs when the sequence goes -- whoever
+ * made the images gives back what their planes lie in (the host C names no core function) */
+fa_seq *fa_seq_open_images(const fa_options *op, float quality, unsigned nframes, fa_image **images,
+                           unsigned rank, unsigned world);
+void    fa_seq_on_free(fa_seq *s, void (*release)(void *ctx), void *ctx);
+/* where the searches deliver every reconstructed frame on the device (fa_dec_job's consumer fields): targets, an array
+ * of nframes structures of target_size bytes in display order which only the core reads, or NULL; sse, maxdiff
+ * [nframes][3] and written [nframes] on the host, or NULL; all borrowed.  Everything NULL: no outputs */
+void    fa_seq_set_outputs(fa_seq *s, const void *targets, size_t target_size, unsigned long long *sse, unsigned *maxdiff,
+                           unsigned char *written, void *stream);
+unsigned fa_seq_nframes(const fa_seq *s);
+void    fa_seq_size(const fa_seq *s, unsigned *width, unsigned *height, int *color);
+/* the handle of the C ABI around a sequence (takes s over; options == NULL: the defaults, made here) */
+fiasco_amd_seq_t *fa_seq_handle(fa_seq *s, fiasco_c_options_t *defaults);
+fa_seq *fa_seq_of_handle(const fiasco_amd_seq_t *q);
+unsigned fa_seq_display_of(const fa_seq *s, unsigned k);      /* display number of coded frame k */
+fa_image *fa_seq_image(const fa_seq *s, unsigned display);    /* fa_seq_open_images: the frame; else NULL */
 void    fa_seq_free(fa_seq *s);
 int     fa_seq_search(fa_seq *s, const unsigned *carry_in, const uint8_t *todo);
 int     fa_seq_probe(fa_seq *s, unsigned *level);

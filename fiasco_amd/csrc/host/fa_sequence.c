@@ -28,6 +28,7 @@
 #include <math.h>
 #include <time.h>
 #include "fa_host.h"
+#include "libfiasco_amd_video.h"
 
 /* developer aid: FIASCO_AMD_SEQ_TIMING=1 prints where a sweep spends its time (stderr) */
 static double seq_now(void)
@@ -47,6 +48,22 @@ struct fa_seq {
     const unsigned char *const *bufs;     /* raw PNM of every frame (display order), borrowed */
     const size_t *lens;
     char const *const *names;
+    /* frames that came as images (fa_seq_open_images), display order, owned; bufs is NULL then.  A search takes a frame
+     * as a copy of the descriptor: the planes stay where they are (fa_image.src_dev) */
+    fa_image **images;
+    void     (*release)(void *ctx);
+    void      *release_ctx;
+    /* fiasco_amd_seq_keep_reconstructed: the reconstruction of every frame a search decodes, by display number
+     * (bands * width * height int16 each), owned */
+    int        keep;
+    int16_t  **kept;
+    /* fa_seq_set_outputs: where the decoder delivers every reconstructed frame on the device, by display number */
+    struct {
+        int on;
+        const char *targets; size_t target_size;
+        unsigned long long *sse; unsigned *maxdiff; unsigned char *written;
+        void *stream;
+    } outp;
     int        color;
     unsigned   ncoded;                    /* frames in coding order */
     unsigned  *order;                     /* display number */
@@ -119,33 +136,92 @@ void fa_seq_free(fa_seq *s)
     if (!s) return;
     for (k = 0; s->wfa && k < s->ncoded; k++) fa_wfa_free(s->wfa[k]);
     fa_wfa_free(s->probe_wfa);
+    for (k = 0; s->kept && k < s->nframes; k++) free(s->kept[k]);
+    free(s->kept);
+    for (k = 0; s->images && k < s->nframes; k++) fa_image_free(s->images[k]);
+    free(s->images);
+    if (s->release) s->release(s->release_ctx);
     free(s->wfa); free(s->stats); free(s->order); free(s->type); free(s->isfut); free(s->gfirst);
     free(s->carry_used); free(s->carry_out); free(s->gdone); free(s->gfail); free(s->gerr);
     fa_info_free(&s->wi);
     free(s);
 }
 
+/* frame i of a sequence is fw x fh, colour model fc: the first one decides, the others have to agree */
+static int seq_same_kind(fa_seq *s, unsigned i, const char *name, unsigned fw, unsigned fh, int fc, unsigned *w, unsigned *h)
+{
+    if (i == 0) { *w = fw; *h = fh; s->color = fc; }
+    else if (fw != *w || fh != *h) {
+        fa_set_error("`%s': all images of a sequence have to be of the same size.", name);
+        return 0;
+    } else if (fc != s->color) {
+        fa_set_error("`%s': all images a sequence have to use the same color model.", name);
+        return 0;
+    }
+    return 1;
+}
+
+/* what a sequence of nframes frames of w x h needs, whatever its frames came as */
+static fa_seq *seq_open_rest(fa_seq *s, float quality, unsigned w, unsigned h);
+
 fa_seq *fa_seq_open(const fa_options *op, float quality, unsigned nframes, const unsigned char *const *bufs,
                     const size_t *lens, char const *const *names, unsigned rank, unsigned world)
 {
     fa_seq *s = (fa_seq *) calloc(1, sizeof *s);
     unsigned i, w = 0, h = 0;
-    int n;
     if (!s) { fa_set_error("Out of memory!"); return NULL; }
     s->op = op; s->nframes = nframes; s->bufs = bufs; s->lens = lens; s->names = names;
     s->rank = rank; s->world = world ? world : 1;
     for (i = 0; i < nframes; i++) {
         unsigned fw, fh; int fc; size_t off;
-        if (!fa_pnm_header(bufs[i], lens[i], names ? names[i] : "<memory>", &fw, &fh, &fc, &off)) goto bad;
-        if (i == 0) { w = fw; h = fh; s->color = fc; }
-        else if (fw != w || fh != h) {
-            fa_set_error("`%s': all images of a sequence have to be of the same size.", names ? names[i] : "<memory>");
-            goto bad;
-        } else if (fc != s->color) {
-            fa_set_error("`%s': all images a sequence have to use the same color model.", names ? names[i] : "<memory>");
-            goto bad;
-        }
+        if (!fa_pnm_header(bufs[i], lens[i], names ? names[i] : "<memory>", &fw, &fh, &fc, &off)
+            || !seq_same_kind(s, i, names ? names[i] : "<memory>", fw, fh, fc, &w, &h)) { fa_seq_free(s); return NULL; }
     }
+    return seq_open_rest(s, quality, w, h);
+}
+
+fa_seq *fa_seq_open_images(const fa_options *op, float quality, unsigned nframes, fa_image **images, unsigned rank, unsigned world)
+{
+    fa_seq *s = (fa_seq *) calloc(1, sizeof *s);
+    unsigned i, w = 0, h = 0;
+    if (!s) {
+        for (i = 0; images && i < nframes; i++) fa_image_free(images[i]);
+        free(images);
+        fa_set_error("Out of memory!");
+        return NULL;
+    }
+    s->op = op; s->nframes = nframes; s->images = images;
+    s->rank = rank; s->world = world ? world : 1;
+    for (i = 0; i < nframes; i++) {
+        char name[32];
+        snprintf(name, sizeof name, "<device frame %u>", i);
+        if (!seq_same_kind(s, i, name, images[i]->width, images[i]->height, images[i]->color != 0, &w, &h)) { fa_seq_free(s); return NULL; }
+    }
+    return seq_open_rest(s, quality, w, h);
+}
+
+void fa_seq_set_outputs(fa_seq *s, const void *targets, size_t target_size, unsigned long long *sse, unsigned *maxdiff,
+                        unsigned char *written, void *stream)
+{
+    s->outp.targets = (const char *) targets; s->outp.target_size = target_size;
+    s->outp.sse = sse; s->outp.maxdiff = maxdiff; s->outp.written = written; s->outp.stream = stream;
+    s->outp.on = targets || sse || maxdiff;
+}
+unsigned fa_seq_nframes(const fa_seq *s) { return s->nframes; }
+void fa_seq_size(const fa_seq *s, unsigned *width, unsigned *height, int *color)
+{
+    *width = s->wi.width; *height = s->wi.height; *color = s->color;
+}
+void fa_seq_on_free(fa_seq *s, void (*release)(void *ctx), void *ctx) { s->release = release; s->release_ctx = ctx; }
+unsigned fa_seq_display_of(const fa_seq *s, unsigned k) { return s->order[k]; }
+fa_image *fa_seq_image(const fa_seq *s, unsigned display) { return s->images && display < s->nframes ? s->images[display] : NULL; }
+
+static fa_seq *seq_open_rest(fa_seq *s, float quality, unsigned w, unsigned h)
+{
+    const fa_options *op = s->op;
+    const unsigned nframes = s->nframes;
+    unsigned i;
+    int n;
     if (!nframes) { fa_set_error("Can't open frame `%s'.", "<none>"); goto bad; }
     if (!fa_setup_params(op, quality, w, h, s->color, nframes, &s->wi, &s->cp)) goto bad;
     s->order = (unsigned *) calloc(nframes, sizeof *s->order);
@@ -167,7 +243,8 @@ fa_seq *fa_seq_open(const fa_options *op, float quality, unsigned nframes, const
     s->gdone = (uint8_t *) calloc(s->ngop, 1);
     s->gfail = (uint8_t *) calloc(s->ngop, 1);
     s->gerr = (char (*)[160]) calloc(s->ngop, sizeof *s->gerr);
-    if (!s->wfa || !s->stats || !s->carry_used || !s->carry_out || !s->gdone || !s->gfail || !s->gerr) {
+    s->kept = (int16_t **) calloc(nframes, sizeof *s->kept);
+    if (!s->wfa || !s->stats || !s->carry_used || !s->carry_out || !s->gdone || !s->gfail || !s->gerr || !s->kept) {
         fa_set_error("Out of memory!");
         goto bad;
     }
@@ -238,6 +315,39 @@ static void seq_dump_reconst(const char *dir, const fa_image *im, const fa_wfa *
     fclose(f);
 }
 
+/* The input of a search: display frame d as an image the caller frees.  PNM: parsed here; a frame that came as an
+ * image: a copy of its descriptor, which says where the planes are (src_dev) and has no host planes of its own */
+static fa_image *seq_input(const fa_seq *s, unsigned d)
+{
+    fa_image *im;
+    if (!s->images) return fa_image_from_pnm(s->bufs[d], s->lens[d], s->names ? s->names[d] : "<memory>");
+    im = (fa_image *) calloc(1, sizeof *im);
+    if (!im) { fa_set_error("Out of memory!"); return NULL; }
+    im->width = s->images[d]->width; im->height = s->images[d]->height; im->color = s->images[d]->color;
+    im->src_dev = s->images[d]->src_dev; im->src_dev_id = s->images[d]->src_dev_id; im->src_owner = s->images[d]->src_owner;
+    return im;
+}
+
+/* "Some consumer wants every frame reconstructed", not only the references of the frames to come: the tests' directory
+ * (videos, as ever), fiasco_amd_seq_keep_reconstructed and the device outputs (the frames of an all-intra sequence too) */
+static int seq_wants_every_frame(const fa_seq *s, int video)
+{
+    return s->keep || s->outp.on || (video && fa_knob("FIASCO_AMD_SEQ_RECONST_DIR"));
+}
+
+/* keep: the planes of coded frame k as the decoder left them on the host */
+static int seq_keep_planes(fa_seq *s, unsigned k, const fa_image *im)
+{
+    const size_t n = (size_t) im->width * im->height;
+    const unsigned d = s->order[k];
+    int band;
+    free(s->kept[d]);
+    s->kept[d] = (int16_t *) malloc(n * (s->color ? 3 : 1) * sizeof(int16_t));
+    if (!s->kept[d]) return 0;
+    for (band = 0; band < (s->color ? 3 : 1); band++) memcpy(s->kept[d] + n * band, im->pixels[band], n * sizeof(int16_t));
+    return 1;
+}
+
 /* per-GOP running state of a sweep */
 typedef struct gop_run {
     unsigned g, pos, n;                    /* GOP, next frame inside it, frames */
@@ -265,7 +375,7 @@ static void parse_share(void *ctx, unsigned t, unsigned nt)
         p->pre[r].im = NULL; p->pre[r].err[0] = 0;
         if (q->dead || p->step >= q->n) continue;
         k = s->gfirst[q->g] + p->step;
-        p->pre[r].im = fa_image_from_pnm(s->bufs[s->order[k]], s->lens[s->order[k]], s->names ? s->names[s->order[k]] : "<memory>");
+        p->pre[r].im = seq_input(s, s->order[k]);
         if (!p->pre[r].im) snprintf(p->pre[r].err, sizeof p->pre[r].err, "%s", fiasco_get_error_message());   /* this thread's message */
     }
 }
@@ -291,7 +401,11 @@ int fa_seq_search(fa_seq *s, const unsigned *carry_in, const uint8_t *todo)
     for (g = 0; g < s->ngop; g++) {
         unsigned k;
         if (!fa_seq_is_mine(s, g) || !todo[g]) continue;
-        for (k = s->gfirst[g]; k < s->gfirst[g + 1]; k++) { fa_wfa_free(s->wfa[k]); s->wfa[k] = NULL; }
+        for (k = s->gfirst[g]; k < s->gfirst[g + 1]; k++) {
+            fa_wfa_free(s->wfa[k]); s->wfa[k] = NULL;
+            free(s->kept[s->order[k]]); s->kept[s->order[k]] = NULL;
+            if (s->outp.written) s->outp.written[s->order[k]] = 0;
+        }
         run[nrun].g = g; run[nrun].n = s->gfirst[g + 1] - s->gfirst[g]; run[nrun].carry = carry_in[g];
         s->carry_used[g] = carry_in[g]; s->gdone[g] = 0; s->gfail[g] = 0; s->gerr[g][0] = 0;
         if (run[nrun].n > maxlen) maxlen = run[nrun].n;
@@ -391,9 +505,9 @@ int fa_seq_search(fa_seq *s, const unsigned *carry_in, const uint8_t *todo)
                 q->carry = jobs[b].lc_min_level_out;
                 /* reference for the frames to come (:647-651); tests that dump the planes want every frame, as the
                  * reference decodes every frame it codes, the last of a GOP included */
-                need[b] = video && (step + 1 < q->n || fa_knob("FIASCO_AMD_SEQ_RECONST_DIR"));
+                need[b] = (video && step + 1 < q->n) || seq_wants_every_frame(s, video);
             }
-            fa_image_free(ims[b]); ims[b] = NULL;
+            /* (the step's image lives until its decode is over: the original the frame is measured against) */
         }
         /* the references of the frames to come (codec/coder.c:647-651): decode_image + restore_mc, one batch for
          * the core -- the device, which keeps the planes for the next search (fa_image.dev) */
@@ -410,12 +524,22 @@ int fa_seq_search(fa_seq *s, const unsigned *carry_in, const uint8_t *todo)
                 djobs[b].wfa = s->wfa[k]; djobs[b].width = s->wi.width; djobs[b].height = s->wi.height;
                 djobs[b].color = s->color; djobs[b].frame_type = s->type[k];
                 djobs[b].past = q->past; djobs[b].future = q->future; djobs[b].p_max_level = s->wi.p_max_level;
+                if (s->outp.on) {
+                    const unsigned d = s->order[k];
+                    djobs[b].target = s->outp.targets ? s->outp.targets + (size_t) d * s->outp.target_size : NULL;
+                    djobs[b].sse = s->outp.sse ? s->outp.sse + (size_t) d * 3 : NULL;
+                    djobs[b].maxdiff = s->outp.maxdiff ? s->outp.maxdiff + (size_t) d * 3 : NULL;
+                    djobs[b].orig = ims[b];
+                    djobs[b].consumer_stream = s->outp.stream;
+                }
             }
             if (any) (void) fa_core_decode_frames(nb, djobs);
+            for (b = 0; b < nb; b++) { fa_image_free(ims[b]); ims[b] = NULL; }
             for (b = 0; b < nb; b++) {
                 gop_run *q = &run[who[b]];
                 if (!need[b]) continue;
                 q->reconst = djobs[b].out;
+                if (q->reconst && djobs[b].delivered && s->outp.written) s->outp.written[s->order[s->gfirst[q->g] + step]] = 1;
                 if (q->reconst && fa_knob("FIASCO_AMD_SEQ_RECONST_LOG")) {
                     /* tests: one line per reconstructed frame (GOP, step, FNV-1a of its planes) -- the device decoder
                      * against the host restatement on P and B frames */
@@ -437,6 +561,10 @@ int fa_seq_search(fa_seq *s, const unsigned *carry_in, const uint8_t *todo)
                     seq_dump_reconst(fa_knob("FIASCO_AMD_SEQ_RECONST_DIR"), q->reconst, s->wfa[k], s->order[k], s->type[k],
                                      s->color, s->wi.p_max_level);
                 }
+                if (q->reconst && s->keep && !seq_keep_planes(s, s->gfirst[q->g] + step, q->reconst)) {
+                    snprintf(djobs[b].errmsg, sizeof djobs[b].errmsg, "Out of memory!");
+                    fa_image_free(q->reconst); q->reconst = NULL;
+                }
                 if (!q->reconst) {
                     snprintf(s->gerr[q->g], 160, "%s", djobs[b].errmsg[0] ? djobs[b].errmsg : "decoder failed");
                     s->gfail[q->g] = 1; q->dead = 1;
@@ -449,8 +577,11 @@ int fa_seq_search(fa_seq *s, const unsigned *carry_in, const uint8_t *todo)
         fprintf(stderr, "fa_seq_search: %u GOPs, %u steps: prepare %.2f s, core %.2f s, decode %.2f s\n",
                 nrun, maxlen, t_prep, t_core, t_dec);
     for (r = 0; r < nrun; r++) {
+        unsigned k;
         s->carry_out[run[r].g] = run[r].carry;
         s->gdone[run[r].g] = 1;
+        for (k = s->gfirst[run[r].g]; s->gfail[run[r].g] && s->outp.written && k < s->gfirst[run[r].g + 1]; k++)
+            s->outp.written[s->order[k]] = 0;
     }
     rc = 1;
 out:
@@ -471,7 +602,7 @@ int fa_seq_probe(fa_seq *s, unsigned *level)
     int ok;
     *level = s->cp.lc_min_level;
     if (!s->color || s->ngop < 2) return 1;
-    im = fa_image_from_pnm(s->bufs[s->order[0]], s->lens[s->order[0]], s->names ? s->names[s->order[0]] : "<memory>");
+    im = seq_input(s, s->order[0]);
     if (!im) return 0;
     memset(&job, 0, sizeof job);
     job.image = im; job.cp = s->cp; job.frame_type = FA_I_FRAME;
@@ -635,6 +766,15 @@ fiasco_amd_seq_t *fiasco_amd_seq_open(unsigned n, const unsigned char *const *pn
     return q;
 }
 
+fiasco_amd_seq_t *fa_seq_handle(fa_seq *s, fiasco_c_options_t *defaults)
+{
+    fiasco_amd_seq_t *q = (fiasco_amd_seq_t *) calloc(1, sizeof *q);
+    if (!q) { fa_set_error("Out of memory!"); return NULL; }
+    q->s = s; q->defaults = defaults;
+    return q;
+}
+fa_seq *fa_seq_of_handle(const fiasco_amd_seq_t *q) { return q ? q->s : NULL; }
+
 void fiasco_amd_seq_free(fiasco_amd_seq_t *q)
 {
     if (!q) return;
@@ -690,4 +830,58 @@ int fiasco_amd_seq_write(fiasco_amd_seq_t *q, unsigned frame, const unsigned cha
     }
     fa_bw_free(&bw);
     return ok;
+}
+
+/* fa_seq_encode_all behind the C ABI: probe, search, verify, write; the whole stream, header included */
+int fiasco_amd_seq_encode(fiasco_amd_seq_t *q, unsigned char **out, size_t *out_len)
+{
+    fa_bitw bw;
+    int ok;
+    if (!out || !out_len) { fa_set_error("fiasco_amd_seq_encode: no place for the stream"); return 0; }
+    *out = NULL; *out_len = 0;
+    if (!q) { fa_set_error("fiasco_amd_seq_encode: no sequence"); return 0; }
+    if (q->s->world != 1) {
+        fa_set_error("fiasco_amd_seq_encode: rank %d of %d: one process codes the whole stream (world == 1); "
+                     "several ranks exchange their results through fiasco_amd_seq_search / _write", (int) q->s->rank, (int) q->s->world);
+        return 0;
+    }
+    fa_bw_init(&bw);
+    ok = fa_seq_encode_all(q->s, &bw, NULL);
+    if (ok) {
+        *out_len = fa_bw_finish(&bw);
+        *out = (unsigned char *) malloc(*out_len ? *out_len : 1);
+        if (*out) memcpy(*out, bw.buf, *out_len); else { fa_set_error("Out of memory!"); *out_len = 0; ok = 0; }
+    }
+    fa_bw_free(&bw);
+    return ok;
+}
+
+int fiasco_amd_seq_keep_reconstructed(fiasco_amd_seq_t *q, int keep)
+{
+    unsigned d;
+    if (!q) { fa_set_error("fiasco_amd_seq_keep_reconstructed: no sequence"); return 0; }
+    q->s->keep = keep != 0;
+    for (d = 0; !keep && d < q->s->nframes; d++) { free(q->s->kept[d]); q->s->kept[d] = NULL; }
+    return 1;
+}
+
+int fiasco_amd_seq_reconstructed_planes(const fiasco_amd_seq_t *q, unsigned display, int16_t *out, int *frame_type)
+{
+    const fa_seq *s = q ? q->s : NULL;
+    unsigned k;
+    if (!s || !out) { fa_set_error("fiasco_amd_seq_reconstructed_planes: no sequence or no place for the planes"); return 0; }
+    if (display >= s->nframes) { fa_set_error("fiasco_amd_seq_reconstructed_planes: no frame %u (the sequence has %u)", display, s->nframes); return 0; }
+    if (!s->keep) {
+        fa_set_error("fiasco_amd_seq_reconstructed_planes: reconstructed frames are not kept "
+                     "(fiasco_amd_seq_keep_reconstructed(seq, 1) before the search)");
+        return 0;
+    }
+    if (!s->kept[display]) {
+        fa_set_error("fiasco_amd_seq_reconstructed_planes: frame %u has not been reconstructed by this process "
+                     "(its group of pictures was not searched here, or the search failed)", display);
+        return 0;
+    }
+    memcpy(out, s->kept[display], (size_t) s->wi.width * s->wi.height * (s->color ? 3 : 1) * sizeof(int16_t));
+    for (k = 0; frame_type && k < s->ncoded; k++) if (s->order[k] == display) *frame_type = s->type[k];
+    return 1;
 }

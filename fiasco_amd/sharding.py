@@ -57,9 +57,42 @@ def encode_sequence(lib, pnm_list, quality=20.0, options=None, device="cpu", gro
     The byte strings of the frames are then gathered like independent frames (gather_streams) and
     put together in coding order.  Returns the .fco bytes on every rank."""
     import fiasco_amd
+    rank, world = _rank_world(group)
+    return _drive_sequence(fiasco_amd.Sequence(lib, pnm_list, quality, options, rank, world), device, group)
+
+
+def encode_sequence_device(lib, frames, quality=20.0, options=None, device="cpu", group=None, targets=None, distortion=False,
+                           stream=None):
+    """encode_sequence for a video whose frames already live in device memory (fiasco_amd.Sequence.from_device: every
+    rank passes all frames in display order and converts the ones of its own groups of pictures).  targets, distortion:
+    Sequence.set_outputs -- every reconstructed frame of this rank's GOPs as 8-bit pixels into targets[display] and its
+    exact distortion.  Returns the .fco bytes on every rank; with outputs (stream, (sse, maxdiff, written)) as
+    Sequence.distortion gives them: the rows of this rank's frames."""
+    import fiasco_amd
+    rank, world = _rank_world(group)
+    seq = fiasco_amd.Sequence.from_device(lib, frames, quality, options, rank, world, stream)
+    outputs = targets is not None or distortion
+    try:
+        if outputs:
+            seq.set_outputs(targets, distortion, stream)
+    except fiasco_amd.FiascoError:
+        seq.free()
+        raise
+    result = {}
+    data = _drive_sequence(seq, device, group, (lambda s: result.update(d=s.distortion())) if outputs else None)
+    return (data, result["d"]) if outputs else data
+
+
+def _rank_world(group):
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
-    rank = dist.get_rank(group) if world > 1 else 0
-    seq = fiasco_amd.Sequence(lib, pnm_list, quality, options, rank, world)
+    return (dist.get_rank(group) if world > 1 else 0), world
+
+
+def _drive_sequence(seq, device, group, before_free=None):
+    """The driver of encode_sequence on a ready Sequence (freed here).  before_free(seq): what the caller still wants of
+    it once the searches are over."""
+    import fiasco_amd
+    rank, world = seq.rank, seq.world
     # An error on ONE rank (out of HBM, a HIP error on its GPU ...) must not leave the others
     # blocked in the next collective: local errors are caught, folded into the tensor that is
     # reduced anyway (one extra row / element), and every rank raises together after the reduce.
@@ -133,6 +166,8 @@ def encode_sequence(lib, pnm_list, quality=20.0, options=None, device="cpu", gro
             local = {k: seq.write(k, resolved.get(k)) for k in range(K) if seq.gop_of(k) % world == rank}
         except fiasco_amd.FiascoError as e:
             local_err = str(e)
+        if before_free is not None and local_err is None:
+            before_free(seq)
     finally:
         seq.free()
     if world == 1:

@@ -230,6 +230,7 @@ int      fiasco_amd_seq_gop_result(const fiasco_amd_seq_t *seq, unsigned gop, un
 const unsigned char *fiasco_amd_seq_ycol(const fiasco_amd_seq_t *seq, unsigned frame);
 int      fiasco_amd_seq_write(fiasco_amd_seq_t *seq, unsigned frame, const unsigned char *ycol,
                               unsigned char **out, size_t *out_len);
+/* one call for the whole stream, and the reconstructed frames of a video on the host: libfiasco_amd_video.h */
 
 #ifdef __cplusplus
 }

@@ -140,7 +140,7 @@ int fiasco_amd_device_count(void);                      /* shares a batch is spl
  * converts its own frames on its own device (a source on another device is fetched over the peer link first).
  * fiasco_amd_batch_input_planes(): the planes the coder sees for frame i, all bands back to back (width * height
  * int16 each, 12.4 fixed point), for PNM-fed and device-fed batches.  The decoded-PSNR calls fetch the original the
- * same way when a frame has no host copy.  Videos (fiasco_amd_seq_*, fiasco_coder()) take PNM only. */
+ * same way when a frame has no host copy.  Videos: fiasco_amd_seq_open_device() (libfiasco_amd_video.h); fiasco_coder() takes file names. */
 enum { FIASCO_AMD_GRAY8 = 0, FIASCO_AMD_RGB8_INTERLEAVED = 1, FIASCO_AMD_RGB8_PLANAR = 2 };
 typedef struct fiasco_amd_device_frame {
     const void *data;        /* device memory */
