@@ -30,6 +30,7 @@
 #include <sys/stat.h>
 #include <sys/types.h>
 #include <algorithm>
+#include <atomic>
 #include <string>
 #include <utility>
 #include <vector>
@@ -56,29 +57,8 @@ static long long knob_int(const char *name, long long d)
 }
 
 /* ------------------------------------------------------------------ per-device state
- *
- * Everything the launcher keeps between calls belongs to ONE device: the pool of slabs, the log2
- * correction table, the counters.  A process that encodes on one device (the default on a 1-GPU box, a
- * rank of the multi-process harness after fiasco_amd_set_device()) uses the state below from whatever thread
- * calls in: it is the state of share 0, the first of the list that shares.inc keeps.  The multi-device entries
- * there give every further device a DevState of its own and run its share of a batch on a host thread whose
- * t_dev points there. */
-struct PoolEntry { char *base; size_t bytes; int device; };   /* device: where hipMalloc gave the slab out (checked on every acquire) */
-struct Log2Patch { unsigned *d_keys = nullptr; double *d_vals = nullptr; unsigned mask = 0; int device = -1;
-                   unsigned long long entries = 0; bool tried = false, ok = false; };
-struct DevState {
-    fiasco_amd_stats stats;
-    std::vector<PoolEntry> free;
-    Log2Patch l2;
-    char l2_err[200];
-    DevState() { memset(&stats, 0, sizeof stats); l2_err[0] = 0; }
-};
-static DevState g_state0;
-static thread_local DevState *t_dev = &g_state0;
-#define g_stats  (t_dev->stats)
-#define g_free   (t_dev->free)
-#define g_l2     (t_dev->l2)
-#define g_l2_err (t_dev->l2_err)
+ * DevState, the state of share 0 (g_state0), the calling thread's share (t_dev) and the lock every share has */
+#include "dev_state.h"
 
 /* the kernel builds (frame_coder.hip, one object per build: Makefile FC_BUILDS) */
 typedef void launch_fn(DevFrame *d_frames, unsigned n, unsigned nlend, unsigned long long *ring, unsigned *ctr,

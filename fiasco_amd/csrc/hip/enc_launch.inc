@@ -102,16 +102,18 @@ static int collect(Staged *S, FrameSlot &fs, const char *pinned)
     }
     job->lc_min_level_out = (unsigned) F.lc_min_out;
     job->status = 1;
-    g_stats.frames += 1;
-    g_stats.bytes_mp += F.bytes_mp; g_stats.bytes_img += F.bytes_img; g_stats.bytes_gram += F.bytes_gram;
-    g_stats.n_mp += F.n_mp; g_stats.n_steps += F.n_steps; g_stats.n_blocks += F.n_blocks;
-    g_stats.n_appends += F.n_appends; g_stats.n_fulleval += F.n_fulleval;
-    g_stats.t_init += F.t_init; g_stats.t_approx += F.t_approx; g_stats.t_ipis += F.t_ipis;
-    g_stats.t_append += F.t_append; g_stats.t_serial += F.t_serial; g_stats.t_total += F.t_total;
-    g_stats.t_mpA += F.t_mpA; g_stats.t_mpB += F.t_mpB; g_stats.n_blockevals += F.n_blockevals;
-    for (int k = 0; k < 8; k++) g_stats.dbg[k] += F.dbg[k];
-    g_stats.states_sum += ns;
-    if (ns > g_stats.states_max) g_stats.states_max = ns;
+    stats_update([&](fiasco_amd_stats &st) {
+        st.frames += 1;
+        st.bytes_mp += F.bytes_mp; st.bytes_img += F.bytes_img; st.bytes_gram += F.bytes_gram;
+        st.n_mp += F.n_mp; st.n_steps += F.n_steps; st.n_blocks += F.n_blocks;
+        st.n_appends += F.n_appends; st.n_fulleval += F.n_fulleval;
+        st.t_init += F.t_init; st.t_approx += F.t_approx; st.t_ipis += F.t_ipis;
+        st.t_append += F.t_append; st.t_serial += F.t_serial; st.t_total += F.t_total;
+        st.t_mpA += F.t_mpA; st.t_mpB += F.t_mpB; st.n_blockevals += F.n_blockevals;
+        for (int k = 0; k < 8; k++) st.dbg[k] += F.dbg[k];
+        st.states_sum += ns;
+        if (ns > st.states_max) st.states_max = ns;
+    });
     cap_hint_put(job, F.ystates_out, F.states);
     if (fa_knob("FIASCO_AMD_CAP_TRACE"))
         fprintf(stderr, "capacity: frame type %d used %d table states of %d, %d states of %d; %.3f s on the device\n", job->frame_type,
@@ -172,8 +174,11 @@ static bool order_batch(Staged *S, WaveGroups &g)
         key[k] = 3 * b + part;
         g.n[b]++;
         if (part == 0) g.lend[b]++; else if (part == 1) g.borrow[b]++;
-        if (k_build[b].stats_slot >= 0) g_stats.frames_by_build[k_build[b].stats_slot]++; else g_stats.spec_frames++;
     }
+    stats_update([&](fiasco_amd_stats &st) {
+        for (int b = 0; b < N_BUILDS; b++)
+            if (k_build[b].stats_slot >= 0) st.frames_by_build[k_build[b].stats_slot] += g.n[b]; else st.spec_frames += g.n[b];
+    });
     std::stable_sort(batch.begin(), batch.end(), [&](size_t a, size_t b) { return key[a] < key[b]; });
     return true;
 }
@@ -362,7 +367,7 @@ static unsigned setup_coop(Staged *S, Build b, size_t at, size_t plain, bool &fa
     hdr.minsub = 1;
     for (size_t i = at; i < at + plain && !fail; i++)
         fail = hipMemcpyAsync(hf[i].coop, &hdr, sizeof(FcCoop), hipMemcpyHostToDevice, S->stream) != hipSuccess;
-    g_stats.coop_frames += plain; g_stats.coop_workgroups = W;
+    stats_update([&](fiasco_amd_stats &st) { st.coop_frames += plain; st.coop_workgroups = W; });
     return W;
 }
 
@@ -445,8 +450,7 @@ static bool download_wave(Staged *S)
     if (!fail) {
         float ms = 0;
         if (hipEventElapsedTime(&ms, S->ev0, S->ev1) == hipSuccess) {
-            g_stats.kernel_ms += ms;
-            g_stats.launches += 1;
+            stats_update([&](fiasco_amd_stats &st) { st.kernel_ms += ms; st.launches += 1; });
         }
         fail = hipMemcpy(hf.data(), S->d_frames, sizeof(DevFrame) * S->batch.size(),
                          hipMemcpyDeviceToHost) != hipSuccess;
@@ -455,14 +459,16 @@ static bool download_wave(Staged *S)
         std::vector<FcSpecCtl> ctl(S->spec_frames.size());
         if (hipMemcpy2D(ctl.data(), sizeof(FcSpecCtl), S->d_spec, S->spec_ctl_span, sizeof(FcSpecCtl), ctl.size(),
                         hipMemcpyDeviceToHost) == hipSuccess)
-            for (size_t i = 0; i < ctl.size(); i++) {
-                g_stats.spec_tasks += ctl[i].n_tasks; g_stats.spec_confirmed += ctl[i].n_confirmed;
-                g_stats.spec_wrong += ctl[i].n_wrong; g_stats.spec_timeout += ctl[i].n_timeout;
-                g_stats.spec_inline += ctl[i].n_inline; g_stats.spec_wait += ctl[i].t_wait;
-                g_stats.spec_tab_used += ctl[i].n_tab_used; g_stats.spec_tab_missed += ctl[i].n_tab_missed;
-                g_stats.spec_adopted += ctl[i].n_adopted;
-                g_stats.spec_app_rows += ctl[i].n_app_dealt; g_stats.spec_app_wait += ctl[i].t_app_wait;
-            }
+            stats_update([&](fiasco_amd_stats &st) {
+                for (size_t i = 0; i < ctl.size(); i++) {
+                    st.spec_tasks += ctl[i].n_tasks; st.spec_confirmed += ctl[i].n_confirmed;
+                    st.spec_wrong += ctl[i].n_wrong; st.spec_timeout += ctl[i].n_timeout;
+                    st.spec_inline += ctl[i].n_inline; st.spec_wait += ctl[i].t_wait;
+                    st.spec_tab_used += ctl[i].n_tab_used; st.spec_tab_missed += ctl[i].n_tab_missed;
+                    st.spec_adopted += ctl[i].n_adopted;
+                    st.spec_app_rows += ctl[i].n_app_dealt; st.spec_app_wait += ctl[i].t_app_wait;
+                }
+            });
         else (void) hipGetLastError();
     }
     const char *trace_path = fa_knob("FIASCO_AMD_TRACE");
@@ -537,7 +543,7 @@ static void frame_outcome(Staged *S, size_t b, size_t off)
      * workgroup with all of it, like the reference would, before "Maximum number of states" is said) */
     if (st == FC_ERR_CAPACITY && ((size_t) fs.P < cap || (size_t) fs.PA < cap || fs.spec)) {
         /* capacity guess too small: bigger slab, same inputs, encode again */
-        g_stats.reencodes += 1;
+        stats_update([](fiasco_amd_stats &st) { st.reencodes += 1; });
         size_t np = align_up((size_t) fs.P + (size_t) fs.P / 2, 64);
         size_t npa = align_up((size_t) fs.PA + (size_t) fs.PA / 2, 64);
         if ((size_t) fs.P >= cap || np >= cap) fs.spec = false;
@@ -545,7 +551,7 @@ static void frame_outcome(Staged *S, size_t b, size_t off)
          * back in the 1024-thread speculating build, one workgroup per CU: its verifiers might not be
          * resident (the chain's waits are bounded, but slow) -- one workgroup for such a frame */
         if (np > 3072 && S->specG > 1 && (size_t) S->specG * S->n > (size_t) S->ncu) fs.spec = false;
-        if (fs.base) slab_release(fs.base, fs.bytes);
+        if (fs.base) slab_release(fs.base, fs.bytes, fs.slab_dev);
         /* a borrower gets a slab of its own; its pixel planes stay where they are (the queue's
          * pixel buffer or an upload buffer): the host copy may belong to the next pass by now */
         if (fs.borrow) { fs.borrow = false; S->borrowers--; }
@@ -676,7 +682,7 @@ static int core1_finish2(void *h, int resubmit)
         if (!pending) break;
         for (size_t k = 0; k < S->slots.size(); k++) {
             FrameSlot &fs = S->slots[k];
-            if (fs.done && fs.base) { slab_release(fs.base, fs.bytes); fs.base = nullptr; fs.staged = false; }
+            if (fs.done && fs.base) { slab_release(fs.base, fs.bytes, fs.slab_dev); fs.base = nullptr; fs.staged = false; }
         }
         for (size_t k = 0; k < S->slots.size(); k++) {
             FrameSlot &fs = S->slots[k];

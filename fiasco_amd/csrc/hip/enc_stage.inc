@@ -10,6 +10,7 @@ struct FrameSlot {
     int      job;            /* index into jobs[] */
     char    *base = nullptr;
     size_t   bytes = 0;
+    int      slab_dev = -1;  /* the device that allocated the slab: goes back to the pool with it */
     int      P = 0, PA = 0;
     int      floorP = 0, floorPA = 0;   /* what frames of this kind needed before (capacity memory) */
     Layout   L;
@@ -129,14 +130,16 @@ static Build build_of(const Staged *S, const FrameSlot &fs, bool few)
  * counts as the plain build of its width */
 static size_t frames_per_cu(const FrameSlot &fs)
 {
-    static int cache[N_BUILDS];
+    static std::atomic<int> cache[N_BUILDS];      /* 0: not asked yet; two threads that ask at once store the same answer */
     const Build b = fs.gm ? B_BIG_GM : fs.hm ? B_BIG_HM
                   : (Build) ((fs.big ? B_BIG : B_DEFAULT) + (fs.P > 12 * 256 || fs.wide_only ? 1 : 0));
-    if (!cache[b]) {
-        cache[b] = k_build[b].occupancy();
-        if (cache[b] < 1) cache[b] = 1;
+    int occ = cache[b].load(std::memory_order_relaxed);
+    if (!occ) {
+        occ = k_build[b].occupancy();
+        if (occ < 1) occ = 1;
+        cache[b].store(occ, std::memory_order_relaxed);
     }
-    return (size_t) cache[b];
+    return (size_t) occ;
 }
 
 static inline const fa_image *slot_image(const Staged *S, const FrameSlot &fs)
@@ -366,7 +369,7 @@ static int stage_slot(Staged *S, FrameSlot &fs)
     const size_t npix = (size_t) job->image->width * job->image->height;
     const int bands = job->image->color ? 3 : 1;
     slot_layout(S, fs);
-    fs.base = slab_acquire(fs.L.total, &fs.bytes);
+    fs.base = slab_acquire(fs.L.total, &fs.bytes, &fs.slab_dev);
     /* developer aid: FIASCO_AMD_POISON=<byte> fills the slab first -- the kernel must write every
      * cell before it reads it, whatever an earlier frame left there */
     if (fs.base && fa_knob("FIASCO_AMD_POISON"))
@@ -377,7 +380,7 @@ static int stage_slot(Staged *S, FrameSlot &fs)
     }
     auto give_up = [&](const char *msg) {
         snprintf(job->errmsg, sizeof job->errmsg, "%s", msg);
-        slab_release(fs.base, fs.bytes); fs.base = nullptr;
+        slab_release(fs.base, fs.bytes, fs.slab_dev); fs.base = nullptr;
         return 0;
     };
     fill_frame(fs, job);
@@ -388,7 +391,7 @@ static int stage_slot(Staged *S, FrameSlot &fs)
         || fs.F.ML > 26) {
         snprintf(job->errmsg, sizeof job->errmsg,
                  "coefficient model too large for the device coder (levels x mantissa symbols > %d)", hmx ? FC_MAXCOEFF_HM : FC_MAXCOEFF_BIG_STD);
-        slab_release(fs.base, fs.bytes); fs.base = nullptr;
+        slab_release(fs.base, fs.bytes, fs.slab_dev); fs.base = nullptr;
         fs.done = true; fs.rejected = true;      /* permanent: not a matter of free HBM */
         return 0;
     }
@@ -445,7 +448,7 @@ static void core1_unstage(void *h)
         if (S->d_trace) (void) hipFree(S->d_trace);
     }
     for (size_t k = 0; k < S->slots.size(); k++)
-        if (S->slots[k].base) slab_release(S->slots[k].base, S->slots[k].bytes);
+        if (S->slots[k].base) slab_release(S->slots[k].base, S->slots[k].bytes, S->slots[k].slab_dev);
     for (void *p : std::initializer_list<void *>{ S->d_frames, S->qpix, S->d_ring, S->d_queue, S->d_ptrmask, S->d_vframes, S->d_spec })
         if (p) (void) hipFree(p);
     if (S->cstream) { (void) hipStreamSynchronize(S->cstream); (void) hipStreamDestroy(S->cstream); }
@@ -525,8 +528,8 @@ static void fit_hbm(Staged *S)
 {
     FrameSlot probe = S->slots[0];
     slot_layout(S, probe);
-    size_t free_b = 0, total_b = 0, pooled = 0;
-    for (size_t i = 0; i < g_free.size(); i++) pooled += g_free[i].bytes;
+    size_t free_b = 0, total_b = 0;
+    const size_t pooled = pool_bytes();
     size_t want = S->slots.size();
     const size_t resident = (size_t) S->ncu * frames_per_cu(probe);
     if (want > resident) want = resident;
@@ -619,12 +622,13 @@ static void *core1_stage(unsigned n, fa_job *jobs, const fiasco_amd_device_frame
                      "libfiasco_amd: no HIP device available (the hot path has no CPU fallback)");
         return S;
     }
-    if (!log2_patch_build()) {               /* once per process and device */
+    char l2_why[200];
+    if (!log2_patch_build(l2_why, sizeof l2_why)) {      /* built once per share and device, whoever comes first */
         /* frames coded without it could differ from the reference's: fail them, loudly */
         for (unsigned i = 0; i < n; i++)
             snprintf(jobs[i].errmsg, sizeof jobs[i].errmsg,
                      "libfiasco_amd: no log2 correction table, streams could differ from the reference's "
-                     "(FIASCO_AMD_NO_LOG2_TABLE=1 encodes without it): %s", g_l2_err);
+                     "(FIASCO_AMD_NO_LOG2_TABLE=1 encodes without it): %s", l2_why);
         return S;                             /* S->ok stays false: nothing of this batch runs */
     }
     {

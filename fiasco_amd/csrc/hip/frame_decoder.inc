@@ -444,12 +444,9 @@ static void dec_flight_fail(DecShare &S, DecFlight &F, const char *msg)
     F.alive.clear();
 }
 
-static pthread_mutex_t g_dec_stats_lock = PTHREAD_MUTEX_INITIALIZER;
 static void dec_account(unsigned long long us, unsigned frames, unsigned long long bytes)
 {
-    pthread_mutex_lock(&g_dec_stats_lock);
-    g_stats.decoder_us += us; g_stats.decoder_frames += frames; g_stats.decoder_bytes += bytes;
-    pthread_mutex_unlock(&g_dec_stats_lock);
+    stats_update([&](fiasco_amd_stats &st) { st.decoder_us += us; st.decoder_frames += frames; st.decoder_bytes += bytes; });
 }
 
 /* a frame that gets a thumbnail beside it: the level shown is the frame's less twice the reduction, which the level

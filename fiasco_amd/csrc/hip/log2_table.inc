@@ -52,8 +52,8 @@ static void l2_share(void *ctx, unsigned t, unsigned nt)
 }
 
 /* the table of host log2 values the kernels use (DevFrame.l2_*), per process */
-static unsigned long long g_l2_max_ulp;      /* largest distance seen by the last comparisons, in ulps */
-extern "C" unsigned long long fiasco_amd_selftest_log2_max_ulp(void) { return g_l2_max_ulp; }
+static std::atomic<unsigned long long> g_l2_max_ulp(0);      /* largest distance seen by the comparisons of the process, in ulps */
+extern "C" unsigned long long fiasco_amd_selftest_log2_max_ulp(void) { return g_l2_max_ulp.load(); }
 
 /* compare over the floats with biased exponent in [exp_lo, exp_hi]; with `use_table` the device
  * side goes through the patch table like the frame kernel does; `collect` gathers the
@@ -91,7 +91,8 @@ static int log2_compare(unsigned exp_lo, unsigned exp_hi, bool use_table, unsign
         fa_fan_out(NT, l2_share, task);
         for (unsigned t = 0; t < NT; t++) {
             dd += task[t].dd;
-            if (task[t].max_ulp > g_l2_max_ulp) g_l2_max_ulp = task[t].max_ulp;
+            for (unsigned long long seen = g_l2_max_ulp.load(); task[t].max_ulp > seen; )       /* table builds of two shares may meet here */
+                if (g_l2_max_ulp.compare_exchange_weak(seen, task[t].max_ulp)) break;
             if (task[t].df && !df) bad = task[t].bad;
             df += task[t].df;
             if (collect) collect->insert(collect->end(), part[t].begin(), part[t].end());
@@ -122,10 +123,12 @@ extern "C" int fiasco_amd_selftest_log2(unsigned exp_lo, unsigned exp_hi, unsign
  * name that carries the host libm's and the device's answers to a few probe arguments.  A cache file is
  * taken only if its checksum fits and EVERY stored value is what this host's log2 computes now.
  *
- * Returns false -- with the reason in g_l2_err -- when the table is needed but could not be built or
+ * log2_patch_build() returns false -- with the reason in err -- when the table is needed but could not be built or
  * brought onto the device: 1 018 853 arguments differ between ocml and glibc, frames coded without
  * the table could differ from the reference's streams, so fa_core_stage() fails them instead
- * (FIASCO_AMD_NO_LOG2_TABLE=1 runs without the table on purpose). */
+ * (FIASCO_AMD_NO_LOG2_TABLE=1 runs without the table on purpose).  It is called by every staging call of every
+ * thread: l2_once() (dev_state.h) lets ONE of them run log2_patch_fill() per share and device, the others wait for it
+ * and leave with its answer -- a failure stays one, with the builder's reason, until the share meets another device. */
 
 static unsigned long long fnv64(const void *p, size_t n, unsigned long long h = 1469598103934665603ull)
 {
@@ -155,18 +158,12 @@ static void l2_cache_dir(char *out, size_t n)
     if (access(out, W_OK) != 0) snprintf(out, n, "/tmp");
 }
 
-static bool log2_patch_build(void)
+/* the builder's part (the share is in L2_BUILDING: nobody else reads or writes g_l2 and g_l2_err meanwhile) */
+static bool log2_patch_fill(int dev)
 {
-    int dev = 0;
-    g_l2_err[0] = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { snprintf(g_l2_err, sizeof g_l2_err, "no current HIP device"); return false; }
-    if (g_l2.tried && g_l2.device == dev) {
-        if (!g_l2.ok) snprintf(g_l2_err, sizeof g_l2_err, "an earlier attempt on this device failed");
-        return g_l2.ok;
-    }
-    if (g_l2.d_keys) { (void) hipFree(g_l2.d_keys); (void) hipFree(g_l2.d_vals); g_l2 = Log2Patch(); }
-    g_l2.tried = true; g_l2.device = dev; g_l2.ok = false;
-    if (getenv("FIASCO_AMD_NO_LOG2_TABLE")) { g_l2.ok = true; return true; }
+    if (g_l2.d_keys) { (void) hipFree(g_l2.d_keys); (void) hipFree(g_l2.d_vals); }
+    g_l2.d_keys = nullptr; g_l2.d_vals = nullptr; g_l2.mask = 0; g_l2.entries = 0;
+    if (getenv("FIASCO_AMD_NO_LOG2_TABLE")) return true;
     if (fa_knob("FIASCO_AMD_FAIL_LOG2_TABLE")) {                    /* tests: what a failed build looks like */
         snprintf(g_l2_err, sizeof g_l2_err, "failure requested by FIASCO_AMD_FAIL_LOG2_TABLE");
         return false;
@@ -230,7 +227,7 @@ static bool log2_patch_build(void)
         } else if (fd >= 0) close(fd);
     }
     g_l2.entries = list.size();
-    if (list.empty()) { g_l2.ok = true; return true; }       /* the two logarithms agree everywhere: nothing to correct */
+    if (list.empty()) return true;                           /* the two logarithms agree everywhere: nothing to correct */
     unsigned slots = 1024;
     while (slots < 4 * list.size()) slots <<= 1;
     std::vector<unsigned> keys(slots, 0u);
@@ -254,15 +251,22 @@ static bool log2_patch_build(void)
         return false;
     }
     g_l2.mask = slots - 1;
-    g_l2.ok = true;
     return true;
+}
+
+static bool log2_patch_build(char *err, size_t n)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void) hipGetLastError(); snprintf(err, n, "no current HIP device"); return false; }
+    return l2_once(t_dev, dev, [dev] { return log2_patch_fill(dev); }, err, n);
 }
 
 /* the same comparison THROUGH the table the frame kernel uses: n_double must come out 0 */
 extern "C" int fiasco_amd_selftest_log2_patched(unsigned exp_lo, unsigned exp_hi, unsigned long long *n_checked,
                                                 unsigned long long *n_double, unsigned long long *n_entries)
 {
-    if (!log2_patch_build()) { fa_set_error("selftest: no log2 table on this device: %s", g_l2_err); return 0; }
+    char why[200];
+    if (!log2_patch_build(why, sizeof why)) { fa_set_error("selftest: no log2 table on this device: %s", why); return 0; }
     if (n_entries) *n_entries = g_l2.entries;
     if (!g_l2.d_keys && g_l2.entries) { fa_set_error("selftest: no log2 table on this device"); return 0; }
     return log2_compare(exp_lo, exp_hi, g_l2.d_keys != nullptr, n_checked, n_double, nullptr, nullptr, nullptr);

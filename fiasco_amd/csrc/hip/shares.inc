@@ -21,11 +21,18 @@
  * thread; every share of a call -- also the only one -- runs bound to its device (bind_share) and the caller's
  * current device is restored afterwards (for_each_share).
  *
- * Threading contract: the batch entries may be called from several host threads.  Calls with ONE share run
- * concurrently as before (each on its calling thread).  The worker threads of the shares k >= 1 belong to the
- * process, not to a batch: calls that spread over several shares are serialised by g_share_lock, one phase
- * (stage / submit / finish / upload) at a time.  The workers are detached and parked on a condition variable;
- * they are never joined (a dlclose of the library with several devices in use is not supported). */
+ * Threading contract.  Calls on DISTINCT batch, sequence and options objects may run at the same time on any mix of
+ * entries, from any number of host threads; one batch or sequence object is used by one thread at a time.  What such
+ * calls share is the DevState of a share -- slab pool, counters, log2 table --, and that is locked (dev_state.h): every
+ * thread of a process with one device works on g_state0, and with several shares a call whose only part lies on
+ * share k runs on its calling thread beside worker k serving another caller.  A call with ONE part runs on its
+ * calling thread, concurrently with everything else.  The worker threads of the shares k >= 1 belong to the process,
+ * not to a batch: calls that spread over several shares are serialised by g_share_lock, one phase (stage / submit /
+ * finish / upload) at a time.  The workers are detached and parked on a condition variable; they are never joined (a
+ * dlclose of the library with several devices in use is not supported).
+ *   Not while other calls run: fiasco_amd_set_devices(), fiasco_amd_set_device(), fiasco_amd_set_limits() and
+ * fiasco_amd_release_memory().  They change what the running calls read without a lock -- the device list, and
+ * g_dev_state, which bind_share() indexes while grow_dev_states() may move it -- and hand the pools' slabs back. */
 static std::vector<int> g_devices;              /* empty = not resolved yet */
 static int  g_device_explicit = -1;             /* fiasco_amd_set_device() */
 /* [k]: the state of share k.  [0] is the one every thread works on unless bind_share() says otherwise (t_dev's
@@ -109,10 +116,10 @@ extern "C" void fiasco_amd_release_memory(void)
     const bool have_cur = hipGetDevice(&cur) == hipSuccess;
     for (size_t k = 0; k < g_dev_state.size(); k++) {
         DevState *st = g_dev_state[k];
+        DevLock lock(st);
         if (st->free.empty()) continue;
         if (k < g_devices.size() && g_devices[k] >= 0 && g_devices.size() > 1) (void) hipSetDevice(g_devices[k]);
-        for (size_t i = 0; i < st->free.size(); i++) (void) hipFree(st->free[i].base);
-        st->free.clear();
+        pool_drop_locked(st);
     }
     if (have_cur && g_devices.size() > 1) (void) hipSetDevice(cur);
 }
@@ -123,6 +130,7 @@ extern "C" void fiasco_amd_get_stats(fiasco_amd_stats *out)
 {
     memset(out, 0, sizeof *out);
     for (size_t k = 0; k < g_dev_state.size(); k++) {
+        DevLock lock(g_dev_state[k]);
         const fiasco_amd_stats &b = g_dev_state[k]->stats;
         unsigned long long *o = (unsigned long long *) ((char *) out + sizeof(double));
         const unsigned long long *v = (const unsigned long long *) ((const char *) &b + sizeof(double));
@@ -136,7 +144,10 @@ extern "C" void fiasco_amd_get_stats(fiasco_amd_stats *out)
 }
 extern "C" void fiasco_amd_reset_stats(void)
 {
-    for (size_t k = 0; k < g_dev_state.size(); k++) memset(&g_dev_state[k]->stats, 0, sizeof(fiasco_amd_stats));
+    for (size_t k = 0; k < g_dev_state.size(); k++) {
+        DevLock lock(g_dev_state[k]);
+        memset(&g_dev_state[k]->stats, 0, sizeof(fiasco_amd_stats));
+    }
 }
 
 /* A batch over the shares.  Every part is the batch of ONE share (a Staged, enc_stage.inc) and knows the jobs it

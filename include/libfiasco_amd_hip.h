@@ -96,10 +96,18 @@ int fiasco_amd_rccl_gather(void *comm, void *stream, int rank, int world, int ro
  * environment if set; else what fiasco_amd_set_devices() chose; else the ONE device of
  * fiasco_amd_set_device() (one process per GPU: the multi-process harness); else every visible device.
  * An id may be listed twice (two shares on one GPU).  Replacement of staged inputs (fiasco_amd_batch_upload) works
- * with several devices too: one pinned host buffer, every share copies the planes of ITS frames.  Threading: the
- * batch entries of ONE process may be called from several host threads, but calls that spread over more than one
- * device share run one after the other (the shares' worker threads belong to the process, shares.inc
- * for_each_share).  All return 1 on success, 0 + error message. */
+ * with several devices too: one pinned host buffer, every share copies the planes of ITS frames.  All return 1 on
+ * success, 0 + error message.
+ *   Threading.  Calls on DISTINCT batch, sequence and options objects may run at the same time from several host
+ * threads, on any mix of entries (fiasco_coder(), fiasco_amd_encode_batch(), staged batches, sequences, the decoding
+ * entries, fiasco_amd_get_stats() / _reset_stats()): what they share inside -- the slab pool, the counters and the
+ * log2 correction table of a device share -- is locked, and the table is built once whoever asks first.  ONE batch or
+ * sequence object is used by one thread at a time.  Calls that spread over more than one device share run one after
+ * the other (the shares' worker threads belong to the process, shares.inc for_each_share); a call with one part runs
+ * on its calling thread beside them.  fiasco_amd_set_devices(), fiasco_amd_set_device(), fiasco_amd_set_limits() and
+ * fiasco_amd_release_memory() must not run while other calls do: they change the device list and the limits that
+ * running calls read, and hand the pools' memory back.  The fiasco_amd_selftest_*() entries are meant for one thread;
+ * fiasco_amd_selftest_log2_max_ulp() reports the largest distance any comparison of the process has seen. */
 /* workgroups per frame the launcher gives the table passes of `frames` big frames (prediction, P/B frames, -z 1/2)
  * on a chip of `cus` CUs: 1, 2, 4 or 8 (csrc/hip/frame_coder.h FcCoop); pure function */
 unsigned fiasco_amd_coop_workgroups(unsigned frames, int cus);

@@ -373,6 +373,28 @@ def test_fan_out_helper_under_sanitizers(sanitizer, tmp_path):
     assert out.returncode == 0 and "fan_out_check: ok" in out.stdout and not out.stderr, out.stdout[-2000:] + out.stderr[-4000:]
 
 
+@pytest.mark.parametrize("sanitizer", ["thread", "address,undefined"])
+def test_dev_state_under_sanitizers(sanitizer, tmp_path):
+    """What concurrent callers share on one device share -- the slab pool, the once-guard of the log2 table, the
+    counters (csrc/hip/dev_state.h, slab_pool.inc) -- in a program of its own over a fake of the pool's five HIP calls,
+    tests/dev_state_check.cpp, built with a sanitizer: no slab with two holders, every allocation freed once, the drop
+    and retry branch under contention, device tags kept, one table build for eight callers, exact counters -- and no
+    report."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "dev_state_check")
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=" + sanitizer, "-fno-sanitize-recover=all",
+                        "-I" + os.path.join(root, "fiasco_amd", "csrc", "hip"), "-I" + os.path.join(root, "include"),
+                        "-I" + os.path.join(root, "tests"),
+                        "-o", exe, os.path.join(root, "tests", "dev_state_check.cpp"), "-lpthread"], capture_output=True, text=True)
+    if r.returncode != 0 and ("cannot find" in r.stderr or "unrecognized" in r.stderr):
+        pytest.skip("no %s sanitizer runtime on this machine" % sanitizer)
+    assert r.returncode == 0 and not r.stderr, r.stderr
+    out = subprocess.run([exe], capture_output=True, text=True)
+    if "unexpected memory mapping" in out.stderr:          # the runtime cannot place its shadow memory in this address space
+        pytest.skip("the %s sanitizer runtime does not start on this machine" % sanitizer)
+    assert out.returncode == 0 and "dev_state_check: ok" in out.stdout and not out.stderr, out.stdout[-2000:] + out.stderr[-4000:]
+
+
 def _declared_functions():
     """name -> number of parameters of every function include/libfiasco_amd.h and include/libfiasco_amd_hip.h declare
     (comment stripper and name pattern of test_headers_and_symbol_list_agree)."""
