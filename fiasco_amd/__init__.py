@@ -185,8 +185,23 @@ def _video_abi():
     }
 
 
+def _smooth_abi():
+    """the same for include/libfiasco_amd_smooth.h: decoded frames smoothed along their partition borders on the device,
+    as the reference's decoder shows them (the HIP library)"""
+    c = ctypes
+    P, ptr, i, u, ull, targets = c.POINTER, c.c_void_p, c.c_int, c.c_uint, c.c_ulonglong, c.POINTER(DeviceTarget)
+    return {
+        "fiasco_amd_batch_decode_device_smoothed": (i, [ptr, i, targets, ptr]),
+        "fiasco_amd_batch_decode_distortion_device_smoothed": (i, [ptr, i, P(ull), P(u), targets, ptr]),
+        "fiasco_amd_smooth_planes_device": (i, [ptr, u, u, P(Border), u, i, ptr]),
+    }
+
+
 _SIGNATURES = _abi()
 _VIDEO_SIGNATURES = _video_abi()
+_SMOOTH_SIGNATURES = _smooth_abi()
+# every symbol include/libfiasco_amd_smooth.h declares
+SMOOTH_SYMBOLS = list(_SMOOTH_SIGNATURES)
 # every symbol include/libfiasco_amd_video.h declares
 VIDEO_SYMBOLS = list(_VIDEO_SIGNATURES)
 # every symbol include/libfiasco_amd.h and include/libfiasco_amd_hip.h declare
@@ -214,7 +229,7 @@ class Library:
             raise FiascoError("%s is missing: run fiasco_amd.build() (there is no fallback)" % path)
         self.path = path
         self.L = ctypes.CDLL(path)
-        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VIDEO_SIGNATURES.items()):      # the one place that declares the ABI to ctypes
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VIDEO_SIGNATURES.items()) + list(_SMOOTH_SIGNATURES.items()):      # the one place that declares the ABI to ctypes
             if hasattr(self.L, name):
                 fn = getattr(self.L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -449,7 +464,7 @@ class Batch:
             raise FiascoError(self.lib.error_message())
         return [(b.x, b.y, b.len, b.level, b.pass_) for b in arr]
 
-    def decode_device(self, targets, stream=None, magnify=0):
+    def decode_device(self, targets, stream=None, magnify=0, smoothing=0):
         """fiasco_amd_batch_decode_device: the frames of the last finished pass, decoded on the device and written as
         8-bit pixels into `targets` -- the bytes of the PGM / PPM `dfiasco -s 0 -o` writes.  A target is a torch uint8
         tensor on the GPU or any writable object with __cuda_array_interface__, of the frame's size: H x W for a gray
@@ -458,13 +473,20 @@ class Batch:
         current stream for torch tensors, else the default stream.  That stream waits for the conversion: what is
         queued on it afterwards sees the pixels, no host synchronisation needed.  Returns the number of frames written.
         magnify != 0: fiasco_amd_batch_decode_device_magnified, the bytes of `dfiasco -s 0 -m magnify -o`; every target
-        has the size magnified_size() gives for its frame."""
+        has the size magnified_size() gives for its frame.
+        smoothing != 0: fiasco_amd_batch_decode_device_smoothed, the frame smoothed along the borders of its partition as
+        `dfiasco -s smoothing -o` writes it (1 .. 100 per cent); -1: at the value of the frame's own stream header, what
+        `dfiasco` shows when no -s is given.  Not together with magnify."""
+        if smoothing and magnify:
+            raise FiascoError("decode_device: smoothing and magnify together (magnified frames are not smoothed)")
         targets = list(targets)
         if len(targets) != self.n:
             raise FiascoError("decode_device: %d targets for a batch of %d" % (len(targets), self.n))
         arr = _device_targets(targets)
         on = _stream_of([t for t in targets if t is not None], stream)
-        if magnify:
+        if smoothing:
+            good = self.lib.L.fiasco_amd_batch_decode_device_smoothed(self.handle, smoothing, arr, on)
+        elif magnify:
             good = self.lib.L.fiasco_amd_batch_decode_device_magnified(self.handle, magnify, arr, on)
         else:
             good = self.lib.L.fiasco_amd_batch_decode_device(self.handle, arr, on)
@@ -496,14 +518,15 @@ class Batch:
             raise FiascoError(self.lib.error_message())
         return good
 
-    def decode_distortion_device(self, targets=None, stream=None):
+    def decode_distortion_device(self, targets=None, stream=None, smoothing=0):
         """fiasco_amd_batch_decode_distortion_device: the frames of the last finished pass, decoded on the device and
         compared with their originals there.  Returns (n measured, sse, maxdiff, psnr_db), each [[per band] per frame]:
         the exact integer sum of the squared byte differences, the largest absolute byte difference, and
         10 log10(255^2 W H / sse) in double (inf for sse == 0; the mean is over the pixels of the image, as
         decode_psnr).  Bands a frame does not have read 0 / 0 / 0.0; a skipped frame reads as sse 0.  `targets`: None, or
         one target per frame as decode_device takes them (None: measured, not written) -- one decode serves both;
-        `stream` as decode_device."""
+        `stream` as decode_device.  smoothing != 0: fiasco_amd_batch_decode_distortion_device_smoothed, the distortion
+        (and the pixels) of the frame smoothed as decode_device(smoothing=...) smooths it."""
         import math
         c = ctypes
         n = self.n
@@ -514,8 +537,11 @@ class Batch:
                 raise FiascoError("decode_distortion_device: %d targets for a batch of %d" % (len(targets), n))
             arr = _device_targets(targets)
         s, m = (c.c_ulonglong * (3 * n))(), (c.c_uint * (3 * n))()
-        good = self.lib.L.fiasco_amd_batch_decode_distortion_device(
-            self.handle, s, m, arr, _stream_of([t for t in targets or [] if t is not None], stream))
+        on = _stream_of([t for t in targets or [] if t is not None], stream)
+        if smoothing:
+            good = self.lib.L.fiasco_amd_batch_decode_distortion_device_smoothed(self.handle, smoothing, s, m, arr, on)
+        else:
+            good = self.lib.L.fiasco_amd_batch_decode_distortion_device(self.handle, s, m, arr, on)
         if not good:
             raise FiascoError(self.lib.error_message())
         psnr = []
@@ -661,6 +687,20 @@ def planes_distortion_device(lib, a, b, stream=None):
                                                      _stream_of([a], stream)):
         raise FiascoError(lib.error_message())
     return list(s), list(m)
+
+
+def smooth_planes_device(lib, planes, borders, smoothing, stream=None):
+    """fiasco_amd_smooth_planes_device: the smoothing step alone.  `planes`: a packed int16 array on the GPU (12.4 fixed
+    point), H x W or 3 x H x W; its Y plane (the first) is changed in place along `borders`, (x, y, len, level, pass)
+    tuples in the order of Batch.smoothing_borders(); `smoothing`: 0 .. 100 per cent.  Runs on `stream` (default as
+    decode_device) and waits for it."""
+    address, shape = _packed_planes(None, planes)
+    borders = list(borders)
+    arr = (Border * max(len(borders), 1))()
+    for k, b in enumerate(borders):
+        arr[k].x, arr[k].y, arr[k].len, arr[k].level, arr[k].pass_ = b
+    if not lib.L.fiasco_amd_smooth_planes_device(address, shape[-1], shape[-2], arr, len(borders), smoothing, _stream_of([planes], stream)):
+        raise FiascoError(lib.error_message())
 
 
 def _packed_strides(shape):

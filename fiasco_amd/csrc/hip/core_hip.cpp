@@ -38,6 +38,7 @@
 #include "frame_coder.h"
 #include "libfiasco_amd_hip.h"
 #include "libfiasco_amd_video.h"
+#include "libfiasco_amd_smooth.h"
 
 /* Developer and test switches (FIASCO_AMD_SPEC, _NO_WIDE, _FORCE_TRI, _CAP_GUESS, _QUEUE_SLABS, _TRACE, ...)
  * are honoured only when FIASCO_AMD_DEBUG is set to something other than 0: a drop-in library must not
@@ -128,8 +129,8 @@ static bool ic_convert(Staged *S, const fiasco_amd_device_frame *frames, int par
 #include "rccl_gather.inc"      /* fiasco_amd_rccl_gather: the streams of all ranks onto one */
 
 /* ------------------------------------------------------------------ the device decoder and its outlets
- * What the four files below agree on.  The decoder (frame_decoder.inc) works in flights of at most DEC_FLIGHT frames:
- * the tables a flight uploads (DecDesc, OcFrame, DsPlane) and the result array of its measuring launch
+ * What the five files below agree on.  The decoder (frame_decoder.inc) works in flights of at most DEC_FLIGHT frames:
+ * the tables a flight uploads (DecDesc, SmDesc, OcFrame, DsPlane) and the result array of its measuring launch
  * (distortion.inc DS_SLOTS) have room for that many. */
 enum { DEC_FLIGHT = 32 };
 
@@ -140,4 +141,5 @@ static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const D
 #include "input_convert.inc"
 #include "output_convert.inc"
 #include "distortion.inc"
+#include "smooth.inc"
 #include "frame_decoder.inc"

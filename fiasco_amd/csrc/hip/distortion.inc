@@ -121,11 +121,11 @@ static bool ds_launch(const DsPlane *d_tab, const std::vector<DsPlane> &tab, voi
 
 /* ------------------------------------------------------------------ the entry points (include/libfiasco_amd_hip.h) */
 
-extern "C" int fiasco_amd_batch_decode_distortion_device(const fiasco_amd_batch_t *b, unsigned long long *sse, unsigned *maxdiff,
-                                                         const fiasco_amd_device_target *targets, void *stream)
+/* the two measuring batch entries (this file's and the smoothed one, smooth.inc): the jobs of B (checked, oc_batch_jobs)
+ * through the decoder, compared with their originals and, with targets, written */
+static int ds_decode_batch(const char *who, const fiasco_amd_batch_t *b, OcBatch &B, unsigned long long *sse, unsigned *maxdiff,
+                           const fiasco_amd_device_target *targets, void *stream)
 {
-    OcBatch B;
-    if (!oc_batch_jobs("fiasco_amd_batch_decode_distortion_device", sse || maxdiff || targets ? nullptr : "no result arrays and no targets", b, targets, B)) return 0;
     const unsigned n = b->n;
     std::vector<unsigned char> written(n, 0), measured(n, 0);
     std::vector<const int16_t *> orig(n, nullptr);
@@ -139,7 +139,7 @@ extern "C" int fiasco_amd_batch_decode_distortion_device(const fiasco_amd_batch_
         if (image[i]->src_dev && image[i]->src_dev_id == B.device[i]) orig[i] = image[i]->src_dev;
         wanted++;
     }
-    if (!wanted) { fa_set_error("fiasco_amd_batch_decode_distortion_device: no frame with a finished intra automaton"); return 0; }
+    if (!wanted) { fa_set_error("%s: no frame with a finished intra automaton", who); return 0; }
     for (unsigned i = 0; i < n; i++)
         if (!B.jobs[i].skip && !orig[i] && !fa_image_host_planes(image[i])) return 0;
     OcOut out;
@@ -157,6 +157,15 @@ extern "C" int fiasco_amd_batch_decode_distortion_device(const fiasco_amd_batch_
     for (unsigned i = 0; i < n; i++)
         if (!B.jobs[i].skip && !measured[i]) fa_set_error("<frame %u>: %s", i, B.jobs[i].errmsg[0] ? B.jobs[i].errmsg : "decoder failed");
     return good;
+}
+
+extern "C" int fiasco_amd_batch_decode_distortion_device(const fiasco_amd_batch_t *b, unsigned long long *sse, unsigned *maxdiff,
+                                                         const fiasco_amd_device_target *targets, void *stream)
+{
+    OcBatch B;
+    const char *who = "fiasco_amd_batch_decode_distortion_device";
+    if (!oc_batch_jobs(who, sse || maxdiff || targets ? nullptr : "no result arrays and no targets", b, targets, B)) return 0;
+    return ds_decode_batch(who, b, B, sse, maxdiff, targets, stream);
 }
 
 /* planes of `bytes' bytes at p: device memory, inside the allocation p belongs to.  *device: where they live */

@@ -32,6 +32,11 @@
  *  size of fiasco_amd_magnified_size().  For M = -k the level launches of a full-size decode have written those images on
  *  their way up: dec_thumb_kernel gathers them into reduced planes and one decode gives the frame and its thumbnail.
  *
+ *  Smoothing (dfiasco -s N, smooth_image codec/decoder.c:674-768; fa_dec_job.smoothing): behind the kernels that write
+ *  the planes of a flight and before every consumer, dec_flight_smooth blends the Y plane of the frames that ask for it
+ *  along the borders of their partition, one launch per pass of the border list (smooth.inc).  What is written and what
+ *  is measured is then the frame the reference's decoder displays.  Intra frames at magnification 0.
+ *
  *  The decoded planes stay on the device (fa_image.dev): the next P/B frame of the sequence takes its
  *  reference frames with a device-to-device copy (upload_reference); the host copy serves every other caller.
  */
@@ -207,6 +212,12 @@ struct DecFrame {                     /* one frame in flight */
     size_t scratch_off = 0;           /* dec_flight_prepare: its scratch_b bytes of the flight's arena */
     unsigned slot = 0;                /* dec_flight_measure: its place in the result array of the measuring launch */
     bool measured = false;            /* ... which it has only if it has an original (DsOut) */
+    /* smoothing (dec_smooth_prepare -> dec_flight_smooth, smooth.inc); sm_np == 0: the frame gets no launch */
+    std::vector<fiasco_amd_border> sm_borders;      /* the checked list: packed into the flight's block, never uploaded itself */
+    unsigned sm_np = 0;               /* its passes */
+    int sm_is = 0, sm_inegs = 0;      /* the factors */
+    size_t sm_off = 0, sm_b = 0;      /* its sm_table_bytes() of the arena */
+    unsigned long long sm_pairs = 0;  /* pixel pairs blended: 4 bytes read and 4 written each */
 };
 
 static void dec_fail(fa_dec_job *j, const char *msg) { snprintf(j->errmsg, sizeof j->errmsg, "%s", msg); j->out = nullptr; }
@@ -414,8 +425,8 @@ struct DecShare {
 };
 
 /* The frames of one flight.  The level images of a frame (14 MB at 720p colour) live for one flight only, beside the
- * slabs of a staged batch.  The flight owns what its asynchronous uploads read -- the frames' host buffers and the three
- * tables -- until dec_flight_wait has drained the stream, and the carve of the arena. */
+ * slabs of a staged batch.  The flight owns what its asynchronous uploads read -- the frames' host buffers, the tables
+ * and the packed smoothing tables -- until dec_flight_wait has drained the stream, and the carve of the arena. */
 struct DecFlight {
     std::vector<unsigned> job;                  /* [frame] index into the jobs */
     std::vector<DecFrame> fr;                   /* [frame] */
@@ -423,11 +434,15 @@ struct DecFlight {
     std::vector<DecDesc>  descs;                /* one per frame alive after the uploads: blockIdx.y of the level launches */
     std::vector<OcFrame>  octab; std::vector<DsPlane> dstab;    /* the frames written; the planes measured */
     std::vector<DecThumb> thtab; std::vector<OcFrame> thoctab;  /* the thumbnails gathered; written */
+    std::vector<SmDesc>   smtab;                /* one per frame alive and smoothed: blockIdx.y of the smoothing launches */
+    std::vector<char>     smhost;               /* the packed smoothing tables of the flight, laid out as in the arena from
+                                                 * sm_first on: sized and filled by dec_flight_prepare, not touched after */
     union { unsigned long long sums[DS_SLOTS]; char bytes[DS_RES_BYTES]; } dsres;      /* sums, then maxima: 8-byte aligned */
     /* the arena: the scratch of every frame (DecFrame::scratch_off), then */
     size_t desc_off = 0, oc_off = 0;            /* the tables of DecDesc and OcFrame */
     size_t th_off = 0, thoc_off = 0;            /* thumbnails: the tables of DecThumb and OcFrame, */
     size_t thumb_first = 0, thumb_all = 0;      /* ... and the reduced planes of all frames, back to back: zeroed with one call */
+    size_t smd_off = 0, sm_first = 0;           /* smoothing: the table of SmDesc; the packed tables of the frames (DecFrame::sm_off) */
     size_t ds_off = 0, res_off = 0, orig_off = 0;       /* measuring: the table of DsPlane, the result array, the originals that come from the host */
     size_t need = 0;                            /* all of it */
 
@@ -464,6 +479,25 @@ static bool dec_thumb_prepare(DecShare &S, unsigned job, DecFrame &D)
     return true;
 }
 
+/* a frame that is smoothed (fa_dec_job.smoothing): its factors, and the borders of its partition, checked against its
+ * plane before anything of the flight is uploaded or launched.  A list that fails the check fails its frame alone.
+ * D.sm_b is what dec_flight_prepare carves and dec_flight_smooth packs */
+static bool dec_smooth_prepare(fa_dec_job *j, DecFrame &D)
+{
+    if (!j->smoothing) return true;
+    if (j->smoothing < 0 || j->smoothing > 100) { dec_fail(j, "device decoder: smoothing out of range (1 .. 100 per cent; the header's value is the batch entries' to look up)"); return false; }
+    if (j->magnify || j->frame_type != FA_I_FRAME) { dec_fail(j, "device decoder: smoothing of intra frames at magnification 0 only"); return false; }
+    if (!sm_factors(j->smoothing, &D.sm_is, &D.sm_inegs)) return true;       /* the reference smooths nothing */
+    const unsigned n = fa_smoothing_borders(j->wfa, D.W, D.H, j->color, nullptr, 0);
+    if (!n) return true;
+    D.sm_borders.resize(n);
+    char msg[200];
+    if (fa_smoothing_borders(j->wfa, D.W, D.H, j->color, D.sm_borders.data(), n) != n) { dec_fail(j, "device decoder: the smoothing borders changed while they were listed"); return false; }
+    if (!sm_check(D.sm_borders.data(), n, D.W, D.H, &D.sm_np, &D.sm_pairs, msg, sizeof msg)) { D.sm_np = 0; dec_fail(j, msg); return false; }
+    D.sm_b = sm_table_bytes(n, D.sm_np);
+    return true;
+}
+
 /* host side of the n frames `idx': their automata as integers, and where everything lies in the arena.  The tables
  * are sized for a full flight whatever n is */
 static void dec_flight_prepare(DecShare &S, DecFlight &F, const unsigned *idx, size_t n)
@@ -471,11 +505,29 @@ static void dec_flight_prepare(DecShare &S, DecFlight &F, const unsigned *idx, s
     F.job.assign(idx, idx + n);
     F.fr.resize(n);
     const bool thumbs = S.out && S.out->thumb;
+    bool smooth = false;
     for (size_t k = 0; k < n; k++)
-        if (dec_prepare(&S.jobs[F.job[k]], F.fr[k]) && (!thumbs || dec_thumb_prepare(S, F.job[k], F.fr[k]))) {
+        if (dec_prepare(&S.jobs[F.job[k]], F.fr[k]) && (!thumbs || dec_thumb_prepare(S, F.job[k], F.fr[k])) && dec_smooth_prepare(&S.jobs[F.job[k]], F.fr[k])) {
             F.alive.push_back(k); F.fr[k].scratch_off = F.take(F.fr[k].scratch_b);
+            smooth = smooth || F.fr[k].sm_np;
         }
     F.desc_off = F.take(DEC_FLIGHT * sizeof(DecDesc));
+    /* smoothing: the table of SmDesc, then the packed tables of every frame that has passes, back to back: filled on the
+     * host here, in a block of the size of the carve, and uploaded with one copy (dec_flight_smooth) */
+    F.smd_off = F.take(smooth ? DEC_FLIGHT * sizeof(SmDesc) : 0);
+    F.sm_first = F.need;
+    for (size_t k : F.alive) if (F.fr[k].sm_np) F.fr[k].sm_off = F.take(F.fr[k].sm_b);
+    F.smhost.assign(F.need - F.sm_first, 0);
+    std::vector<size_t> run;
+    for (size_t k : F.alive) {
+        DecFrame &D = F.fr[k];
+        if (D.sm_np && !sm_pack(D.sm_borders.data(), (unsigned) D.sm_borders.size(), D.sm_np, F.smhost.data() + (D.sm_off - F.sm_first), D.sm_b)) {
+            dec_fail(&S.jobs[F.job[k]], "device decoder: the smoothing tables do not fit their carve");
+            continue;
+        }
+        run.push_back(k);
+    }
+    F.alive.swap(run);
     F.oc_off = F.take(S.out ? DEC_FLIGHT * sizeof(OcFrame) : 0);
     F.th_off = F.take(thumbs ? DEC_FLIGHT * sizeof(DecThumb) : 0);
     F.thoc_off = F.take(thumbs ? DEC_FLIGHT * sizeof(OcFrame) : 0);
@@ -552,6 +604,36 @@ static void dec_flight_mc(DecShare &S, DecFlight &F)
     for (size_t k : F.alive)
         if (S.jobs[F.job[k]].frame_type == FA_I_FRAME || dec_run_mc(&S.jobs[F.job[k]], F.fr[k], S.stream, S.device)) run.push_back(k);
     F.alive.swap(run);
+}
+
+/* the frames of the flight that are smoothed, behind the kernels that wrote their planes and before every consumer: the
+ * descriptors of the frames that got here (blockIdx.y indexes THIS table, not the frames of the flight), the packed
+ * tables with one copy, then one launch of sm_pass_kernel per pass index (smooth.inc).  Both copies read host memory
+ * the flight owns and no longer changes (F.smtab is complete before it is queued, F.smhost since dec_flight_prepare) */
+static void dec_flight_smooth(DecShare &S, DecFlight &F)
+{
+    unsigned passes = 0;
+    for (size_t k : F.alive) {
+        DecFrame &D = F.fr[k];
+        if (!D.sm_np) continue;
+        F.smtab.emplace_back();
+        sm_describe(F.smtab.back(), D.planes, D.W, D.H, S.arena + D.sm_off, (unsigned) D.sm_borders.size(), D.sm_np, D.sm_is, D.sm_inegs);
+        if (D.sm_np > passes) passes = D.sm_np;
+    }
+    if (F.smtab.empty()) return;
+    bool ok = hipMemcpyAsync(S.arena + F.sm_first, F.smhost.data(), F.smhost.size(), hipMemcpyHostToDevice, S.stream) == hipSuccess
+              && hipMemcpyAsync(S.arena + F.smd_off, F.smtab.data(), F.smtab.size() * sizeof(SmDesc), hipMemcpyHostToDevice, S.stream) == hipSuccess;
+    for (unsigned p = 0; ok && p < passes; p++) {
+        unsigned long long most = 0;
+        for (size_t k : F.alive) {
+            const DecFrame &D = F.fr[k];
+            if (!D.sm_np) continue;
+            const unsigned long long items = sm_pass_items(F.smhost.data() + (D.sm_off - F.sm_first), (unsigned) D.sm_borders.size(), D.sm_np, p);
+            if (items > most) most = items;
+        }
+        ok = sm_launch((const SmDesc *) (S.arena + F.smd_off), (unsigned) F.smtab.size(), p, most, S.stream);
+    }
+    if (!ok) dec_flight_fail(S, F, "device decoder: HIP error");
 }
 
 /* the thumbnails of the flight, behind its level launches: the reduced planes zeroed, ONE launch of dec_thumb_kernel
@@ -661,7 +743,8 @@ static bool dec_download(DecShare &S, fa_dec_job *j, DecFrame &D)
 }
 
 /* what the frames alive at the end get: done[] and the sums, or a host image; and the statistics.  Pixels: 2 bytes
- * read per pixel and band, the 8-bit pixel written; measuring: 2 bytes read per side */
+ * read per pixel and band, the 8-bit pixel written; measuring: 2 bytes read per side; smoothing: a pixel pair is read
+ * and written, 8 bytes */
 static void dec_flight_results(DecShare &S, DecFlight &F)
 {
     float ms = 0;
@@ -688,7 +771,7 @@ static void dec_flight_results(DecShare &S, DecFlight &F)
         }
         if ((S.images || (!S.out && !S.ds)) && !dec_download(S, j, D)) continue;
         frames++;
-        bytes += D.bytes + (S.ds ? 4 * vals : 0) + (written ? 3 * vals : 0) + 7 * tvals;
+        bytes += D.bytes + (S.ds ? 4 * vals : 0) + (written ? 3 * vals : 0) + 7 * tvals + (D.sm_np ? 8 * D.sm_pairs : 0);
     }
     dec_account((unsigned long long) (ms * 1000.0f), frames, bytes);
     S.good += (int) frames;
@@ -752,6 +835,7 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine, con
         dec_flight_upload(S, F);
         dec_flight_levels(S, F);
         dec_flight_mc(S, F);
+        dec_flight_smooth(S, F);
         if (out && out->thumb) dec_flight_thumbs(S, F);
         if (ds) dec_flight_measure(S, F);
         if (out) dec_flight_write(S, F);

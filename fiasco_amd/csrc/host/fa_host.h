@@ -204,6 +204,11 @@ typedef struct fa_dec_job {
     const fa_image *orig;                 /* in: the original the frame is measured against (sse or maxdiff given) */
     void           *consumer_stream;      /* in: the caller's hipStream_t, as fiasco_amd_batch_decode_device() takes it */
     int             delivered;            /* out: 1 once every consumer the job names has had the frame */
+    int             smoothing;            /* in: blend the Y plane along the borders of the partition before any consumer sees the
+                                           * frame (smooth_image, codec/decoder.c:674-768; csrc/hip/smooth.inc): 0 nothing, 1 .. 100
+                                           * that percentage (dfiasco -s N); -1 stands for the value of the frame's stream header
+                                           * (fa_info.smoothing), which the batch entries put here in its place -- a job has no
+                                           * header.  Intra frames at magnify == 0 only.  The test oracle does not know the field */
 } fa_dec_job;
 int  fa_core_decode_frames(unsigned n, fa_dec_job *jobs);    /* number of frames decoded */
 /* smoothing along the partition borders (smooth_image, codec/decoder.c:674-768; fa_batch_decode.c): the borders of a

@@ -180,7 +180,8 @@ int fiasco_amd_batch_input_planes(const fiasco_amd_batch_t *b, unsigned i, int16
  * memory (hipPointerGetAttributes) or whose rows leave its allocation; a pitch smaller than a row; a width or height
  * other than the frame's; a layout that contradicts the colour model (GRAY8 <-> gray, the RGB8 layouts <-> colour); a
  * target on a device other than the one the frame's share decodes on (the message names both; there is no peer copy on
- * this path).  Intra frames only; no smoothing (dfiasco -s 0); magnified: fiasco_amd_batch_decode_device_magnified() below.
+ * this path).  Intra frames only; the frame of `dfiasco -s 0'; smoothed: fiasco_amd_batch_decode_device_smoothed()
+ * (libfiasco_amd_smooth.h); magnified: fiasco_amd_batch_decode_device_magnified() below.
  * fiasco_amd_planes_to_pixels_device(): the conversion alone, on `stream' itself: planes [bands][height][width] int16
  * (12.4 fixed point, bands = color ? 3 : 1) in device memory -> target.  1 ok / 0 + message. */
 typedef struct fiasco_amd_device_target {
@@ -201,7 +202,8 @@ int fiasco_amd_planes_to_pixels_device(const int16_t *planes, int color, const f
  * largest absolute difference: 12 bytes per band cross to the host, no plane.  (The PSNR calls sum in float as
  * bin/pnmpsnr.c does; below 2^24 that sum is this one, beyond it rounds.)  The original of a frame that was handed over
  * in device memory is read where the input conversion left it when that is the device the frame is decoded on; every
- * other original is copied up from its host planes.  Intra frames of staged batches only; no smoothing.
+ * other original is copied up from its host planes.  Intra frames of staged batches only; the unsmoothed frame (the
+ * smoothed one: fiasco_amd_batch_decode_distortion_device_smoothed(), libfiasco_amd_smooth.h).
  * fiasco_amd_batch_decode_distortion_device(): */
 /* frames of the last finished pass: decoded on the device, compared with their originals on the device.
  * sse / maxdiff: [b->n][3], either may be NULL; bands a frame does not have and skipped frames get 0.
@@ -222,7 +224,7 @@ int fiasco_amd_planes_distortion_device(const int16_t *a, const int16_t *b, int 
  * codec/decoder.c:776-840): M < 0 gives thumbnails, M > 0 enlargements, both computed from the automaton, not scaled
  * from pixels -- 2 M is added to the level of every state and the coordinates are shifted by M.  The device decoder's
  * recursion never asks for the level of a state, so the frame at M is the images of the same states at level + 2 M
- * (csrc/hip/frame_decoder.inc).  Intra frames of staged batches; no smoothing.
+ * (csrc/hip/frame_decoder.inc).  Intra frames of staged batches; magnified frames and thumbnails are not smoothed.
  * fiasco_amd_magnified_size(): the size a frame of width x height is shown at, and whether the reference decodes it
  * at all (codec/dfiasco.c:104-137, codec/decoder.c:329-342) -- a pure function, no device.
  *   magnify > 0   width << magnify, height << magnify; refused if width * height << 2 n > 2048 * 2048 for an n in
