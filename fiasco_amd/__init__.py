@@ -197,9 +197,26 @@ def _smooth_abi():
     }
 
 
+def _display_abi():
+    """the same for include/libfiasco_amd_display.h: magnified frames and thumbnails smoothed as `dfiasco` shows them (the
+    border list in every build of the library, the rest in the HIP library)"""
+    c = ctypes
+    P, ptr, i, u, ull, targets = c.POINTER, c.c_void_p, c.c_int, c.c_uint, c.c_ulonglong, c.POINTER(DeviceTarget)
+    return {
+        "fiasco_amd_batch_smoothing_borders_magnified": (i, [ptr, u, i, P(Border), u]),
+        "fiasco_amd_batch_decode_device_shown": (i, [ptr, i, i, targets, ptr]),
+        "fiasco_amd_batch_decode_device_thumbnails_shown": (i, [ptr, i, targets, u, targets, ptr]),
+        "fiasco_amd_smooth_planes_device_fused": (i, [ptr, u, u, P(Border), u, i, ptr]),
+        "fiasco_amd_smooth_fused": (i, [ull, u]),
+    }
+
+
 _SIGNATURES = _abi()
 _VIDEO_SIGNATURES = _video_abi()
 _SMOOTH_SIGNATURES = _smooth_abi()
+_DISPLAY_SIGNATURES = _display_abi()
+# every symbol include/libfiasco_amd_display.h declares
+DISPLAY_SYMBOLS = list(_DISPLAY_SIGNATURES)
 # every symbol include/libfiasco_amd_smooth.h declares
 SMOOTH_SYMBOLS = list(_SMOOTH_SIGNATURES)
 # every symbol include/libfiasco_amd_video.h declares
@@ -229,7 +246,7 @@ class Library:
             raise FiascoError("%s is missing: run fiasco_amd.build() (there is no fallback)" % path)
         self.path = path
         self.L = ctypes.CDLL(path)
-        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VIDEO_SIGNATURES.items()) + list(_SMOOTH_SIGNATURES.items()):      # the one place that declares the ABI to ctypes
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VIDEO_SIGNATURES.items()) + list(_SMOOTH_SIGNATURES.items()) + list(_DISPLAY_SIGNATURES.items()):      # the one place that declares the ABI to ctypes
             if hasattr(self.L, name):
                 fn = getattr(self.L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -451,11 +468,19 @@ class Batch:
             raise FiascoError(self.lib.error_message())
         return out
 
-    def smoothing_borders(self, i):
+    def smoothing_borders(self, i, magnify=0):
         """fiasco_amd_batch_smoothing_borders: the borders the reference's decoder smooths frame i along, as a list of
         (x, y, len, level, pass) sorted by pass -- odd level: rows y - 1 and y, columns x .. x + len - 1; even level:
-        columns x - 1 and x, rows y .. y + len - 1.  The borders of one pass share no pixel."""
-        f = self.lib.L.fiasco_amd_batch_smoothing_borders
+        columns x - 1 and x, rows y .. y + len - 1.  The borders of one pass share no pixel.
+        magnify != 0: fiasco_amd_batch_smoothing_borders_magnified, the borders of the frame as `dfiasco -m magnify`
+        shows it, against the size magnified_size() gives.  FiascoError where the size rule refuses the magnification and
+        where a state the reference smooths along falls below level 1 (the reference's own result is undefined there)."""
+        L = self.lib.L
+        if magnify:
+            def f(handle, k, out, cap):
+                return L.fiasco_amd_batch_smoothing_borders_magnified(handle, k, magnify, out, cap)
+        else:
+            f = L.fiasco_amd_batch_smoothing_borders
         n = f(self.handle, i, None, 0)
         if not n:
             raise FiascoError(self.lib.error_message())
@@ -478,7 +503,7 @@ class Batch:
         `dfiasco -s smoothing -o` writes it (1 .. 100 per cent); -1: at the value of the frame's own stream header, what
         `dfiasco` shows when no -s is given.  Not together with magnify."""
         if smoothing and magnify:
-            raise FiascoError("decode_device: smoothing and magnify together (magnified frames are not smoothed)")
+            raise FiascoError("decode_device: smoothing and magnify together (decode_shown writes the smoothed magnified frame)")
         targets = list(targets)
         if len(targets) != self.n:
             raise FiascoError("decode_device: %d targets for a batch of %d" % (len(targets), self.n))
@@ -494,12 +519,32 @@ class Batch:
             raise FiascoError(self.lib.error_message())
         return good
 
-    def decode_thumbnails(self, targets, reduce, thumbs, stream=None):
+    def decode_shown(self, targets, magnify=0, smoothing=-1, stream=None):
+        """fiasco_amd_batch_decode_device_shown: the frames of the last finished pass as `dfiasco -m magnify -s smoothing
+        -o` writes them, into `targets` (as decode_device takes them; every target has the size magnified_size() gives
+        for its frame).  The defaults give what plain `dfiasco -m magnify -o` writes: smoothed at the value of each frame's
+        own stream header.  smoothing: -1, 0 (none) or 1 .. 100 per cent.  A frame that cannot be smoothed at `magnify`
+        (a state of its partition falls below level 1) fails alone: the others are written, the return value counts them
+        and lib.error_message() names the frame.  Returns the number of frames written."""
+        targets = list(targets)
+        if len(targets) != self.n:
+            raise FiascoError("decode_shown: %d targets for a batch of %d" % (len(targets), self.n))
+        arr = _device_targets(targets)
+        good = self.lib.L.fiasco_amd_batch_decode_device_shown(self.handle, magnify, smoothing, arr,
+                                                               _stream_of([t for t in targets if t is not None], stream))
+        if not good:
+            raise FiascoError(self.lib.error_message())
+        return good
+
+    def decode_thumbnails(self, targets, reduce, thumbs, stream=None, smoothing=0):
         """fiasco_amd_batch_decode_device_thumbnails: ONE decode of the frames of the last finished pass that writes
         every frame into `targets` as decode_device does (None, or a list in which None skips the full-size frame) and
         the same frame at 1 / 2^reduce of its side length (reduce >= 1) into `thumbs` -- the bytes
         decode_device(magnify=-reduce) gives; a thumb has the size magnified_size(lib, w, h, -reduce), None skips it.
-        `stream` as decode_device.  Returns the number of frames decoded."""
+        `stream` as decode_device.  Returns the number of frames decoded.
+        smoothing != 0: fiasco_amd_batch_decode_device_thumbnails_shown, both outputs smoothed (-1: at the value of the
+        frame's stream header, 1 .. 100 per cent) -- the frame as decode_device(smoothing=...) writes it, the thumb as
+        decode_shown(magnify=-reduce, smoothing=...) does."""
         thumbs = list(thumbs)
         if reduce < 1:
             raise FiascoError("decode_thumbnails: reduce = %d (1 halves the side length)" % reduce)
@@ -512,8 +557,11 @@ class Batch:
                 raise FiascoError("decode_thumbnails: %d targets for a batch of %d" % (len(targets), self.n))
             arr = _device_targets(targets)
         tarr = _device_targets(thumbs)
-        good = self.lib.L.fiasco_amd_batch_decode_device_thumbnails(
-            self.handle, arr, reduce, tarr, _stream_of([t for t in (targets or []) + thumbs if t is not None], stream))
+        on = _stream_of([t for t in (targets or []) + thumbs if t is not None], stream)
+        if smoothing:
+            good = self.lib.L.fiasco_amd_batch_decode_device_thumbnails_shown(self.handle, smoothing, arr, reduce, tarr, on)
+        else:
+            good = self.lib.L.fiasco_amd_batch_decode_device_thumbnails(self.handle, arr, reduce, tarr, on)
         if not good:
             raise FiascoError(self.lib.error_message())
         return good
@@ -689,17 +737,19 @@ def planes_distortion_device(lib, a, b, stream=None):
     return list(s), list(m)
 
 
-def smooth_planes_device(lib, planes, borders, smoothing, stream=None):
+def smooth_planes_device(lib, planes, borders, smoothing, stream=None, fused=False):
     """fiasco_amd_smooth_planes_device: the smoothing step alone.  `planes`: a packed int16 array on the GPU (12.4 fixed
     point), H x W or 3 x H x W; its Y plane (the first) is changed in place along `borders`, (x, y, len, level, pass)
     tuples in the order of Batch.smoothing_borders(); `smoothing`: 0 .. 100 per cent.  Runs on `stream` (default as
-    decode_device) and waits for it."""
+    decode_device) and waits for it.  fused: fiasco_amd_smooth_planes_device_fused, all passes in one launch of the
+    fused kernel (one workgroup) instead of one launch per pass; the same result."""
     address, shape = _packed_planes(None, planes)
     borders = list(borders)
     arr = (Border * max(len(borders), 1))()
     for k, b in enumerate(borders):
         arr[k].x, arr[k].y, arr[k].len, arr[k].level, arr[k].pass_ = b
-    if not lib.L.fiasco_amd_smooth_planes_device(address, shape[-1], shape[-2], arr, len(borders), smoothing, _stream_of([planes], stream)):
+    f = lib.L.fiasco_amd_smooth_planes_device_fused if fused else lib.L.fiasco_amd_smooth_planes_device
+    if not f(address, shape[-1], shape[-2], arr, len(borders), smoothing, _stream_of([planes], stream)):
         raise FiascoError(lib.error_message())
 
 

@@ -39,6 +39,7 @@
 #include "libfiasco_amd_hip.h"
 #include "libfiasco_amd_video.h"
 #include "libfiasco_amd_smooth.h"
+#include "libfiasco_amd_display.h"
 
 /* Developer and test switches (FIASCO_AMD_SPEC, _NO_WIDE, _FORCE_TRI, _CAP_GUESS, _QUEUE_SLABS, _TRACE, ...)
  * are honoured only when FIASCO_AMD_DEBUG is set to something other than 0: a drop-in library must not

@@ -35,7 +35,9 @@
  *  Smoothing (dfiasco -s N, smooth_image codec/decoder.c:674-768; fa_dec_job.smoothing): behind the kernels that write
  *  the planes of a flight and before every consumer, dec_flight_smooth blends the Y plane of the frames that ask for it
  *  along the borders of their partition, one launch per pass of the border list (smooth.inc).  What is written and what
- *  is measured is then the frame the reference's decoder displays.  Intra frames at magnification 0.
+ *  is measured is then the frame the reference's decoder displays.  Intra frames, at every magnification: the list of a
+ *  magnified frame is fa_smoothing_borders_magnified()'s, and a thumbnail beside a frame is smoothed along the list at
+ *  minus its reduction, behind dec_thumb_kernel.  Small planes take sm_frame_kernel, all passes in one launch.
  *
  *  The decoded planes stay on the device (fa_image.dev): the next P/B frame of the sequence takes its
  *  reference frames with a device-to-device copy (upload_reference); the host copy serves every other caller.
@@ -193,6 +195,16 @@ __global__ void __launch_bounds__(256) dec_clip_chroma_kernel(int16_t *__restric
 
 static int16_t dec_fixed_of(float v) { return (int16_t) ((int) ((double) (v * 8) + .5) * 2); }
 
+/* one plane that is smoothed: the checked border list against it (packed into the flight's block, never uploaded itself),
+ * what sm_check() counted, where its sm_table_bytes() lie in the arena, and which kernel takes it.  np == 0: no launch */
+struct SmPlan {
+    std::vector<fiasco_amd_border> borders;
+    unsigned np = 0;                  /* its passes */
+    unsigned long long pairs = 0;     /* pixel pairs blended: 4 bytes read and 4 written each */
+    size_t off = 0, b = 0;
+    bool fused = false;               /* sm_frame_kernel, not the per-pass launches (sm_takes_fused) */
+};
+
 struct DecFrame {                     /* one frame in flight */
     char *base = nullptr;             /* nodes | tops | mcs | images */
     int16_t *planes = nullptr;        /* the result: stays on the device */
@@ -212,12 +224,9 @@ struct DecFrame {                     /* one frame in flight */
     size_t scratch_off = 0;           /* dec_flight_prepare: its scratch_b bytes of the flight's arena */
     unsigned slot = 0;                /* dec_flight_measure: its place in the result array of the measuring launch */
     bool measured = false;            /* ... which it has only if it has an original (DsOut) */
-    /* smoothing (dec_smooth_prepare -> dec_flight_smooth, smooth.inc); sm_np == 0: the frame gets no launch */
-    std::vector<fiasco_amd_border> sm_borders;      /* the checked list: packed into the flight's block, never uploaded itself */
-    unsigned sm_np = 0;               /* its passes */
+    /* smoothing (dec_smooth_prepare -> dec_flight_smooth, smooth.inc) */
+    SmPlan sm, tsm;                   /* the frame's Y plane at the size shown; the Y plane of its thumbnail */
     int sm_is = 0, sm_inegs = 0;      /* the factors */
-    size_t sm_off = 0, sm_b = 0;      /* its sm_table_bytes() of the arena */
-    unsigned long long sm_pairs = 0;  /* pixel pairs blended: 4 bytes read and 4 written each */
 };
 
 static void dec_fail(fa_dec_job *j, const char *msg) { snprintf(j->errmsg, sizeof j->errmsg, "%s", msg); j->out = nullptr; }
@@ -434,7 +443,8 @@ struct DecFlight {
     std::vector<DecDesc>  descs;                /* one per frame alive after the uploads: blockIdx.y of the level launches */
     std::vector<OcFrame>  octab; std::vector<DsPlane> dstab;    /* the frames written; the planes measured */
     std::vector<DecThumb> thtab; std::vector<OcFrame> thoctab;  /* the thumbnails gathered; written */
-    std::vector<SmDesc>   smtab;                /* one per frame alive and smoothed: blockIdx.y of the smoothing launches */
+    std::vector<SmDesc>   smtab, tsmtab;        /* one per frame (thumbnail) alive and smoothed: first those of the per-pass
+                                                 * launches (their blockIdx.y), then those of the fused launch (its blockIdx.x) */
     std::vector<char>     smhost;               /* the packed smoothing tables of the flight, laid out as in the arena from
                                                  * sm_first on: sized and filled by dec_flight_prepare, not touched after */
     union { unsigned long long sums[DS_SLOTS]; char bytes[DS_RES_BYTES]; } dsres;      /* sums, then maxima: 8-byte aligned */
@@ -442,7 +452,7 @@ struct DecFlight {
     size_t desc_off = 0, oc_off = 0;            /* the tables of DecDesc and OcFrame */
     size_t th_off = 0, thoc_off = 0;            /* thumbnails: the tables of DecThumb and OcFrame, */
     size_t thumb_first = 0, thumb_all = 0;      /* ... and the reduced planes of all frames, back to back: zeroed with one call */
-    size_t smd_off = 0, sm_first = 0;           /* smoothing: the table of SmDesc; the packed tables of the frames (DecFrame::sm_off) */
+    size_t smd_off = 0, tsmd_off = 0, sm_first = 0;     /* smoothing: the tables of SmDesc of the frames and of the thumbnails; the packed tables (SmPlan::off) */
     size_t ds_off = 0, res_off = 0, orig_off = 0;       /* measuring: the table of DsPlane, the result array, the originals that come from the host */
     size_t need = 0;                            /* all of it */
 
@@ -479,22 +489,43 @@ static bool dec_thumb_prepare(DecShare &S, unsigned job, DecFrame &D)
     return true;
 }
 
-/* a frame that is smoothed (fa_dec_job.smoothing): its factors, and the borders of its partition, checked against its
- * plane before anything of the flight is uploaded or launched.  A list that fails the check fails its frame alone.
- * D.sm_b is what dec_flight_prepare carves and dec_flight_smooth packs */
-static bool dec_smooth_prepare(fa_dec_job *j, DecFrame &D)
+/* the borders of the job's partition at `magnify' (fa_smoothing_borders_magnified: the list `dfiasco -m magnify' smooths
+ * along), checked against the plane of W x H they will be blended in.  A frame with a state that falls below level 1 at
+ * that magnification, and a list that fails the check, fail with the message; an empty list is a plan without passes */
+static bool dec_smooth_plan(fa_dec_job *j, int magnify, unsigned W, unsigned H, SmPlan &P)
 {
+    fa_set_error("%s", "");
+    const unsigned n = fa_smoothing_borders_magnified(j->wfa, j->width, j->height, j->color, magnify, nullptr, 0);
+    if (!n) {
+        const char *why = fiasco_get_error_message();
+        if (!why[0]) return true;
+        dec_fail(j, why);
+        return false;
+    }
+    P.borders.resize(n);
+    char msg[200];
+    if (fa_smoothing_borders_magnified(j->wfa, j->width, j->height, j->color, magnify, P.borders.data(), n) != n) { dec_fail(j, "device decoder: the smoothing borders changed while they were listed"); return false; }
+    if (!sm_check(P.borders.data(), n, W, H, &P.np, &P.pairs, msg, sizeof msg)) { P.np = 0; dec_fail(j, msg); return false; }
+    P.b = sm_table_bytes(n, P.np);
+    P.fused = sm_takes_fused(P.pairs, P.np);
+    return true;
+}
+
+/* a frame that is smoothed (fa_dec_job.smoothing): its factors, and the borders of its partition at the magnification it
+ * is shown at -- and, where it gets a thumbnail, a second list at minus the reduction for the reduced plane --, checked
+ * against their planes before anything of the flight is uploaded or launched.  A list that fails fails its frame alone,
+ * thumbnail and all.  SmPlan::b is what dec_flight_prepare carves and packs.  A full-size plane nobody consumes (a
+ * thumbnail only, of a batch entry) is not smoothed */
+static bool dec_smooth_prepare(DecShare &S, unsigned job, DecFrame &D)
+{
+    fa_dec_job *j = &S.jobs[job];
     if (!j->smoothing) return true;
     if (j->smoothing < 0 || j->smoothing > 100) { dec_fail(j, "device decoder: smoothing out of range (1 .. 100 per cent; the header's value is the batch entries' to look up)"); return false; }
-    if (j->magnify || j->frame_type != FA_I_FRAME) { dec_fail(j, "device decoder: smoothing of intra frames at magnification 0 only"); return false; }
+    if (j->frame_type != FA_I_FRAME) { dec_fail(j, "device decoder: smoothing of intra frames only"); return false; }
     if (!sm_factors(j->smoothing, &D.sm_is, &D.sm_inegs)) return true;       /* the reference smooths nothing */
-    const unsigned n = fa_smoothing_borders(j->wfa, D.W, D.H, j->color, nullptr, 0);
-    if (!n) return true;
-    D.sm_borders.resize(n);
-    char msg[200];
-    if (fa_smoothing_borders(j->wfa, D.W, D.H, j->color, D.sm_borders.data(), n) != n) { dec_fail(j, "device decoder: the smoothing borders changed while they were listed"); return false; }
-    if (!sm_check(D.sm_borders.data(), n, D.W, D.H, &D.sm_np, &D.sm_pairs, msg, sizeof msg)) { D.sm_np = 0; dec_fail(j, msg); return false; }
-    D.sm_b = sm_table_bytes(n, D.sm_np);
+    const bool consumed = !S.out || S.ds || S.images || S.out->target[job].data;
+    if (consumed && !dec_smooth_plan(j, j->magnify, D.W, D.H, D.sm)) return false;
+    if (D.thumb_bytes && !dec_smooth_plan(j, -(int) S.out->reduce, D.tw, D.th, D.tsm)) return false;
     return true;
 }
 
@@ -505,23 +536,29 @@ static void dec_flight_prepare(DecShare &S, DecFlight &F, const unsigned *idx, s
     F.job.assign(idx, idx + n);
     F.fr.resize(n);
     const bool thumbs = S.out && S.out->thumb;
-    bool smooth = false;
+    bool smooth = false, tsmooth = false;
     for (size_t k = 0; k < n; k++)
-        if (dec_prepare(&S.jobs[F.job[k]], F.fr[k]) && (!thumbs || dec_thumb_prepare(S, F.job[k], F.fr[k])) && dec_smooth_prepare(&S.jobs[F.job[k]], F.fr[k])) {
+        if (dec_prepare(&S.jobs[F.job[k]], F.fr[k]) && (!thumbs || dec_thumb_prepare(S, F.job[k], F.fr[k])) && dec_smooth_prepare(S, F.job[k], F.fr[k])) {
             F.alive.push_back(k); F.fr[k].scratch_off = F.take(F.fr[k].scratch_b);
-            smooth = smooth || F.fr[k].sm_np;
+            smooth = smooth || F.fr[k].sm.np;
+            tsmooth = tsmooth || F.fr[k].tsm.np;
         }
     F.desc_off = F.take(DEC_FLIGHT * sizeof(DecDesc));
-    /* smoothing: the table of SmDesc, then the packed tables of every frame that has passes, back to back: filled on the
-     * host here, in a block of the size of the carve, and uploaded with one copy (dec_flight_smooth) */
+    /* smoothing: the table of SmDesc of the frames and a second one of the thumbnails, then the packed tables of every
+     * plane that has passes, back to back: filled on the host here, in a block of the size of the carve, and uploaded
+     * with one copy (dec_flight_smooth) */
     F.smd_off = F.take(smooth ? DEC_FLIGHT * sizeof(SmDesc) : 0);
+    F.tsmd_off = F.take(tsmooth ? DEC_FLIGHT * sizeof(SmDesc) : 0);
     F.sm_first = F.need;
-    for (size_t k : F.alive) if (F.fr[k].sm_np) F.fr[k].sm_off = F.take(F.fr[k].sm_b);
+    for (size_t k : F.alive)
+        for (SmPlan *P : { &F.fr[k].sm, &F.fr[k].tsm }) if (P->np) P->off = F.take(P->b);
     F.smhost.assign(F.need - F.sm_first, 0);
     std::vector<size_t> run;
     for (size_t k : F.alive) {
-        DecFrame &D = F.fr[k];
-        if (D.sm_np && !sm_pack(D.sm_borders.data(), (unsigned) D.sm_borders.size(), D.sm_np, F.smhost.data() + (D.sm_off - F.sm_first), D.sm_b)) {
+        bool fits = true;
+        for (SmPlan *P : { &F.fr[k].sm, &F.fr[k].tsm })
+            fits = fits && (!P->np || sm_pack(P->borders.data(), (unsigned) P->borders.size(), P->np, F.smhost.data() + (P->off - F.sm_first), P->b));
+        if (!fits) {
             dec_fail(&S.jobs[F.job[k]], "device decoder: the smoothing tables do not fit their carve");
             continue;
         }
@@ -606,33 +643,44 @@ static void dec_flight_mc(DecShare &S, DecFlight &F)
     F.alive.swap(run);
 }
 
-/* the frames of the flight that are smoothed, behind the kernels that wrote their planes and before every consumer: the
- * descriptors of the frames that got here (blockIdx.y indexes THIS table, not the frames of the flight), the packed
- * tables with one copy, then one launch of sm_pass_kernel per pass index (smooth.inc).  Both copies read host memory
- * the flight owns and no longer changes (F.smtab is complete before it is queued, F.smhost since dec_flight_prepare) */
-static void dec_flight_smooth(DecShare &S, DecFlight &F)
+/* The planes of the flight that are smoothed -- those of the frames (thumbs false: behind the kernels that wrote them,
+ * before every consumer) or the reduced ones of the thumbnails (thumbs true: behind dec_thumb_kernel, before they are
+ * written).  The descriptors of the planes that got here, those of the per-pass launches first; the packed tables of
+ * the whole flight with one copy (queued with the frames' step, which always runs first); then one launch of
+ * sm_pass_kernel per pass index for the planes that take that path (blockIdx.y indexes THEIR part of the table) and ONE
+ * launch of sm_frame_kernel for the fused ones (smooth.inc).  The copies read host memory the flight owns and no longer
+ * changes (the table is complete before it is queued, F.smhost since dec_flight_prepare) */
+static void dec_flight_smooth(DecShare &S, DecFlight &F, bool thumbs)
 {
+    std::vector<SmDesc> &tab = thumbs ? F.tsmtab : F.smtab;
+    const size_t tab_off = thumbs ? F.tsmd_off : F.smd_off;
+    bool ok = thumbs || F.smhost.empty() || F.alive.empty()
+              || hipMemcpyAsync(S.arena + F.sm_first, F.smhost.data(), F.smhost.size(), hipMemcpyHostToDevice, S.stream) == hipSuccess;
     unsigned passes = 0;
-    for (size_t k : F.alive) {
-        DecFrame &D = F.fr[k];
-        if (!D.sm_np) continue;
-        F.smtab.emplace_back();
-        sm_describe(F.smtab.back(), D.planes, D.W, D.H, S.arena + D.sm_off, (unsigned) D.sm_borders.size(), D.sm_np, D.sm_is, D.sm_inegs);
-        if (D.sm_np > passes) passes = D.sm_np;
-    }
-    if (F.smtab.empty()) return;
-    bool ok = hipMemcpyAsync(S.arena + F.sm_first, F.smhost.data(), F.smhost.size(), hipMemcpyHostToDevice, S.stream) == hipSuccess
-              && hipMemcpyAsync(S.arena + F.smd_off, F.smtab.data(), F.smtab.size() * sizeof(SmDesc), hipMemcpyHostToDevice, S.stream) == hipSuccess;
+    unsigned long long fused_most = 0;
+    std::vector<const SmPlan *> per;                    /* the planes of the per-pass launches: the first per.size() descriptors */
+    for (int fused = 0; fused < 2; fused++)
+        for (size_t k : F.alive) {
+            DecFrame &D = F.fr[k];
+            const SmPlan &P = thumbs ? D.tsm : D.sm;
+            if (!P.np || P.fused != (fused != 0)) continue;
+            tab.emplace_back();
+            sm_describe(tab.back(), thumbs ? D.thumb : D.planes, thumbs ? D.tw : D.W, thumbs ? D.th : D.H, S.arena + P.off, (unsigned) P.borders.size(), P.np,
+                        D.sm_is, D.sm_inegs);
+            if (!fused) { per.push_back(&P); if (P.np > passes) passes = P.np; }
+            else for (unsigned p = 0; p < P.np; p++)
+                fused_most = std::max(fused_most, sm_pass_items(F.smhost.data() + (P.off - F.sm_first), (unsigned) P.borders.size(), P.np, p));
+        }
+    if (ok && tab.empty()) return;
+    const SmDesc *d_tab = (const SmDesc *) (S.arena + tab_off);
+    ok = ok && hipMemcpyAsync(S.arena + tab_off, tab.data(), tab.size() * sizeof(SmDesc), hipMemcpyHostToDevice, S.stream) == hipSuccess;
     for (unsigned p = 0; ok && p < passes; p++) {
         unsigned long long most = 0;
-        for (size_t k : F.alive) {
-            const DecFrame &D = F.fr[k];
-            if (!D.sm_np) continue;
-            const unsigned long long items = sm_pass_items(F.smhost.data() + (D.sm_off - F.sm_first), (unsigned) D.sm_borders.size(), D.sm_np, p);
-            if (items > most) most = items;
-        }
-        ok = sm_launch((const SmDesc *) (S.arena + F.smd_off), (unsigned) F.smtab.size(), p, most, S.stream);
+        for (const SmPlan *P : per)
+            most = std::max(most, sm_pass_items(F.smhost.data() + (P->off - F.sm_first), (unsigned) P->borders.size(), P->np, p));
+        ok = sm_launch(d_tab, (unsigned) per.size(), p, most, S.stream);
     }
+    if (ok) ok = sm_launch_fused(d_tab + per.size(), (unsigned) (tab.size() - per.size()), fused_most, S.stream);
     if (!ok) dec_flight_fail(S, F, "device decoder: HIP error");
 }
 
@@ -771,7 +819,7 @@ static void dec_flight_results(DecShare &S, DecFlight &F)
         }
         if ((S.images || (!S.out && !S.ds)) && !dec_download(S, j, D)) continue;
         frames++;
-        bytes += D.bytes + (S.ds ? 4 * vals : 0) + (written ? 3 * vals : 0) + 7 * tvals + (D.sm_np ? 8 * D.sm_pairs : 0);
+        bytes += D.bytes + (S.ds ? 4 * vals : 0) + (written ? 3 * vals : 0) + 7 * tvals + (D.sm.np ? 8 * D.sm.pairs : 0) + (D.thumb && D.tsm.np ? 8 * D.tsm.pairs : 0);
     }
     dec_account((unsigned long long) (ms * 1000.0f), frames, bytes);
     S.good += (int) frames;
@@ -835,8 +883,8 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine, con
         dec_flight_upload(S, F);
         dec_flight_levels(S, F);
         dec_flight_mc(S, F);
-        dec_flight_smooth(S, F);
-        if (out && out->thumb) dec_flight_thumbs(S, F);
+        dec_flight_smooth(S, F, false);
+        if (out && out->thumb) { dec_flight_thumbs(S, F); dec_flight_smooth(S, F, true); }
         if (ds) dec_flight_measure(S, F);
         if (out) dec_flight_write(S, F);
         dec_flight_wait(S, F);

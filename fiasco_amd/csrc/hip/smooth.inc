@@ -9,7 +9,9 @@
  *  ascending level, then Cb by ascending level -- such that the borders of one pass share no pixel; pass after pass
  *  that is the reference's sequential result.  Here ONE launch of sm_pass_kernel per pass index blends that pass in
  *  every frame of a decoder flight (blockIdx.y = frame; a frame with fewer passes returns); stream order separates the
- *  passes.
+ *  passes.  A plane small enough that those launches, not its bytes, are its cost (sm_fused) takes sm_frame_kernel
+ *  instead: ONE launch in which one workgroup runs all passes of the plane, a barrier between two passes.  Magnified
+ *  frames and thumbnails are smoothed along fa_smoothing_borders_magnified()'s list against their own size.
  *
  *  Arithmetic (tests/smooth_ref.py restates it in numpy): a pixel pair (a, b) across a border becomes
  *    a' = (((is * a) >> 10) << 1) + (((inegs * b) >> 10) << 1),  b' = the mirror image
@@ -37,9 +39,10 @@
  *  size, the two tables and the factors.  All of it lies in the flight's arena, carved by dec_flight_prepare from the
  *  counts that sm_check() returned and sm_pack() packs -- sm_pack() refuses a block of another size.
  *
- *  sm_factors(), sm_check(), sm_table_bytes(), sm_pack(), sm_pass_items(), sm_describe() and the per-item function
- *  sm_item() are plain C++: with SMOOTH_HOST_REPLAY defined this file compiles without HIP and holds nothing else
- *  (tests/smooth_step_check.cpp replays flights on the CPU under the sanitizers).
+ *  sm_factors(), sm_check(), sm_table_bytes(), sm_pack(), sm_pass_items(), sm_describe(), sm_fused(), the per-item function
+ *  sm_item() and the fused kernel's body between two barriers, sm_frame_step(), are plain C++: with SMOOTH_HOST_REPLAY
+ *  defined this file compiles without HIP and holds nothing else (tests/smooth_step_check.cpp and
+ *  tests/shown_step_check.cpp replay flights on the CPU under the sanitizers).
  */
 
 #ifdef SMOOTH_HOST_REPLAY
@@ -87,6 +90,36 @@ SM_ITEM void sm_item(const SmDesc &d, unsigned pass, unsigned long long i)
     p[ia] = (int16_t) (((is * a) >> 10) * 2 + ((inegs * b) >> 10) * 2);
     p[ib] = (int16_t) (((is * b) >> 10) * 2 + ((inegs * a) >> 10) * 2);
 }
+
+/* the items of pass `pass' of the frame d, read where the kernel reads them: borders << log2(side); 0 beyond the last pass */
+SM_ITEM unsigned long long sm_items(const SmDesc &d, unsigned pass)
+{
+    if (pass >= d.npasses) return 0;
+    const SM_GLOBAL unsigned *first = (const SM_GLOBAL unsigned *) d.first;
+    const SM_GLOBAL fiasco_amd_border *bd = (const SM_GLOBAL fiasco_amd_border *) d.borders;
+    const unsigned b0 = first[pass], nb = first[pass + 1] - b0;
+    return nb ? (unsigned long long) nb << sm_log2_side(bd[b0].level) : 0ull;
+}
+
+/* The body of sm_frame_kernel between two barriers: what thread t of nt does in pass `pass' of the plane its workgroup
+ * owns -- the items t, t + nt, ... of that pass, each through sm_item().  The items of a pass touch disjoint pixels, so
+ * their order within the pass is free; the barrier between two passes is the caller's (the kernel: __syncthreads(); a
+ * replay on the CPU: finishing every t of a pass before the next pass begins). */
+SM_ITEM void sm_frame_step(const SmDesc &d, unsigned pass, unsigned t, unsigned nt)
+{
+    const unsigned long long n = sm_items(d, pass);
+    for (unsigned long long i = t; i < n; i += nt) sm_item(d, pass, i);
+}
+
+/* Which smoothed planes take the fused kernel (sm_frame_kernel: ONE launch, one workgroup per plane, all passes) and
+ * which the per-pass launches that the planes of a flight share: a pure function of the counts sm_check() returns.
+ * One workgroup blends at most 1024 pairs at a time where the per-pass launches spread a pass over the chip, so the
+ * fused kernel wins where launches dominate: small planes.  SM_FUSED_MAX_PAIRS is the largest measured size at which a
+ * fused flight of 32 planes was faster by more than the spread of the measurement: 240 x 136, a 1080p frame at -3, by
+ * 12 us of 981; at 25 368 pairs (512 x 384) it lost by 5 us (profiles/shown_device.json, DESIGN.md 3).
+ * A plane without passes has no launch of either kind. */
+static const unsigned long long SM_FUSED_MAX_PAIRS = 17270ull;
+static inline bool sm_fused(unsigned long long pairs, unsigned npasses) { return npasses >= 1 && pairs <= SM_FUSED_MAX_PAIRS; }
 
 /* the factors of a smoothing percentage; false: the reference smooths nothing (s < 0.5 || s >= 1) */
 static bool sm_factors(int percent, int *is, int *inegs)
@@ -181,6 +214,42 @@ static bool sm_launch(const SmDesc *d_descs, unsigned nframes, unsigned pass, un
     return hipGetLastError() == hipSuccess;
 }
 
+/* All passes of a plane in ONE launch: blockIdx.x selects a descriptor, and the one workgroup that gets it owns that
+ * plane for the whole launch.  Pass after pass its threads stride the items of the pass (sm_frame_step -> sm_item, the
+ * per-item function of sm_pass_kernel) and meet at a barrier: what a pass reads was written by the kernels before this
+ * one on the stream or by waves of THIS workgroup before the barrier -- same CU, same L1; nothing another CU wrote during
+ * the launch is read, so there is no hand-off between workgroups.  Plain 16-bit loads and stores.  npasses is one
+ * value per block (the descriptor is read by every thread from the same address): every thread reaches every barrier.
+ * hipcc, gfx950: 16 VGPRs, 38 SGPRs, no LDS, no scratch (-Rpass-analysis=kernel-resource-usage). */
+__global__ void __launch_bounds__(1024) sm_frame_kernel(const SmDesc *__restrict__ descs)
+{
+    const SmDesc d = descs[blockIdx.x];
+    for (unsigned pass = 0; pass < d.npasses; pass++) {
+        sm_frame_step(d, pass, threadIdx.x, blockDim.x);
+        __syncthreads();
+    }
+}
+
+/* the nplanes planes of the table at d_descs (device memory), each by a workgroup of its own; most: the items of the
+ * largest pass among them, which sizes the workgroups (64 .. 1024 threads, whole waves) */
+static bool sm_launch_fused(const SmDesc *d_descs, unsigned nplanes, unsigned long long most, hipStream_t stream)
+{
+    if (!most || !nplanes) return true;
+    const unsigned threads = most >= 1024 ? 1024u : (unsigned) ((most + 63) / 64 * 64);
+    sm_frame_kernel<<<dim3(nplanes), dim3(threads), 0, stream>>>(d_descs);
+    return hipGetLastError() == hipSuccess;
+}
+
+/* sm_fused(), or what the developer switch FIASCO_AMD_SMOOTH_FUSED says in its place (1: every smoothed plane through
+ * the fused kernel, 0: none; honoured with FIASCO_AMD_DEBUG only): the tests run both paths on the same frames */
+static bool sm_takes_fused(unsigned long long pairs, unsigned npasses)
+{
+    const long long forced = knob_int("FIASCO_AMD_SMOOTH_FUSED", -1);
+    return forced == 0 ? false : forced == 1 ? npasses >= 1 : sm_fused(pairs, npasses);
+}
+
+extern "C" int fiasco_amd_smooth_fused(unsigned long long pairs, unsigned npasses) { return sm_fused(pairs, npasses) ? 1 : 0; }
+
 /* ------------------------------------------------------------------ the entry points (include/libfiasco_amd_smooth.h) */
 
 static const char *sm_refuse(int smoothing)
@@ -218,10 +287,34 @@ extern "C" int fiasco_amd_batch_decode_distortion_device_smoothed(const fiasco_a
     return ds_decode_batch(who, b, B, sse, maxdiff, targets, stream);
 }
 
-extern "C" int fiasco_amd_smooth_planes_device(int16_t *y_plane, unsigned width, unsigned height, const fiasco_amd_border *borders, unsigned n,
-                                               int smoothing, void *stream)
+/* include/libfiasco_amd_display.h: the magnified entry and the thumbnail entry with the jobs' smoothing set -- the
+ * decoder's flights do the rest (dec_smooth_prepare, frame_decoder.inc) */
+extern "C" int fiasco_amd_batch_decode_device_shown(const fiasco_amd_batch_t *b, int magnify, int smoothing, const fiasco_amd_device_target *targets, void *stream)
 {
-    const char *who = "fiasco_amd_smooth_planes_device";
+    OcBatch B;
+    const char *who = "fiasco_amd_batch_decode_device_shown";
+    if (!oc_batch_jobs(who, targets ? sm_refuse(smoothing) : "no targets", b, targets, B, magnify)) return 0;
+    sm_batch_jobs(b, B, smoothing);
+    return oc_decode_batch(who, b, B, 0, stream);
+}
+
+extern "C" int fiasco_amd_batch_decode_device_thumbnails_shown(const fiasco_amd_batch_t *b, int smoothing, const fiasco_amd_device_target *targets, unsigned reduce,
+                                                               const fiasco_amd_device_target *thumbs, void *stream)
+{
+    OcBatch B;
+    const char *who = "fiasco_amd_batch_decode_device_thumbnails_shown";
+    const char *refuse = !thumbs ? "no thumbnails" : !reduce ? "a reduction of at least 1 (half the side length) is needed" : reduce > 15 ? "reduction out of range"
+                         : sm_refuse(smoothing);
+    if (!oc_batch_jobs(who, refuse, b, targets, B, 0, thumbs, reduce)) return 0;
+    sm_batch_jobs(b, B, smoothing);
+    return oc_decode_batch(who, b, B, reduce, stream);
+}
+
+/* the step alone (fiasco_amd_smooth_planes_device, fiasco_amd_smooth_planes_device_fused): one launch per pass, or the
+ * fused kernel */
+static int sm_planes_device(const char *who, bool fused, int16_t *y_plane, unsigned width, unsigned height, const fiasco_amd_border *borders, unsigned n,
+                            int smoothing, void *stream)
+{
     if (!y_plane || (n && !borders)) { fa_set_error("%s: no plane or no borders", who); return 0; }
     if (smoothing < 0 || smoothing > 100) { fa_set_error("%s: smoothing %d (0 .. 100 per cent; there is no header here).", who, smoothing); return 0; }
     if (width < 1 || width > 8192 || height < 1 || height > 8192) {
@@ -271,13 +364,29 @@ extern "C" int fiasco_amd_smooth_planes_device(int16_t *y_plane, unsigned width,
         memcpy(host.data(), &d, sizeof d);
         ok = hipMemcpy(buf, host.data(), host.size(), hipMemcpyHostToDevice) == hipSuccess;
     }
-    for (unsigned p = 0; ok && p < npasses; p++)
+    unsigned long long most = 0;
+    for (unsigned p = 0; p < npasses; p++) most = std::max(most, sm_pass_items(host.data() + desc_b, n, npasses, p));
+    if (ok && fused) ok = sm_launch_fused((const SmDesc *) buf, 1, most, (hipStream_t) stream);
+    for (unsigned p = 0; ok && !fused && p < npasses; p++)
         ok = sm_launch((const SmDesc *) buf, 1, p, sm_pass_items(host.data() + desc_b, n, npasses, p), (hipStream_t) stream);
     if (buf && hipStreamSynchronize((hipStream_t) stream) != hipSuccess) ok = false;
     if (!ok) fa_set_error("HIP error: %s", hipGetErrorString(hipGetLastError()));
     if (buf) (void) hipFree(buf);
     if (cur >= 0 && cur != at.device) (void) hipSetDevice(cur);
     return ok ? 1 : 0;
+}
+
+extern "C" int fiasco_amd_smooth_planes_device(int16_t *y_plane, unsigned width, unsigned height, const fiasco_amd_border *borders, unsigned n,
+                                               int smoothing, void *stream)
+{
+    return sm_planes_device("fiasco_amd_smooth_planes_device", false, y_plane, width, height, borders, n, smoothing, stream);
+}
+
+/* include/libfiasco_amd_display.h */
+extern "C" int fiasco_amd_smooth_planes_device_fused(int16_t *y_plane, unsigned width, unsigned height, const fiasco_amd_border *borders, unsigned n,
+                                                     int smoothing, void *stream)
+{
+    return sm_planes_device("fiasco_amd_smooth_planes_device_fused", true, y_plane, width, height, borders, n, smoothing, stream);
 }
 
 #endif /* !SMOOTH_HOST_REPLAY */

@@ -8,11 +8,13 @@
  *  the frame in device memory are the core's (csrc/hip/output_convert.inc, distortion.inc); they fill their decoder
  *  jobs with fa_dec_job_of() too.
  */
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
 #include "fa_host.h"
 #include "libfiasco_amd_hip.h"
+#include "libfiasco_amd_display.h"
 
 /* The guard of every outlet `who': the finished intra job of frame i, or NULL + message.  `usable': the caller's own
  * precondition (an output buffer), refused in the same words as a missing automaton.  `why' ends the refusal of a P/B
@@ -256,6 +258,80 @@ int fiasco_amd_magnified_size(unsigned width, unsigned height, int magnify, unsi
  * horizontally (rows y - 1 and y, `len' columns from x), even levels vertically (columns x - 1 and x, `len' rows from
  * y); len is the block's side, clipped at the frame.  Returns the number of borders; out may be NULL (count only);
  * more than cap: 0 + message. */
+/* The list at magnification `mag', against the size shown (width x height are the magnified ones): what smooth_image
+ * walks after enlarge_image (codec/decoder.c:776-840) has added 2 mag to the level of every state and shifted its
+ * coordinates by mag.  Same phases, same order.  *low: set to 1 + the coded level of the first visible state whose shifted
+ * level falls below 1 (the caller refuses the frame); such a state is not listed. */
+static unsigned borders_at(const fa_wfa *w, unsigned width, unsigned height, int color, int mag, fiasco_amd_border *out, unsigned cap,
+                           unsigned *low)
+{
+    unsigned from[2], to[2], phases = 1, phase, n = 0, pass = 0;
+    from[0] = w->basis_states; to[0] = w->states;
+    if (color) {
+        const unsigned join = (unsigned) FA_TREE(w, w->root_state, 0);
+        to[0] = (unsigned) FA_TREE(w, join, 0) + 1;
+        from[1] = to[0]; to[1] = join;
+        phases = 2;
+    }
+    for (phase = 0; phase < phases; phase++) {
+        int level, maxl = 0;
+        unsigned s;
+        for (s = from[phase]; s < to[phase]; s++) if ((int) w->level_of_state[s] + 2 * mag > maxl) maxl = (int) w->level_of_state[s] + 2 * mag;
+        for (level = 0; level <= maxl; level++) {
+            const unsigned side = level & 1 ? 1u << (level >> 1) : 1u << ((level + 1) >> 1);
+            unsigned found = 0;
+            for (s = from[phase]; s < to[phase]; s++) {
+                const int shifted = (int) w->level_of_state[s] + 2 * mag;
+                const unsigned x = mag >= 0 ? (unsigned) w->x[s * 2 + 1] << mag : (unsigned) w->x[s * 2 + 1] >> -mag;
+                const unsigned y = mag >= 0 ? (unsigned) w->y[s * 2 + 1] << mag : (unsigned) w->y[s * 2 + 1] >> -mag;
+                unsigned room;
+                if ((shifted < 1 ? 0 : shifted) != level || y >= height || x >= width) continue;
+                if (shifted < 1) { if (!*low) *low = 1u + w->level_of_state[s]; continue; }
+                if (level & 1 ? !y : !x) continue;
+                room = level & 1 ? width - x : height - y;
+                if (out) {
+                    if (n >= cap) { fa_set_error("fiasco_amd_batch_smoothing_borders_magnified: more than %u borders", cap); return 0; }
+                    out[n].x = (uint16_t) x; out[n].y = (uint16_t) y; out[n].len = (uint16_t) (side < room ? side : room);
+                    out[n].level = (uint8_t) level; out[n].pass = (uint8_t) pass;
+                }
+                n++; found = 1;
+            }
+            pass += found;
+        }
+    }
+    return n;
+}
+
+/* fa_smoothing_borders() of the frame as `dfiasco -m magnify' shows it: the coded list with x and y shifted by magnify,
+ * the level raised by 2 magnify, the length the side of that level clipped at the size of fiasco_amd_magnified_size(), a
+ * border that begins outside that size left out.  width x height: the CODED size.  magnify == 0: fa_smoothing_borders()
+ * itself.  The pass order stays the reference's sequential result while every listed state keeps a level >= 1: its cut
+ * then still lies on a whole pixel of the shown grid.  A state whose level falls below 1 (coded level <= 2 k at reduction
+ * k) is clamped to level 0 by enlarge_image with its coordinates floored: the cut lands on the block's own edge, borders
+ * share pixels, and at (0, 0) smooth_image reads and writes the word before the plane.  Such a frame is refused: 0 + message
+ * `who' begins; so is a magnification the size rule refuses (its message). */
+static unsigned borders_magnified(const fa_wfa *w, unsigned width, unsigned height, int color, int magnify, fiasco_amd_border *out,
+                                  unsigned cap, const char *who)
+{
+    unsigned mw = width, mh = height, low = 0, n;
+    if (!magnify) return fa_smoothing_borders(w, width, height, color, out, cap);
+    if (!fiasco_amd_magnified_size(width, height, magnify, &mw, &mh)) return 0;
+    if (magnify > 8) { fa_set_error("%s: magnification %d: the borders of the frame do not fit 16-bit coordinates", who, magnify); return 0; }
+    n = borders_at(w, mw, mh, color, magnify, out, cap, &low);
+    if (low) {
+        fa_set_error("%s: at magnification %d a smoothed state of level %u falls to level %d (below 1), where the "
+                     "reference's own result is undefined", who, magnify, low - 1, (int) low - 1 + 2 * magnify);
+        return 0;
+    }
+    return n;
+}
+
+unsigned fa_smoothing_borders_magnified(const fa_wfa *w, unsigned width, unsigned height, int color, int magnify, fiasco_amd_border *out,
+                                        unsigned cap)
+{
+    return borders_magnified(w, width, height, color, magnify, out, cap, "smoothing borders");
+}
+
 unsigned fa_smoothing_borders(const fa_wfa *w, unsigned width, unsigned height, int color, fiasco_amd_border *out, unsigned cap)
 {
     unsigned from[2], to[2], phases = 1, phase, n = 0, pass = 0;
@@ -295,4 +371,14 @@ int fiasco_amd_batch_smoothing_borders(const fiasco_amd_batch_t *b, unsigned i, 
 {
     const fa_job *job = finished_intra(b, i, 1, "fiasco_amd_batch_smoothing_borders", "", 0);
     return job ? (int) fa_smoothing_borders(job->wfa, job->image->width, job->image->height, job->image->color, out, cap) : 0;
+}
+
+/* include/libfiasco_amd_display.h */
+int fiasco_amd_batch_smoothing_borders_magnified(const fiasco_amd_batch_t *b, unsigned i, int magnify, fiasco_amd_border *out, unsigned cap)
+{
+    const fa_job *job = finished_intra(b, i, 1, "fiasco_amd_batch_smoothing_borders_magnified", "", 0);
+    char who[80];
+    if (!job) return 0;
+    snprintf(who, sizeof who, "fiasco_amd_batch_smoothing_borders_magnified: frame %u", i);
+    return (int) borders_magnified(job->wfa, job->image->width, job->image->height, job->image->color, magnify, out, cap, who);
 }

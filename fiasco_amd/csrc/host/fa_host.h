@@ -208,12 +208,17 @@ typedef struct fa_dec_job {
                                            * frame (smooth_image, codec/decoder.c:674-768; csrc/hip/smooth.inc): 0 nothing, 1 .. 100
                                            * that percentage (dfiasco -s N); -1 stands for the value of the frame's stream header
                                            * (fa_info.smoothing), which the batch entries put here in its place -- a job has no
-                                           * header.  Intra frames at magnify == 0 only.  The test oracle does not know the field */
+                                           * header.  Intra frames, at every magnify (the list of a magnified frame:
+                                           * fa_smoothing_borders_magnified).  The test oracle does not know the field */
 } fa_dec_job;
 int  fa_core_decode_frames(unsigned n, fa_dec_job *jobs);    /* number of frames decoded */
 /* smoothing along the partition borders (smooth_image, codec/decoder.c:674-768; fa_batch_decode.c): the borders of a
  * frame in passes (fiasco_amd_batch_smoothing_borders) */
 unsigned fa_smoothing_borders(const fa_wfa *w, unsigned width, unsigned height, int color, fiasco_amd_border *out, unsigned cap);
+/* ... of the frame as `dfiasco -m magnify' shows it (width x height: the coded size; fiasco_amd_batch_smoothing_borders_magnified).
+ * 0 + message: the size rule refuses the magnification, or a smoothed state falls below level 1 */
+unsigned fa_smoothing_borders_magnified(const fa_wfa *w, unsigned width, unsigned height, int color, int magnify, fiasco_amd_border *out,
+                                        unsigned cap);
 void fa_core_release_dev(void *dev, int dev_id);
 
 /* ---------------- stream info (reference codec/wfa.h:65-110 wfa_info_t) ----------- */

@@ -224,7 +224,7 @@ int fiasco_amd_planes_distortion_device(const int16_t *a, const int16_t *b, int 
  * codec/decoder.c:776-840): M < 0 gives thumbnails, M > 0 enlargements, both computed from the automaton, not scaled
  * from pixels -- 2 M is added to the level of every state and the coordinates are shifted by M.  The device decoder's
  * recursion never asks for the level of a state, so the frame at M is the images of the same states at level + 2 M
- * (csrc/hip/frame_decoder.inc).  Intra frames of staged batches; magnified frames and thumbnails are not smoothed.
+ * (csrc/hip/frame_decoder.inc).  Intra frames of staged batches; unsmoothed (`-s 0'): libfiasco_amd_display.h has the smoothed siblings.
  * fiasco_amd_magnified_size(): the size a frame of width x height is shown at, and whether the reference decodes it
  * at all (codec/dfiasco.c:104-137, codec/decoder.c:329-342) -- a pure function, no device.
  *   magnify > 0   width << magnify, height << magnify; refused if width * height << 2 n > 2048 * 2048 for an n in

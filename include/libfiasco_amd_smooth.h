@@ -27,7 +27,7 @@ extern "C" {
  *                 unsmoothed siblings; 1 .. 100: that percentage.  Anything else is refused.
  * fiasco_amd_batch_decode_device_smoothed(), fiasco_amd_batch_decode_distortion_device_smoothed(): every rule, refusal
  * and return value of fiasco_amd_batch_decode_device() / fiasco_amd_batch_decode_distortion_device().  Intra frames at
- * the coded size; the frames of a video, magnified frames and thumbnails are not smoothed. */
+ * the coded size; the frames of a video are not smoothed, magnified frames and thumbnails are libfiasco_amd_display.h's. */
 int fiasco_amd_batch_decode_device_smoothed(const fiasco_amd_batch_t *b, int smoothing, const fiasco_amd_device_target *targets, void *stream);
 int fiasco_amd_batch_decode_distortion_device_smoothed(const fiasco_amd_batch_t *b, int smoothing, unsigned long long *sse, unsigned *maxdiff,
                                                        const fiasco_amd_device_target *targets, void *stream);
