@@ -44,6 +44,11 @@ class DeviceTarget(ctypes.Structure):
     _fields_ = DeviceFrame._fields_
 
 
+class DeviceSurface(ctypes.Structure):
+    """struct fiasco_amd_device_surface (include/libfiasco_amd_render.h): a display surface in device memory."""
+    _fields_ = [("data", ctypes.c_void_p), ("pitch", ctypes.c_size_t), ("width", ctypes.c_uint), ("height", ctypes.c_uint)]
+
+
 class SeqOutputs(ctypes.Structure):
     """struct fiasco_amd_seq_outputs (include/libfiasco_amd_video.h)."""
     _fields_ = [("targets", ctypes.POINTER(DeviceTarget)), ("sse", ctypes.POINTER(ctypes.c_ulonglong)),
@@ -211,10 +216,29 @@ def _display_abi():
     }
 
 
+def _render_abi():
+    """the same for include/libfiasco_amd_render.h: decoded frames in the pixel formats of a display, as the reference's
+    renderer writes them into an XImage (the handle, the size and the host loop in host code that needs no device; the kernel
+    and the batch entry in the HIP library)"""
+    c = ctypes
+    P, ptr, i, u, ul, size, surfaces = c.POINTER, c.c_void_p, c.c_int, c.c_uint, c.c_ulong, c.c_size_t, c.POINTER(DeviceSurface)
+    return {
+        "fiasco_amd_renderer_new": (ptr, [ul, ul, ul, u, i]),
+        "fiasco_amd_renderer_delete": (None, [ptr]),
+        "fiasco_amd_renderer_surface_size": (i, [ptr, u, u, i, P(u), P(u), P(size)]),
+        "fiasco_amd_renderer_render_planes": (i, [ptr, ptr, i, u, u, ptr]),
+        "fiasco_amd_planes_render_device": (i, [ptr, i, u, u, ptr, surfaces, ptr]),
+        "fiasco_amd_batch_decode_device_rendered": (i, [ptr, ptr, i, i, surfaces, ptr]),
+    }
+
+
 _SIGNATURES = _abi()
 _VIDEO_SIGNATURES = _video_abi()
 _SMOOTH_SIGNATURES = _smooth_abi()
 _DISPLAY_SIGNATURES = _display_abi()
+_RENDER_SIGNATURES = _render_abi()
+# every symbol include/libfiasco_amd_render.h declares
+RENDER_SYMBOLS = list(_RENDER_SIGNATURES)
 # every symbol include/libfiasco_amd_display.h declares
 DISPLAY_SYMBOLS = list(_DISPLAY_SIGNATURES)
 # every symbol include/libfiasco_amd_smooth.h declares
@@ -246,7 +270,7 @@ class Library:
             raise FiascoError("%s is missing: run fiasco_amd.build() (there is no fallback)" % path)
         self.path = path
         self.L = ctypes.CDLL(path)
-        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VIDEO_SIGNATURES.items()) + list(_SMOOTH_SIGNATURES.items()) + list(_DISPLAY_SIGNATURES.items()):      # the one place that declares the ABI to ctypes
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VIDEO_SIGNATURES.items()) + list(_SMOOTH_SIGNATURES.items()) + list(_DISPLAY_SIGNATURES.items()) + list(_RENDER_SIGNATURES.items()):      # the one place that declares the ABI to ctypes
             if hasattr(self.L, name):
                 fn = getattr(self.L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -536,6 +560,22 @@ class Batch:
             raise FiascoError(self.lib.error_message())
         return good
 
+    def decode_rendered(self, renderer, surfaces, magnify=0, smoothing=-1, stream=None):
+        """fiasco_amd_batch_decode_device_rendered: the frames of the last finished pass as the reference's viewer puts them
+        on the screen at `-m magnify -s smoothing`, through `renderer` into `surfaces` -- one per frame, a writable uint8 GPU
+        array of shape (H, W, bpp // 8) with H, W from renderer.surface_size() for the frame at magnified_size(); the pitch is
+        the first stride; None skips the frame.  Flights, smoothing, per-frame refusals and `stream` as decode_shown.
+        Returns the number of frames written."""
+        surfaces = list(surfaces)
+        if len(surfaces) != self.n:
+            raise FiascoError("decode_rendered: %d surfaces for a batch of %d" % (len(surfaces), self.n))
+        arr = _device_surfaces(surfaces, renderer.bpp)
+        good = self.lib.L.fiasco_amd_batch_decode_device_rendered(self.handle, renderer.handle, magnify, smoothing, arr,
+                                                                  _stream_of([t for t in surfaces if t is not None], stream))
+        if not good:
+            raise FiascoError(self.lib.error_message())
+        return good
+
     def decode_thumbnails(self, targets, reduce, thumbs, stream=None, smoothing=0):
         """fiasco_amd_batch_decode_device_thumbnails: ONE decode of the frames of the last finished pass that writes
         every frame into `targets` as decode_device does (None, or a list in which None skips the full-size frame) and
@@ -683,6 +723,84 @@ def _device_targets(targets):
         if t is not None and _describe("target", i, t, arr[i]):
             raise FiascoError("target %d is read-only" % i)
     return arr
+
+
+def _device_surfaces(surfaces, bpp):
+    """The fiasco_amd_device_surface array of a list of writable uint8 GPU arrays of shape (H, W, bpp // 8); the pitch is the
+    first stride, the other two must be bpp // 8 and 1; None: data = NULL, skipped."""
+    arr = (DeviceSurface * max(len(surfaces), 1))()
+    for i, t in enumerate(surfaces):
+        if t is None:
+            continue
+        cai = getattr(t, "__cuda_array_interface__", None)
+        if cai is None:
+            raise FiascoError("surface %d is not in device memory (no __cuda_array_interface__)" % i)
+        if cai["typestr"] not in ("|u1", "<u1", ">u1", "=u1"):
+            raise FiascoError("surface %d: bytes (uint8) expected, not %s" % (i, cai["typestr"]))
+        shape = tuple(int(v) for v in cai["shape"])
+        if len(shape) != 3 or shape[2] != bpp // 8:
+            raise FiascoError("surface %d: shape %s is not H x W x %d (the bytes of a pixel at %d bpp)" % (i, shape, bpp // 8, bpp))
+        strides = cai.get("strides")
+        strides = tuple(int(v) for v in (strides if strides is not None else _packed_strides(shape)))
+        if strides[2] != 1 or strides[1] != bpp // 8 or strides[0] <= 0:
+            raise FiascoError("surface %d: strides %s cannot be described by a pitch (the bytes of a pixel and the pixels of a row "
+                              "must be adjacent)" % (i, strides))
+        if cai["data"][1]:
+            raise FiascoError("surface %d is read-only" % i)
+        arr[i].data, arr[i].pitch, (arr[i].height, arr[i].width) = int(cai["data"][0]), strides[0], shape[:2]
+    return arr
+
+
+class Renderer:
+    """fiasco_amd_renderer_*: the reference's renderer (fiasco_renderer_new) restated -- colour masks, 16, 24 or 32 bits per
+    pixel, optionally every pixel doubled in both directions.  Immutable; delete() frees it."""
+
+    def __init__(self, lib, red_mask, green_mask, blue_mask, bpp, double_resolution=False):
+        self.lib, self.bpp, self.double_resolution = lib, bpp, bool(double_resolution)
+        self.handle = lib.L.fiasco_amd_renderer_new(red_mask, green_mask, blue_mask, bpp, 1 if double_resolution else 0)
+        if not self.handle:
+            raise FiascoError(lib.error_message())
+
+    def surface_size(self, width, height, color):
+        """fiasco_amd_renderer_surface_size: (surface width, surface height, bytes of a packed row) for a frame of
+        width x height; FiascoError where the reference's loops would not fill the surface."""
+        w, h, row = ctypes.c_uint(), ctypes.c_uint(), ctypes.c_size_t()
+        if not self.lib.L.fiasco_amd_renderer_surface_size(self.handle, width, height, 1 if color else 0, w, h, row):
+            raise FiascoError(self.lib.error_message())
+        return w.value, h.value, row.value
+
+    def render_planes(self, planes):
+        """fiasco_amd_renderer_render_planes, the host loop: int16 numpy planes (H x W gray, 3 x H x W for Y, Cb, Cr; 12.4
+        fixed point) -> the bytes of the packed surface."""
+        import numpy
+        planes = numpy.ascontiguousarray(planes, dtype=numpy.int16)
+        if planes.ndim not in (2, 3) or (planes.ndim == 3 and planes.shape[0] not in (1, 3)):
+            raise FiascoError("render_planes: int16 H x W or 3 x H x W expected, not %s" % (planes.shape,))
+        color = planes.ndim == 3 and planes.shape[0] == 3
+        h, w = planes.shape[-2:]
+        _, sh, row = self.surface_size(w, h, color)
+        buf = ctypes.create_string_buffer(sh * row)
+        if not self.lib.L.fiasco_amd_renderer_render_planes(self.handle, planes.ctypes.data, 1 if color else 0, w, h, buf):
+            raise FiascoError(self.lib.error_message())
+        return buf.raw
+
+    def delete(self):
+        if self.handle:
+            self.lib.L.fiasco_amd_renderer_delete(self.handle)
+            self.handle = None
+
+
+def render_planes_device(lib, renderer, planes, surface, stream=None):
+    """fiasco_amd_planes_render_device: the rendering kernel alone.  `planes`: a packed int16 array on the GPU (12.4 fixed
+    point), H x W or 3 x H x W; `surface`: as Batch.decode_rendered.  Runs on `stream` (default as decode_device) and waits
+    for it."""
+    address, shape = _packed_planes(None, planes)
+    arr = _device_surfaces([surface], renderer.bpp)
+    if surface is None:
+        raise FiascoError("render_planes_device: no surface")
+    if not lib.L.fiasco_amd_planes_render_device(address, 1 if len(shape) == 3 else 0, shape[-1], shape[-2], renderer.handle, arr,
+                                                 _stream_of([surface], stream)):
+        raise FiascoError(lib.error_message())
 
 
 def magnified_size(lib, width, height, magnify):

@@ -40,6 +40,7 @@
 #include "libfiasco_amd_video.h"
 #include "libfiasco_amd_smooth.h"
 #include "libfiasco_amd_display.h"
+#include "libfiasco_amd_render.h"
 
 /* Developer and test switches (FIASCO_AMD_SPEC, _NO_WIDE, _FORCE_TRI, _CAP_GUESS, _QUEUE_SLABS, _TRACE, ...)
  * are honoured only when FIASCO_AMD_DEBUG is set to something other than 0: a drop-in library must not
@@ -143,4 +144,5 @@ static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const D
 #include "output_convert.inc"
 #include "distortion.inc"
 #include "smooth.inc"
+#include "render.inc"             /* beside output_convert.inc: display surfaces instead of 8-bit pixels; its batch entry is smooth.inc's with surfaces */
 #include "frame_decoder.inc"

@@ -743,7 +743,8 @@ static void dec_flight_measure(DecShare &S, DecFlight &F)
 }
 
 /* the frames of the flight that have a target into the caller's buffers, once the caller's stream has let go of them:
- * ONE launch of oc_convert_kernel; one more for the thumbnails, if there are any */
+ * ONE launch of oc_convert_kernel -- or of rd_render_kernel, where the targets are display surfaces (OcOut::render) --;
+ * one more for the thumbnails, if there are any */
 static void dec_flight_write(DecShare &S, DecFlight &F)
 {
     unsigned long long total = 0, thtotal = 0;
@@ -760,7 +761,8 @@ static void dec_flight_write(DecShare &S, DecFlight &F)
     bool ok = hipStreamWaitEvent(S.stream, S.out->ready, 0) == hipSuccess;
     if (ok && !F.octab.empty())
         ok = hipMemcpyAsync(S.arena + F.oc_off, F.octab.data(), F.octab.size() * sizeof(OcFrame), hipMemcpyHostToDevice, S.stream) == hipSuccess
-             && oc_launch((const OcFrame *) (S.arena + F.oc_off), (unsigned) F.octab.size(), total, oc_cus(), S.stream);
+             && (S.out->render ? rd_launch((const OcFrame *) (S.arena + F.oc_off), (unsigned) F.octab.size(), total, S.out->render, oc_cus(), S.stream)
+                                : oc_launch((const OcFrame *) (S.arena + F.oc_off), (unsigned) F.octab.size(), total, oc_cus(), S.stream));
     if (ok && !F.thoctab.empty())
         ok = hipMemcpyAsync(S.arena + F.thoc_off, F.thoctab.data(), F.thoctab.size() * sizeof(OcFrame), hipMemcpyHostToDevice, S.stream) == hipSuccess
              && oc_launch((const OcFrame *) (S.arena + F.thoc_off), (unsigned) F.thoctab.size(), thtotal, oc_cus(), S.stream);

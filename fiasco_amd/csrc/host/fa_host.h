@@ -429,6 +429,16 @@ int fa_setup_params(const fa_options *op, float quality, unsigned width, unsigne
 void fa_info_free(fa_info *wi);
 void fa_limits(unsigned *max_states, unsigned *max_level);
 
+/* ---------------- a renderer (include/libfiasco_amd_render.h; fa_render.c makes it, hip/render.inc reads it) ----- */
+struct fiasco_amd_renderer {
+    unsigned bpp;             /* 16, 24 or 32 */
+    unsigned doubled;         /* 1: every pixel twice in both directions */
+    unsigned rgb;             /* 24 bpp: 1 = R, G, B in memory order (red_mask > green_mask), 0 = B, G, R */
+    unsigned r_drop, g_drop, b_drop;      /* 8 - bits set in the mask */
+    unsigned r_up, g_up, b_up;            /* zero bits below the mask; b_up is kept and NOT applied (the reference's blue) */
+};
+enum { FA_RENDER_MAX_SIDE = 16384 };      /* of the frame rendered */
+
 #ifdef __cplusplus
 }
 #endif
