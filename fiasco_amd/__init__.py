@@ -49,6 +49,12 @@ class DeviceSurface(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("pitch", ctypes.c_size_t), ("width", ctypes.c_uint), ("height", ctypes.c_uint)]
 
 
+class DeviceTarget420(ctypes.Structure):
+    """struct fiasco_amd_device_target_420 (include/libfiasco_amd_420.h): where a 4:2:0 frame goes in device memory."""
+    _fields_ = [("y", ctypes.c_void_p), ("y_pitch", ctypes.c_size_t), ("cb", ctypes.c_void_p), ("cr", ctypes.c_void_p),
+                ("c_pitch", ctypes.c_size_t), ("c_step", ctypes.c_uint), ("width", ctypes.c_uint), ("height", ctypes.c_uint)]
+
+
 class SeqOutputs(ctypes.Structure):
     """struct fiasco_amd_seq_outputs (include/libfiasco_amd_video.h)."""
     _fields_ = [("targets", ctypes.POINTER(DeviceTarget)), ("sse", ctypes.POINTER(ctypes.c_ulonglong)),
@@ -232,11 +238,27 @@ def _render_abi():
     }
 
 
+def _yuv420_abi():
+    """the same for include/libfiasco_amd_420.h: decoded frames in 4:2:0 as NV12 / NV21 / I420 buffers (the border list and the
+    host planes' entry in host code, which every build of the library has; the kernel and the batch entry in the HIP library)"""
+    c = ctypes
+    P, ptr, i, u, targets = c.POINTER, c.c_void_p, c.c_int, c.c_uint, c.POINTER(DeviceTarget420)
+    return {
+        "fiasco_amd_batch_decode_device_420": (i, [ptr, i, i, targets, ptr]),
+        "fiasco_amd_batch_decode_planes_420": (i, [ptr, u, i, ptr]),
+        "fiasco_amd_batch_smoothing_borders_420": (i, [ptr, u, i, P(Border), u]),
+        "fiasco_amd_planes_to_420_device": (i, [ptr, ptr, ptr, u, u, targets, ptr]),
+    }
+
+
 _SIGNATURES = _abi()
 _VIDEO_SIGNATURES = _video_abi()
 _SMOOTH_SIGNATURES = _smooth_abi()
 _DISPLAY_SIGNATURES = _display_abi()
 _RENDER_SIGNATURES = _render_abi()
+_YUV420_SIGNATURES = _yuv420_abi()
+# every symbol include/libfiasco_amd_420.h declares
+YUV420_SYMBOLS = list(_YUV420_SIGNATURES)
 # every symbol include/libfiasco_amd_render.h declares
 RENDER_SYMBOLS = list(_RENDER_SIGNATURES)
 # every symbol include/libfiasco_amd_display.h declares
@@ -270,7 +292,7 @@ class Library:
             raise FiascoError("%s is missing: run fiasco_amd.build() (there is no fallback)" % path)
         self.path = path
         self.L = ctypes.CDLL(path)
-        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VIDEO_SIGNATURES.items()) + list(_SMOOTH_SIGNATURES.items()) + list(_DISPLAY_SIGNATURES.items()) + list(_RENDER_SIGNATURES.items()):      # the one place that declares the ABI to ctypes
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VIDEO_SIGNATURES.items()) + list(_SMOOTH_SIGNATURES.items()) + list(_DISPLAY_SIGNATURES.items()) + list(_RENDER_SIGNATURES.items()) + list(_YUV420_SIGNATURES.items()):      # the one place that declares the ABI to ctypes
             if hasattr(self.L, name):
                 fn = getattr(self.L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -560,6 +582,51 @@ class Batch:
             raise FiascoError(self.lib.error_message())
         return good
 
+    def decode_420(self, targets, magnify=0, smoothing=-1, stream=None, order="nv12"):
+        """fiasco_amd_batch_decode_device_420: the frames of the last finished pass decoded in 4:2:0, as the reference's
+        decoder does with fiasco_d_options_set_4_2_0_format -- the chroma bands come from the automaton at half the side
+        length, they are not subsampled -- at `-m magnify -s smoothing`, as 8-bit Y, Cb, Cr into `targets`.  A target is
+        (y, cb, cr), three writable 2-D uint8 GPU arrays of H x W, H/2 x W/2 and H/2 x W/2 (I420; the chroma planes share one
+        pitch), or (y, cbcr) with cbcr of shape H/2 x W/2 x 2: interleaved pairs, Cb first for order="nv12", Cr first for
+        order="nv21"; W x H is magnified_size() of the frame; None skips the frame.  Flights, smoothing, per-frame refusals
+        and `stream` as decode_shown; a gray frame and a frame whose chroma the reference leaves zero fail alone.  Returns
+        the number of frames written."""
+        targets = list(targets)
+        if len(targets) != self.n:
+            raise FiascoError("decode_420: %d targets for a batch of %d" % (len(targets), self.n))
+        arr = _device_targets_420(targets, order)
+        flat = [a for t in targets if t is not None for a in t]
+        good = self.lib.L.fiasco_amd_batch_decode_device_420(self.handle, magnify, smoothing, arr, _stream_of(flat, stream))
+        if not good:
+            raise FiascoError(self.lib.error_message())
+        return good
+
+    def decode_planes_420(self, i, magnify=0):
+        """fiasco_amd_batch_decode_planes_420: the unsmoothed planes of frame i decoded in 4:2:0 at `magnify`, three int16
+        arrays (12.4 fixed point): Y [h, w], Cb and Cr [h / 2, w / 2]; h, w are those of magnified_size()."""
+        import numpy
+        w, h, _ = self._geom[i]
+        if magnify:
+            w, h = magnified_size(self.lib, w, h, magnify)
+        out = numpy.empty(w * h + 2 * (w // 2) * (h // 2), dtype=numpy.int16)
+        if not self.lib.L.fiasco_amd_batch_decode_planes_420(self.handle, i, magnify, out.ctypes.data):
+            raise FiascoError(self.lib.error_message())
+        c = (w // 2) * (h // 2)
+        return (out[:w * h].reshape(h, w), out[w * h:w * h + c].reshape(h // 2, w // 2), out[w * h + c:].reshape(h // 2, w // 2))
+
+    def smoothing_borders_420(self, i, magnify=0):
+        """fiasco_amd_batch_smoothing_borders_420: the borders the reference smooths the Y plane of frame i along when it
+        decodes in 4:2:0, (x, y, len, level, pass) as smoothing_borders() lists them: the Y passes at shift `magnify`, then
+        the Cb passes at shift `magnify` - 1, against the size magnified_size() gives."""
+        L = self.lib.L
+        n = L.fiasco_amd_batch_smoothing_borders_420(self.handle, i, magnify, None, 0)
+        if not n:
+            raise FiascoError(self.lib.error_message())
+        arr = (Border * n)()
+        if L.fiasco_amd_batch_smoothing_borders_420(self.handle, i, magnify, arr, n) != n:
+            raise FiascoError(self.lib.error_message())
+        return [(b.x, b.y, b.len, b.level, b.pass_) for b in arr]
+
     def decode_rendered(self, renderer, surfaces, magnify=0, smoothing=-1, stream=None):
         """fiasco_amd_batch_decode_device_rendered: the frames of the last finished pass as the reference's viewer puts them
         on the screen at `-m magnify -s smoothing`, through `renderer` into `surfaces` -- one per frame, a writable uint8 GPU
@@ -725,6 +792,58 @@ def _device_targets(targets):
     return arr
 
 
+def _plane_of(what, i, a, ndim):
+    """(address, shape, strides) of one writable uint8 GPU array of `ndim` dimensions whose innermost elements are adjacent"""
+    cai = getattr(a, "__cuda_array_interface__", None)
+    if cai is None:
+        raise FiascoError("target %d: the %s is not in device memory (no __cuda_array_interface__)" % (i, what))
+    if cai["typestr"] not in ("|u1", "<u1", ">u1", "=u1"):
+        raise FiascoError("target %d: the %s holds %s, not bytes (uint8)" % (i, what, cai["typestr"]))
+    shape = tuple(int(v) for v in cai["shape"])
+    if len(shape) != ndim:
+        raise FiascoError("target %d: the %s has shape %s, %d dimensions expected" % (i, what, shape, ndim))
+    strides = cai.get("strides")
+    strides = tuple(int(v) for v in (strides if strides is not None else _packed_strides(shape)))
+    if strides[-1] != 1 or (ndim == 3 and strides[1] != 2) or strides[0] <= 0:
+        raise FiascoError("target %d: the strides %s of the %s cannot be described by a pitch" % (i, strides, what))
+    if cai["data"][1]:
+        raise FiascoError("target %d: the %s is read-only" % (i, what))
+    return int(cai["data"][0]), shape, strides
+
+
+def _device_targets_420(targets, order="nv12"):
+    """The fiasco_amd_device_target_420 array of a list of 4:2:0 targets: (y, cb, cr), three 2-D arrays, or (y, cbcr) with
+    cbcr of shape H/2 x W/2 x 2 and `order` "nv12" (Cb first) or "nv21"; None: y = NULL, skipped."""
+    if order not in ("nv12", "nv21"):
+        raise FiascoError("order %r is neither \"nv12\" nor \"nv21\"" % (order,))
+    arr = (DeviceTarget420 * max(len(targets), 1))()
+    for i, t in enumerate(targets):
+        if t is None:
+            continue
+        t = tuple(t)
+        if len(t) not in (2, 3):
+            raise FiascoError("target %d: (y, cb, cr) or (y, cbcr) expected, not %d arrays" % (i, len(t)))
+        d = arr[i]
+        y, (h, w), ys = _plane_of("Y plane", i, t[0], 2)
+        d.y, d.y_pitch, d.width, d.height = y, ys[0], w, h
+        if len(t) == 3:
+            (cb, sb, stb), (cr, sr, str_) = _plane_of("Cb plane", i, t[1], 2), _plane_of("Cr plane", i, t[2], 2)
+            if sb != (h // 2, w // 2) or sr != sb:
+                raise FiascoError("target %d: chroma planes of %s and %s for a Y plane of %d x %d (%d x %d expected)"
+                                  % (i, sb[::-1], sr[::-1], w, h, w // 2, h // 2))
+            if stb[0] != str_[0]:
+                raise FiascoError("target %d: the chroma planes have pitches %d and %d (one pitch expected)" % (i, stb[0], str_[0]))
+            d.cb, d.cr, d.c_pitch, d.c_step = cb, cr, stb[0], 1
+        else:
+            c, sc, stc = _plane_of("chroma plane", i, t[1], 3)
+            if sc != (h // 2, w // 2, 2):
+                raise FiascoError("target %d: an interleaved chroma plane of shape %s for a Y plane of %d x %d (%d x %d x 2 expected)"
+                                  % (i, sc, w, h, h // 2, w // 2))
+            d.cb, d.cr = (c, c + 1) if order == "nv12" else (c + 1, c)
+            d.c_pitch, d.c_step = stc[0], 2
+    return arr
+
+
 def _device_surfaces(surfaces, bpp):
     """The fiasco_amd_device_surface array of a list of writable uint8 GPU arrays of shape (H, W, bpp // 8); the pitch is the
     first stride, the other two must be bpp // 8 and 1; None: data = NULL, skipped."""
@@ -822,6 +941,23 @@ def planes_to_pixels_device(lib, planes, target, stream=None):
     if (arr[0].height, arr[0].width) != shape[-2:]:
         raise FiascoError("target of %d x %d pixels for planes of %d x %d" % (arr[0].width, arr[0].height, shape[-1], shape[-2]))
     if not lib.L.fiasco_amd_planes_to_pixels_device(address, 1 if len(shape) == 3 else 0, arr, _stream_of([target], stream)):
+        raise FiascoError(lib.error_message())
+
+
+def planes_to_420_device(lib, y, cb, cr, target, stream=None, order="nv12"):
+    """fiasco_amd_planes_to_420_device: the 4:2:0 conversion kernel alone.  `y`, `cb`, `cr`: packed int16 arrays on the GPU
+    (12.4 fixed point) of H x W, H/2 x W/2 and H/2 x W/2; `target` and `order` as Batch.decode_420.  Runs on `stream`
+    (default as decode_device) and waits for it."""
+    planes = [_packed_planes(n, p) for n, p in (("y", y), ("cb", cb), ("cr", cr))]
+    if any(len(shape) != 2 for _, shape in planes):
+        raise FiascoError("planes_to_420_device: three int16 arrays of two dimensions expected")
+    (h, w), sb, sr = planes[0][1], planes[1][1], planes[2][1]
+    if sb != (h // 2, w // 2) or sr != sb:
+        raise FiascoError("planes_to_420_device: chroma planes of %s and %s for a Y plane of %d x %d" % (sb[::-1], sr[::-1], w, h))
+    if target is None:
+        raise FiascoError("planes_to_420_device: no target")
+    arr = _device_targets_420([target], order)
+    if not lib.L.fiasco_amd_planes_to_420_device(planes[0][0], planes[1][0], planes[2][0], w, h, arr, _stream_of(list(target), stream)):
         raise FiascoError(lib.error_message())
 
 

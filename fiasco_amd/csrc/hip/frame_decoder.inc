@@ -39,6 +39,13 @@
  *  magnified frame is fa_smoothing_borders_magnified()'s, and a thumbnail beside a frame is smoothed along the list at
  *  minus its reduction, behind dec_thumb_kernel.  Small planes take sm_frame_kernel, all passes in one launch.
  *
+ *  4:2:0 (fa_dec_job.format_420; include/libfiasco_amd_420.h; enlarge_image with FORMAT_4_2_0, codec/decoder.c:792-838): the
+ *  states behind the Y root get one more step of reduction, so the chroma planes have half the side length and are made of
+ *  states two levels higher in the tree, shown at the same level as the Y tops.  fa_420_plan_of (fa_batch_decode.c) gives
+ *  that level and the coded levels of the tops; the level launches are the ones above; dec_assemble420_kernel places the
+ *  tops in planes Y [H][W], Cb, Cr [H >> 1][W >> 1]; the smoothing list is fa_smoothing_borders_420()'s.  Intra frames, to
+ *  4:2:0 targets (output_convert_420.inc) or to the host; the frames of a call are of one format.
+ *
  *  The decoded planes stay on the device (fa_image.dev): the next P/B frame of the sequence takes its
  *  reference frames with a device-to-device copy (upload_reference); the host copy serves every other caller.
  */
@@ -116,6 +123,25 @@ __global__ void __launch_bounds__(256) dec_assemble_kernel(const DecDesc *__rest
     const unsigned y = t.y0 + (p >> wl), x = t.x0 + (p & ((1u << wl) - 1));
     if (x >= W || y >= H) return;                                  /* the crop of decode_image */
     d.planes[(size_t) t.band * W * H + (size_t) y * W + x] = l ? dec_pixel(d.nodes, d.img, S, (unsigned) t.state, l, p) : d.img[t.state];
+}
+
+/* dec_assemble_kernel for a flight of 4:2:0 frames (include/libfiasco_amd_420.h): the planes are Y [H][W], then Cb and Cr
+ * [H >> 1][W >> 1], and every top goes into the plane of its band with that band's base, pitch and crop -- the chroma
+ * tops are states two levels higher in the tree, decoded at the same level maxl and placed at coordinates the host has
+ * shifted one step further (alloc_state_images, codec/decoder.c:918-937; the crop :502-529) */
+__global__ void __launch_bounds__(256) dec_assemble420_kernel(const DecDesc *__restrict__ descs)
+{
+    const DecDesc d = descs[blockIdx.y];
+    const unsigned l = d.maxl, S = d.S;
+    const size_t idx = (size_t) blockIdx.x * 256 + threadIdx.x;
+    if (idx >= ((size_t) d.ntops << l)) return;
+    const DecTop t = d.tops[idx >> l];
+    const unsigned W = t.band ? d.W >> 1 : d.W, H = t.band ? d.H >> 1 : d.H;
+    const size_t base = t.band ? (size_t) d.W * d.H + (size_t) (t.band - 1) * W * H : 0;
+    const unsigned p = (unsigned) (idx & ((1u << l) - 1)), wl = l >> 1;
+    const unsigned y = t.y0 + (p >> wl), x = t.x0 + (p & ((1u << wl) - 1));
+    if (x >= W || y >= H) return;
+    d.planes[base + (size_t) y * W + x] = l ? dec_pixel(d.nodes, d.img, S, (unsigned) t.state, l, p) : d.img[t.state];
 }
 
 /* the thumbnails of a flight side by side: blockIdx.y = thumbnail.  img, tops: those of the frame's DecDesc; l: the level
@@ -216,6 +242,8 @@ struct DecFrame {                     /* one frame in flight */
     size_t nodes_b = 0, tops_b = 0, mcs_b = 0, img_b = 0, scratch_b = 0;
     unsigned S = 0, maxl = 0, mc_maxl = 0, ntops = 0, nmcs = 0;           /* maxl: the level shown (magnification included) */
     unsigned W = 0, H = 0;            /* the size shown: the coded one, or fiasco_amd_magnified_size() */
+    bool c420 = false;                /* 4:2:0 (fa_dec_job.format_420): the planes are Y [H][W], Cb and Cr [H >> 1][W >> 1] */
+    size_t vals = 0;                  /* the values of all its planes */
     int16_t *thumb = nullptr;         /* a thumbnail beside the frame (dec_flight_thumbs): its reduced planes in the arena */
     size_t thumb_off = 0, thumb_bytes = 0;
     unsigned tw = 0, th = 0;
@@ -258,6 +286,7 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
     unsigned root[3] = { 0, 0, 0 }, maxl = 0, W = j->width, H = j->height;
     const int mag = j->magnify;
     if (mag && j->frame_type != FA_I_FRAME) { dec_fail(j, "device decoder: magnification of intra frames only (the vectors of a P/B frame are not scaled)"); return false; }
+    if (j->format_420 && (j->frame_type != FA_I_FRAME || j->keep_dev)) { dec_fail(j, "device decoder: 4:2:0 for intra frames only (restore_mc scales the vectors per band)"); return false; }
     if (mag && !fiasco_amd_magnified_size(j->width, j->height, mag, &W, &H)) {
         snprintf(j->errmsg, sizeof j->errmsg, "device decoder: magnification %d is out of range for a frame of %u x %u pixels", mag, j->width, j->height);
         j->out = nullptr; return false;
@@ -273,7 +302,18 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
     /* the level shown (the header): the states of level `maxl' at level maxl + 2 mag.  Blocks smaller than the reduction
      * -- the reference clamps their level at 0 and several land on one pixel -- are refused, not reproduced */
     if (mag < 0 && maxl < 2u * (unsigned) -mag) { dec_fail(j, "device decoder: the blocks of the frame are smaller than the reduction (level of the linear combinations below twice the reduction)"); return false; }
-    const unsigned shown = (unsigned) ((int) maxl + 2 * mag);
+    unsigned shown = (unsigned) ((int) maxl + 2 * mag);
+    /* 4:2:0: the level shown and the coded levels of the states the planes are made of come from fa_420_plan_of, which
+     * also refuses what is not reproduced (fa_batch_decode.c) */
+    fa_420_plan plan = { 0, 0, 0 };
+    if (j->format_420) {
+        char why[160];
+        if (!fa_420_plan_of(w, j->color, mag, &plan, why, sizeof why)) {
+            snprintf(j->errmsg, sizeof j->errmsg, "device decoder: %.140s", why);
+            j->out = nullptr; return false;
+        }
+        shown = plan.max_level;
+    }
     if (shown > 24) { dec_fail(j, "device decoder: level of the magnified linear combinations out of range (above 24)"); return false; }
     /* host side of the arithmetic: nodes with integer weights, the lists of blocks */
     std::vector<DecTop> tops;
@@ -281,11 +321,13 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
     for (unsigned s = w->basis_states; s < S; s++) {
         if (j->color && (s == w->root_state || s == (unsigned) FA_TREE(w, w->root_state, 0) || s == (unsigned) FA_TREE(w, w->root_state, 1)))
             continue;
-        if (w->level_of_state[s] == maxl) {
+        const int band = !j->color || s <= root[FA_Y] ? 0 : s > root[FA_CB] ? FA_CR : FA_CB;
+        if (w->level_of_state[s] == (!j->format_420 ? maxl : band ? plan.c_level : plan.y_level)) {
+            const int shift = j->format_420 && band ? mag - 1 : mag;       /* enlarge_image: one step more behind the Y root */
             DecTop t;
             t.state = (int) s; t.x0 = w->x[s * 2]; t.y0 = w->y[s * 2];
-            if (mag > 0) { t.x0 <<= mag; t.y0 <<= mag; } else if (mag < 0) { t.x0 >>= -mag; t.y0 >>= -mag; }
-            t.band = !j->color || s <= root[FA_Y] ? 0 : s > root[FA_CB] ? FA_CR : FA_CB;
+            if (shift > 0) { t.x0 <<= shift; t.y0 <<= shift; } else if (shift < 0) { t.x0 >>= -shift; t.y0 >>= -shift; }
+            t.band = band;
             tops.push_back(t);
         }
     }
@@ -337,7 +379,9 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
     for (unsigned s = 0; s < S; s++) D.px0[s] = dec_fixed_of(w->final_distribution[s]);
 
     const size_t npix = (size_t) W * H;
-    D.plane_bytes = align_up(npix * bands * 2, 256);
+    D.c420 = j->format_420 != 0;
+    D.vals = D.c420 ? npix + 2 * ((size_t) (W >> 1) * (H >> 1)) : npix * bands;
+    D.plane_bytes = align_up(D.vals * 2, 256);
     D.nodes_b = nodes_b; D.tops_b = tops_b; D.mcs_b = mcs_b; D.img_b = img_b;
     D.S = S; D.maxl = shown; D.W = W; D.H = H; D.mc_maxl = mc_maxl; D.ntops = (unsigned) tops.size(); D.nmcs = (unsigned) mcs.size();
     D.own_planes = j->keep_dev != 0;
@@ -350,7 +394,7 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
         for (unsigned l = 0; l < 2; l++) top_terms += dec_terms(nodes[(size_t) tops[k].state * 2 + l], ext);
     const unsigned long long lower = shown ? (((unsigned long long) S << shown) - 2ull * S) : 0ull;
     const unsigned long long lower_reads = shown ? terms * ((1ull << (shown - 1)) - 1) : 0ull;
-    D.bytes = 2ull * (lower + lower_reads + (shown ? top_terms << (shown - 1) : 0ull)) + 2ull * npix * bands;
+    D.bytes = 2ull * (lower + lower_reads + (shown ? top_terms << (shown - 1) : 0ull)) + 2ull * D.vals;
     return true;
 }
 
@@ -442,6 +486,7 @@ struct DecFlight {
     std::vector<size_t>   alive;                /* the frames nothing has failed yet, in order */
     std::vector<DecDesc>  descs;                /* one per frame alive after the uploads: blockIdx.y of the level launches */
     std::vector<OcFrame>  octab; std::vector<DsPlane> dstab;    /* the frames written; the planes measured */
+    std::vector<Y4Frame>  y4tab;                /* ... written as 4:2:0 buffers (OcOut::t420), in place of octab */
     std::vector<DecThumb> thtab; std::vector<OcFrame> thoctab;  /* the thumbnails gathered; written */
     std::vector<SmDesc>   smtab, tsmtab;        /* one per frame (thumbnail) alive and smoothed: first those of the per-pass
                                                  * launches (their blockIdx.y), then those of the fused launch (its blockIdx.x) */
@@ -492,10 +537,15 @@ static bool dec_thumb_prepare(DecShare &S, unsigned job, DecFrame &D)
 /* the borders of the job's partition at `magnify' (fa_smoothing_borders_magnified: the list `dfiasco -m magnify' smooths
  * along), checked against the plane of W x H they will be blended in.  A frame with a state that falls below level 1 at
  * that magnification, and a list that fails the check, fail with the message; an empty list is a plan without passes */
-static bool dec_smooth_plan(fa_dec_job *j, int magnify, unsigned W, unsigned H, SmPlan &P)
+static bool dec_smooth_plan(fa_dec_job *j, int magnify, unsigned W, unsigned H, SmPlan &P, bool c420 = false)
 {
+    /* a 4:2:0 frame: the list of the automaton enlarge_image has shifted for that format (fa_smoothing_borders_420) */
+    auto list = [&](fiasco_amd_border *out, unsigned cap) {
+        return c420 ? fa_smoothing_borders_420(j->wfa, j->width, j->height, j->color, magnify, out, cap)
+                    : fa_smoothing_borders_magnified(j->wfa, j->width, j->height, j->color, magnify, out, cap);
+    };
     fa_set_error("%s", "");
-    const unsigned n = fa_smoothing_borders_magnified(j->wfa, j->width, j->height, j->color, magnify, nullptr, 0);
+    const unsigned n = list(nullptr, 0);
     if (!n) {
         const char *why = fiasco_get_error_message();
         if (!why[0]) return true;
@@ -504,7 +554,7 @@ static bool dec_smooth_plan(fa_dec_job *j, int magnify, unsigned W, unsigned H, 
     }
     P.borders.resize(n);
     char msg[200];
-    if (fa_smoothing_borders_magnified(j->wfa, j->width, j->height, j->color, magnify, P.borders.data(), n) != n) { dec_fail(j, "device decoder: the smoothing borders changed while they were listed"); return false; }
+    if (list(P.borders.data(), n) != n) { dec_fail(j, "device decoder: the smoothing borders changed while they were listed"); return false; }
     if (!sm_check(P.borders.data(), n, W, H, &P.np, &P.pairs, msg, sizeof msg)) { P.np = 0; dec_fail(j, msg); return false; }
     P.b = sm_table_bytes(n, P.np);
     P.fused = sm_takes_fused(P.pairs, P.np);
@@ -524,7 +574,7 @@ static bool dec_smooth_prepare(DecShare &S, unsigned job, DecFrame &D)
     if (j->frame_type != FA_I_FRAME) { dec_fail(j, "device decoder: smoothing of intra frames only"); return false; }
     if (!sm_factors(j->smoothing, &D.sm_is, &D.sm_inegs)) return true;       /* the reference smooths nothing */
     const bool consumed = !S.out || S.ds || S.images || S.out->target[job].data;
-    if (consumed && !dec_smooth_plan(j, j->magnify, D.W, D.H, D.sm)) return false;
+    if (consumed && !dec_smooth_plan(j, j->magnify, D.W, D.H, D.sm, D.c420)) return false;
     if (D.thumb_bytes && !dec_smooth_plan(j, -(int) S.out->reduce, D.tw, D.th, D.tsm)) return false;
     return true;
 }
@@ -539,6 +589,14 @@ static void dec_flight_prepare(DecShare &S, DecFlight &F, const unsigned *idx, s
     bool smooth = false, tsmooth = false;
     for (size_t k = 0; k < n; k++)
         if (dec_prepare(&S.jobs[F.job[k]], F.fr[k]) && (!thumbs || dec_thumb_prepare(S, F.job[k], F.fr[k])) && dec_smooth_prepare(S, F.job[k], F.fr[k])) {
+            /* 4:2:0 planes have consumers of their own -- the 4:2:0 targets of the call, or the host -- and a flight has one
+             * assembly launch: the frames of a call are of one format */
+            const bool c420 = F.fr[k].c420;
+            if ((c420 && (S.ds || S.images || thumbs || (S.out && !S.out->t420))) || (!c420 && S.out && S.out->t420)
+                || (!F.alive.empty() && F.fr[F.alive[0]].c420 != c420)) {
+                dec_fail(&S.jobs[F.job[k]], "device decoder: 4:2:0 frames and 4:4:4 frames do not share a call, and 4:2:0 frames go to 4:2:0 targets or to the host");
+                continue;
+            }
             F.alive.push_back(k); F.fr[k].scratch_off = F.take(F.fr[k].scratch_b);
             smooth = smooth || F.fr[k].sm.np;
             tsmooth = tsmooth || F.fr[k].tsm.np;
@@ -565,7 +623,7 @@ static void dec_flight_prepare(DecShare &S, DecFlight &F, const unsigned *idx, s
         run.push_back(k);
     }
     F.alive.swap(run);
-    F.oc_off = F.take(S.out ? DEC_FLIGHT * sizeof(OcFrame) : 0);
+    F.oc_off = F.take(S.out ? DEC_FLIGHT * (S.out->t420 ? sizeof(Y4Frame) : sizeof(OcFrame)) : 0);
     F.th_off = F.take(thumbs ? DEC_FLIGHT * sizeof(DecThumb) : 0);
     F.thoc_off = F.take(thumbs ? DEC_FLIGHT * sizeof(OcFrame) : 0);
     F.thumb_first = F.need;
@@ -631,7 +689,10 @@ static void dec_flight_levels(DecShare &S, DecFlight &F)
         const size_t n = nlev << l;
         dec_level_kernel<<<dim3((unsigned) ((n + 255) / 256), (unsigned) F.descs.size()), dim3(256), 0, S.stream>>>(dd, l);
     }
-    if (nasm) dec_assemble_kernel<<<dim3((unsigned) ((nasm + 255) / 256), (unsigned) F.descs.size()), dim3(256), 0, S.stream>>>(dd);
+    /* the frames of a call have one format, so a flight has (dec_flight_prepare) */
+    const dim3 grid((unsigned) ((nasm + 255) / 256), (unsigned) F.descs.size());
+    if (nasm && F.fr[F.alive[0]].c420) dec_assemble420_kernel<<<grid, dim3(256), 0, S.stream>>>(dd);
+    else if (nasm) dec_assemble_kernel<<<grid, dim3(256), 0, S.stream>>>(dd);
 }
 
 /* the P/B frames of the flight; one that fails drops out alone */
@@ -754,11 +815,19 @@ static void dec_flight_write(DecShare &S, DecFlight &F)
             oc_describe(F.thoctab.back(), F.fr[k].thumb, S.out->thumb[F.job[k]], thtotal);
         }
         if (!S.out->target[F.job[k]].data) continue;            /* measured only, the thumbnail only, or not this frame */
+        if (S.out->t420) {
+            F.y4tab.emplace_back();
+            y4_describe_packed(F.y4tab.back(), F.fr[k].planes, S.out->t420[F.job[k]], total);
+            continue;
+        }
         F.octab.emplace_back();
         oc_describe(F.octab.back(), F.fr[k].planes, S.out->target[F.job[k]], total);
     }
-    if (F.octab.empty() && F.thoctab.empty()) return;
+    if (F.octab.empty() && F.thoctab.empty() && F.y4tab.empty()) return;
     bool ok = hipStreamWaitEvent(S.stream, S.out->ready, 0) == hipSuccess;
+    if (ok && !F.y4tab.empty())
+        ok = hipMemcpyAsync(S.arena + F.oc_off, F.y4tab.data(), F.y4tab.size() * sizeof(Y4Frame), hipMemcpyHostToDevice, S.stream) == hipSuccess
+             && y4_launch((const Y4Frame *) (S.arena + F.oc_off), (unsigned) F.y4tab.size(), total, oc_cus(), S.stream);
     if (ok && !F.octab.empty())
         ok = hipMemcpyAsync(S.arena + F.oc_off, F.octab.data(), F.octab.size() * sizeof(OcFrame), hipMemcpyHostToDevice, S.stream) == hipSuccess
              && (S.out->render ? rd_launch((const OcFrame *) (S.arena + F.oc_off), (unsigned) F.octab.size(), total, S.out->render, oc_cus(), S.stream)
@@ -782,10 +851,11 @@ static void dec_flight_wait(DecShare &S, DecFlight &F)
 static bool dec_download(DecShare &S, fa_dec_job *j, DecFrame &D)
 {
     fa_image *im = fa_image_alloc(D.W, D.H, j->color);
-    const size_t npix = (size_t) D.W * D.H;
+    const size_t npix = (size_t) D.W * D.H, cpix = D.c420 ? (size_t) (D.W >> 1) * (D.H >> 1) : npix;     /* 4:2:0: the chroma planes at the beginning of theirs */
     bool ok = im != nullptr;
     for (int b = 0; ok && b < (j->color ? 3 : 1); b++)
-        ok = hipMemcpy(im->pixels[b], D.planes + (size_t) b * npix, npix * 2, hipMemcpyDeviceToHost) == hipSuccess;
+        ok = hipMemcpy(im->pixels[b], D.planes + (b ? npix + (size_t) (b - 1) * cpix : 0), (b ? cpix : npix) * 2, hipMemcpyDeviceToHost) == hipSuccess;
+    if (ok) j->out_420 = D.c420;
     if (!ok) { fa_image_free(im); dec_fail(j, "device decoder: download failed"); return false; }
     if (D.own_planes) { im->dev = D.planes; im->dev_id = S.device; D.planes = nullptr; }
     j->out = im;
@@ -807,7 +877,7 @@ static void dec_flight_results(DecShare &S, DecFlight &F)
         fa_dec_job *j = &S.jobs[i];
         DecFrame &D = F.fr[k];
         const unsigned bands = j->color ? 3 : 1;
-        const unsigned long long vals = (unsigned long long) D.W * D.H * bands;
+        const unsigned long long vals = D.vals;
         const bool written = S.out && S.out->target[i].data;
         if (written) S.out->done[i] = 1;
         const unsigned long long tvals = D.thumb ? (unsigned long long) D.tw * D.th * bands : 0ull;     /* gathered: 2 + 2 bytes; written: 2 + 1 */

@@ -158,6 +158,9 @@ struct OcOut {
     /* display surfaces instead of 8-bit pixels (fiasco_amd_batch_decode_device_rendered, render.inc): target[] describes
      * the surfaces (width, height: the frame's) and the flight launches rd_render_kernel; NULL: oc_convert_kernel */
     const fiasco_amd_renderer *render = nullptr;
+    /* 4:2:0 buffers instead (fiasco_amd_batch_decode_device_420, output_convert_420.inc): t420[] are the checked targets
+     * by job index, target[] only says which frames are wanted, and the flight launches oc420_convert_kernel */
+    const fiasco_amd_device_target_420 *t420 = nullptr;
 };
 
 static void oc_describe(OcFrame &d, const int16_t *planes, const fiasco_amd_device_frame &t, unsigned long long &total)
@@ -280,7 +283,8 @@ static bool oc_batch_jobs(const char *who, const char *refuse, const fiasco_amd_
 
 /* the three batch entries: the frames with a target (checked, in B) through the decoder, each at the magnification of
  * its job, and with reduce != 0 the thumbnails of B.thumb beside them */
-static int oc_decode_batch(const char *who, const fiasco_amd_batch_t *b, OcBatch &B, unsigned reduce, void *stream, const fiasco_amd_renderer *render = nullptr)
+static int oc_decode_batch(const char *who, const fiasco_amd_batch_t *b, OcBatch &B, unsigned reduce, void *stream, const fiasco_amd_renderer *render = nullptr,
+                           const fiasco_amd_device_target_420 *t420 = nullptr)
 {
     const unsigned n = b->n;
     std::vector<unsigned char> done(n, 0), thumb_done(n, 0);
@@ -293,7 +297,7 @@ static int oc_decode_batch(const char *who, const fiasco_amd_batch_t *b, OcBatch
     OcOut out;
     out.target = B.target.data(); out.done = done.data(); out.caller = (hipStream_t) stream;
     if (reduce) { out.thumb = B.thumb.data(); out.thumb_done = thumb_done.data(); out.reduce = reduce; }
-    out.render = render;
+    out.render = render; out.t420 = t420;
     out.ready = ic_mark_ready(stream);
     if (!out.ready) return 0;
     const int good = decode_frames(n, B.jobs.data(), &out, nullptr);

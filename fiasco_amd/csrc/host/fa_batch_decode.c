@@ -15,6 +15,7 @@
 #include "fa_host.h"
 #include "libfiasco_amd_hip.h"
 #include "libfiasco_amd_display.h"
+#include "libfiasco_amd_420.h"
 
 /* The guard of every outlet `who': the finished intra job of frame i, or NULL + message.  `usable': the caller's own
  * precondition (an output buffer), refused in the same words as a missing automaton.  `why' ends the refusal of a P/B
@@ -258,12 +259,12 @@ int fiasco_amd_magnified_size(unsigned width, unsigned height, int magnify, unsi
  * horizontally (rows y - 1 and y, `len' columns from x), even levels vertically (columns x - 1 and x, `len' rows from
  * y); len is the block's side, clipped at the frame.  Returns the number of borders; out may be NULL (count only);
  * more than cap: 0 + message. */
-/* The list at magnification `mag', against the size shown (width x height are the magnified ones): what smooth_image
+/* The list at magnification `mag_y' (the Cb phase: `mag_cb', the same but for a 4:2:0 frame), against the size shown (width x height are the magnified ones): what smooth_image
  * walks after enlarge_image (codec/decoder.c:776-840) has added 2 mag to the level of every state and shifted its
  * coordinates by mag.  Same phases, same order.  *low: set to 1 + the coded level of the first visible state whose shifted
  * level falls below 1 (the caller refuses the frame); such a state is not listed. */
-static unsigned borders_at(const fa_wfa *w, unsigned width, unsigned height, int color, int mag, fiasco_amd_border *out, unsigned cap,
-                           unsigned *low)
+static unsigned borders_at(const fa_wfa *w, unsigned width, unsigned height, int color, int mag_y, int mag_cb, fiasco_amd_border *out, unsigned cap,
+                           unsigned *low, int *low_mag)
 {
     unsigned from[2], to[2], phases = 1, phase, n = 0, pass = 0;
     from[0] = w->basis_states; to[0] = w->states;
@@ -274,6 +275,7 @@ static unsigned borders_at(const fa_wfa *w, unsigned width, unsigned height, int
         phases = 2;
     }
     for (phase = 0; phase < phases; phase++) {
+        const int mag = phase ? mag_cb : mag_y;
         int level, maxl = 0;
         unsigned s;
         for (s = from[phase]; s < to[phase]; s++) if ((int) w->level_of_state[s] + 2 * mag > maxl) maxl = (int) w->level_of_state[s] + 2 * mag;
@@ -286,7 +288,7 @@ static unsigned borders_at(const fa_wfa *w, unsigned width, unsigned height, int
                 const unsigned y = mag >= 0 ? (unsigned) w->y[s * 2 + 1] << mag : (unsigned) w->y[s * 2 + 1] >> -mag;
                 unsigned room;
                 if ((shifted < 1 ? 0 : shifted) != level || y >= height || x >= width) continue;
-                if (shifted < 1) { if (!*low) *low = 1u + w->level_of_state[s]; continue; }
+                if (shifted < 1) { if (!*low) { *low = 1u + w->level_of_state[s]; *low_mag = mag; } continue; }
                 if (level & 1 ? !y : !x) continue;
                 room = level & 1 ? width - x : height - y;
                 if (out) {
@@ -314,10 +316,11 @@ static unsigned borders_magnified(const fa_wfa *w, unsigned width, unsigned heig
                                   unsigned cap, const char *who)
 {
     unsigned mw = width, mh = height, low = 0, n;
+    int low_mag = 0;
     if (!magnify) return fa_smoothing_borders(w, width, height, color, out, cap);
     if (!fiasco_amd_magnified_size(width, height, magnify, &mw, &mh)) return 0;
     if (magnify > 8) { fa_set_error("%s: magnification %d: the borders of the frame do not fit 16-bit coordinates", who, magnify); return 0; }
-    n = borders_at(w, mw, mh, color, magnify, out, cap, &low);
+    n = borders_at(w, mw, mh, color, magnify, magnify, out, cap, &low, &low_mag);
     if (low) {
         fa_set_error("%s: at magnification %d a smoothed state of level %u falls to level %d (below 1), where the "
                      "reference's own result is undefined", who, magnify, low - 1, (int) low - 1 + 2 * magnify);
@@ -381,4 +384,123 @@ int fiasco_amd_batch_smoothing_borders_magnified(const fiasco_amd_batch_t *b, un
     if (!job) return 0;
     snprintf(who, sizeof who, "fiasco_amd_batch_smoothing_borders_magnified: frame %u", i);
     return (int) borders_magnified(job->wfa, job->image->width, job->image->height, job->image->color, magnify, out, cap, who);
+}
+
+/* ---------------------------------------------------------------- 4:2:0 (include/libfiasco_amd_420.h) */
+
+/* What decode_image (codec/decoder.c:411-536) makes of the automaton once enlarge_image (:776-840) has shifted it for
+ * FORMAT_4_2_0: see fa_host.h.  The states of a band cover every level from the largest range level up to the band's
+ * root, so a band has a state at a level exactly when its root is not below it. */
+int fa_420_plan_of(const fa_wfa *w, int color, int magnify, fa_420_plan *plan, char *msg, size_t msg_size)
+{
+    unsigned r0, r1, root[3], s, lc[2] = { 0, 0 }, have[2] = { 0, 0 }, found[3] = { 0, 0, 0 };
+    const int shift[2] = { 2 * magnify, 2 * magnify - 2 };
+    int top = -1, band, y_level, c_level;
+    if (!color) { snprintf(msg, msg_size, "4:2:0: a gray frame has no chroma bands"); return 0; }
+    r0 = (unsigned) FA_TREE(w, w->root_state, 0); r1 = (unsigned) FA_TREE(w, w->root_state, 1);
+    root[0] = (unsigned) FA_TREE(w, r0, 0); root[1] = (unsigned) FA_TREE(w, r0, 1); root[2] = (unsigned) FA_TREE(w, r1, 0);
+    for (s = w->basis_states; s < w->states; s++) {
+        if (s == w->root_state || s == r0 || s == r1) continue;
+        if (FA_INTO(w, s, 0, 0) == FA_NO_EDGE && FA_INTO(w, s, 1, 0) == FA_NO_EDGE) continue;
+        band = s > root[0];
+        have[band] = 1;
+        if (w->level_of_state[s] > lc[band]) lc[band] = w->level_of_state[s];
+    }
+    for (band = 0; band < 2; band++) {
+        if (!have[band]) continue;
+        if ((int) lc[band] + shift[band] < 0) {
+            snprintf(msg, msg_size, "4:2:0: the blocks of the %s are smaller than the reduction (level of the linear combinations %u below "
+                     "twice the reduction %d)", band ? "chroma bands" : "Y band", lc[band], -shift[band] / 2);
+            return 0;
+        }
+        if ((int) lc[band] + shift[band] > top) top = (int) lc[band] + shift[band];
+    }
+    if (top < 0) { snprintf(msg, msg_size, "4:2:0: no state with a linear combination"); return 0; }
+    if (top > 24) { snprintf(msg, msg_size, "4:2:0: level of the magnified linear combinations out of range (above 24)"); return 0; }
+    y_level = top - shift[0]; c_level = top - shift[1];
+    if (y_level < 0 || c_level < 0) { snprintf(msg, msg_size, "4:2:0: the blocks of the frame are smaller than the reduction"); return 0; }
+    for (s = w->basis_states; s < w->states; s++) {
+        if (s == w->root_state || s == r0 || s == r1) continue;
+        band = s <= root[0] ? 0 : s <= root[1] ? 1 : 2;
+        if ((int) w->level_of_state[s] == (band ? c_level : y_level)) found[band] = 1;
+    }
+    if (!found[0]) {
+        snprintf(msg, msg_size, "4:2:0: max_level %d at magnification %d takes Y states of level %d, the Y root has level %u: the "
+                 "reference's Y plane stays zero there", top, magnify, y_level, (unsigned) w->level_of_state[root[0]]);
+        return 0;
+    }
+    if (!found[1] || !found[2]) {
+        snprintf(msg, msg_size, "4:2:0: max_level %d at magnification %d takes chroma states of level %d, the chroma root has level %u: "
+                 "the reference's chroma planes stay zero there", top, magnify, c_level, (unsigned) w->level_of_state[root[found[1] ? 2 : 1]]);
+        return 0;
+    }
+    plan->max_level = (unsigned) top; plan->y_level = (unsigned) y_level; plan->c_level = (unsigned) c_level;
+    return 1;
+}
+
+/* the list smooth_image walks on the automaton enlarge_image has shifted for FORMAT_4_2_0 */
+static unsigned borders_420(const fa_wfa *w, unsigned width, unsigned height, int color, int magnify, fiasco_amd_border *out, unsigned cap,
+                            const char *who)
+{
+    unsigned mw = width, mh = height, low = 0, n;
+    int low_mag = 0;
+    fa_420_plan plan;
+    char msg[200];
+    if (magnify && !fiasco_amd_magnified_size(width, height, magnify, &mw, &mh)) return 0;
+    if (!fa_420_plan_of(w, color, magnify, &plan, msg, sizeof msg)) { fa_set_error("%s: %s", who, msg); return 0; }
+    if (magnify > 8) { fa_set_error("%s: magnification %d: the borders of the frame do not fit 16-bit coordinates", who, magnify); return 0; }
+    n = borders_at(w, mw, mh, color, magnify, magnify - 1, out, cap, &low, &low_mag);
+    if (low) {
+        fa_set_error("%s: in 4:2:0 at magnification %d a smoothed state of level %u falls to level %d (below 1), where the "
+                     "reference's own result is undefined", who, magnify, low - 1, (int) low - 1 + 2 * low_mag);
+        return 0;
+    }
+    return n;
+}
+
+unsigned fa_smoothing_borders_420(const fa_wfa *w, unsigned width, unsigned height, int color, int magnify, fiasco_amd_border *out, unsigned cap)
+{
+    return borders_420(w, width, height, color, magnify, out, cap, "smoothing borders");
+}
+
+int fiasco_amd_batch_smoothing_borders_420(const fiasco_amd_batch_t *b, unsigned i, int magnify, fiasco_amd_border *out, unsigned cap)
+{
+    const fa_job *job = finished_intra(b, i, 1, "fiasco_amd_batch_smoothing_borders_420", "", 0);
+    char who[80];
+    if (!job) return 0;
+    snprintf(who, sizeof who, "fiasco_amd_batch_smoothing_borders_420: frame %u", i);
+    return (int) borders_420(job->wfa, job->image->width, job->image->height, job->image->color, magnify, out, cap, who);
+}
+
+int fiasco_amd_batch_decode_planes_420(const fiasco_amd_batch_t *b, unsigned i, int magnify, int16_t *out)
+{
+    const char *who = "fiasco_amd_batch_decode_planes_420";
+    const fa_job *job = finished_intra(b, i, out != NULL, who, NEEDS_REFERENCES, 0);
+    unsigned w, h;
+    size_t npix, cpix;
+    fa_420_plan plan;
+    fa_dec_job d;
+    char msg[200];
+    if (!job) return 0;
+    w = job->image->width; h = job->image->height;
+    if (magnify && !fiasco_amd_magnified_size(w, h, magnify, &w, &h)) return 0;
+    if (!fa_420_plan_of(job->wfa, job->image->color, magnify, &plan, msg, sizeof msg)) { fa_set_error("%s: frame %u: %s", who, i, msg); return 0; }
+    fa_dec_job_of(job, magnify, &d);
+    d.format_420 = 1;
+    if (fa_core_decode_frames(1, &d) != 1 || !d.out) {
+        fa_set_error("%s", d.errmsg[0] ? d.errmsg : "decoder failed");
+        return 0;
+    }
+    if (!d.out_420 || d.out->width != w || d.out->height != h) {
+        fa_set_error("%s: the decoder of this library (%s) does not decode 4:2:0: it handed back a 4:4:4 frame of %u x %u pixels",
+                     who, fa_core_name(), d.out->width, d.out->height);
+        fa_image_free(d.out);
+        return 0;
+    }
+    npix = (size_t) w * h; cpix = (size_t) (w >> 1) * (h >> 1);
+    memcpy(out, d.out->pixels[0], npix * 2);
+    memcpy(out + npix, d.out->pixels[1], cpix * 2);
+    memcpy(out + npix + cpix, d.out->pixels[2], cpix * 2);
+    fa_image_free(d.out);
+    return 1;
 }

@@ -204,6 +204,10 @@ typedef struct fa_dec_job {
     const fa_image *orig;                 /* in: the original the frame is measured against (sse or maxdiff given) */
     void           *consumer_stream;      /* in: the caller's hipStream_t, as fiasco_amd_batch_decode_device() takes it */
     int             delivered;            /* out: 1 once every consumer the job names has had the frame */
+    int             format_420;           /* in: decode in 4:2:0 (include/libfiasco_amd_420.h; fa_420_plan_of below): colour intra frames.
+                                           * out then has Y at full size and, at the BEGINNING of pixels[1] and pixels[2], the packed
+                                           * chroma planes of (width >> 1) x (height >> 1) values.  The test oracle does not know the field */
+    int             out_420;              /* out: 1 where `out' is such a frame: callers check it as they check the size */
     int             smoothing;            /* in: blend the Y plane along the borders of the partition before any consumer sees the
                                            * frame (smooth_image, codec/decoder.c:674-768; csrc/hip/smooth.inc): 0 nothing, 1 .. 100
                                            * that percentage (dfiasco -s N); -1 stands for the value of the frame's stream header
@@ -219,6 +223,18 @@ unsigned fa_smoothing_borders(const fa_wfa *w, unsigned width, unsigned height, 
  * 0 + message: the size rule refuses the magnification, or a smoothed state falls below level 1 */
 unsigned fa_smoothing_borders_magnified(const fa_wfa *w, unsigned width, unsigned height, int color, int magnify, fiasco_amd_border *out,
                                         unsigned cap);
+/* 4:2:0 (include/libfiasco_amd_420.h; enlarge_image / decode_image / alloc_state_images of codec/decoder.c with
+ * FORMAT_4_2_0): at magnification `magnify' a Y state is shown at its coded level + 2 magnify, a chroma state at its coded
+ * level + 2 magnify - 2.  max_level: the largest shown level of a state with a linear combination, the level every top
+ * image is decoded at; y_level, c_level: the CODED level of the states the Y plane and the chroma planes are made of.
+ * 0 + msg: a gray frame, a band whose shown level would be clamped at 0, a level out of range, or a band without a state
+ * at that level (the reference hands out zeros there) */
+typedef struct fa_420_plan { unsigned max_level, y_level, c_level; } fa_420_plan;
+int fa_420_plan_of(const fa_wfa *w, int color, int magnify, fa_420_plan *plan, char *msg, size_t msg_size);
+/* the borders of the 4:2:0 frame at `magnify': the Y phase at shift magnify, the Cb phase at shift magnify - 1, against the
+ * size shown (width x height: the coded size).  0 + message as fa_smoothing_borders_magnified */
+unsigned fa_smoothing_borders_420(const fa_wfa *w, unsigned width, unsigned height, int color, int magnify, fiasco_amd_border *out,
+                                  unsigned cap);
 void fa_core_release_dev(void *dev, int dev_id);
 
 /* ---------------- stream info (reference codec/wfa.h:65-110 wfa_info_t) ----------- */
