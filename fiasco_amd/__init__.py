@@ -55,6 +55,13 @@ class DeviceTarget420(ctypes.Structure):
                 ("c_pitch", ctypes.c_size_t), ("c_step", ctypes.c_uint), ("width", ctypes.c_uint), ("height", ctypes.c_uint)]
 
 
+class YCbCrFrame(ctypes.Structure):
+    """struct fiasco_amd_ycbcr_frame (include/libfiasco_amd_ycbcr.h): a frame that is YCbCr already, in host or device memory."""
+    _fields_ = [("y", ctypes.c_void_p), ("y_pitch", ctypes.c_size_t), ("cb", ctypes.c_void_p), ("cr", ctypes.c_void_p),
+                ("c_pitch", ctypes.c_size_t), ("c_step", ctypes.c_uint), ("subsampling", ctypes.c_uint),
+                ("width", ctypes.c_uint), ("height", ctypes.c_uint)]
+
+
 class SeqOutputs(ctypes.Structure):
     """struct fiasco_amd_seq_outputs (include/libfiasco_amd_video.h)."""
     _fields_ = [("targets", ctypes.POINTER(DeviceTarget)), ("sse", ctypes.POINTER(ctypes.c_ulonglong)),
@@ -251,12 +258,29 @@ def _yuv420_abi():
     }
 
 
+def _ycbcr_abi():
+    """the same for include/libfiasco_amd_ycbcr.h: NV12 / NV21 / I420 / planar 4:4:4 frames into the coder (the host entries
+    in host code, which every build of the library has; the kernel and the device entries in the HIP library)"""
+    c = ctypes
+    P, ptr, i, u, f32, frames = c.POINTER, c.c_void_p, c.c_int, c.c_uint, c.c_float, c.POINTER(YCbCrFrame)
+    return {
+        "fiasco_amd_batch_stage_ycbcr": (ptr, [u, frames, f32, ptr]),
+        "fiasco_amd_seq_open_ycbcr": (ptr, [u, frames, f32, ptr, u, u]),
+        "fiasco_amd_batch_stage_device_ycbcr": (ptr, [u, frames, ptr, f32, ptr]),
+        "fiasco_amd_batch_upload_device_ycbcr": (i, [ptr, frames, ptr]),
+        "fiasco_amd_seq_open_device_ycbcr": (ptr, [u, frames, ptr, f32, ptr, u, u]),
+    }
+
+
 _SIGNATURES = _abi()
 _VIDEO_SIGNATURES = _video_abi()
 _SMOOTH_SIGNATURES = _smooth_abi()
 _DISPLAY_SIGNATURES = _display_abi()
 _RENDER_SIGNATURES = _render_abi()
 _YUV420_SIGNATURES = _yuv420_abi()
+_YCBCR_SIGNATURES = _ycbcr_abi()
+# every symbol include/libfiasco_amd_ycbcr.h declares
+YCBCR_SYMBOLS = list(_YCBCR_SIGNATURES)
 # every symbol include/libfiasco_amd_420.h declares
 YUV420_SYMBOLS = list(_YUV420_SIGNATURES)
 # every symbol include/libfiasco_amd_render.h declares
@@ -292,7 +316,7 @@ class Library:
             raise FiascoError("%s is missing: run fiasco_amd.build() (there is no fallback)" % path)
         self.path = path
         self.L = ctypes.CDLL(path)
-        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VIDEO_SIGNATURES.items()) + list(_SMOOTH_SIGNATURES.items()) + list(_DISPLAY_SIGNATURES.items()) + list(_RENDER_SIGNATURES.items()) + list(_YUV420_SIGNATURES.items()):      # the one place that declares the ABI to ctypes
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VIDEO_SIGNATURES.items()) + list(_SMOOTH_SIGNATURES.items()) + list(_DISPLAY_SIGNATURES.items()) + list(_RENDER_SIGNATURES.items()) + list(_YUV420_SIGNATURES.items()) + list(_YCBCR_SIGNATURES.items()):      # the one place that declares the ABI to ctypes
             if hasattr(self.L, name):
                 fn = getattr(self.L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -435,6 +459,61 @@ class Batch:
         self._keep = frames
         self._geom = [(a.width, a.height, 1 if a.layout == FIASCO_AMD_GRAY8 else 3) for a in arr]
         return self
+
+    @classmethod
+    def from_ycbcr(cls, lib, frames, quality=20.0, options=None, order="nv12"):
+        """fiasco_amd_batch_stage_ycbcr: a batch of frames that are YCbCr already, in host memory (every build of the
+        library).  A frame is (y, cb, cr), three 2-D numpy uint8 arrays -- chroma of H/2 x W/2 is 4:2:0 (I420; YV12 with cb
+        and cr exchanged), of H x W 4:4:4 --, or (y, cbcr) with cbcr of shape H/2 x W/2 x 2: interleaved pairs, Cb first for
+        order="nv12", Cr first for order="nv21".  Pitches come from the strides.  The planes the coder sees are
+        (byte - 128) * 16, a 4:2:0 chroma sample replicated over its 2 x 2 pixels; the frames are converted during the call."""
+        self = cls.__new__(cls)
+        self.lib = lib
+        frames = [tuple(f) for f in frames]
+        self.n = len(frames)
+        self._keep = None
+        arr = _ycbcr_frames(frames, order, "__array_interface__")
+        if not hasattr(lib.L, "fiasco_amd_batch_stage_ycbcr"):
+            raise FiascoError("%s has no fiasco_amd_batch_stage_ycbcr" % lib.path)
+        self.handle = lib.L.fiasco_amd_batch_stage_ycbcr(self.n, arr, ctypes.c_float(quality), options.handle if options else None)
+        if not self.handle:
+            raise FiascoError(lib.error_message())
+        self._geom = [(a.width, a.height, 3) for a in arr[:self.n]]
+        return self
+
+    @classmethod
+    def from_device_ycbcr(cls, lib, frames, quality=20.0, options=None, stream=None, order="nv12"):
+        """fiasco_amd_batch_stage_device_ycbcr: from_ycbcr with frames that live in device memory -- torch uint8 tensors on
+        the GPU or anything with __cuda_array_interface__, for instance what decode_420 filled -- read in place by one
+        kernel launch per device share.  `stream` as from_device.  The objects are kept alive until the next upload or
+        free()."""
+        if not hasattr(lib.L, "fiasco_amd_batch_stage_device_ycbcr"):
+            raise FiascoError("%s has no fiasco_amd_batch_stage_device_ycbcr: frames in device memory need the HIP library" % lib.path)
+        self = cls.__new__(cls)
+        self.lib = lib
+        frames = [tuple(f) for f in frames]
+        self.n = len(frames)
+        arr = _ycbcr_frames(frames, order, "__cuda_array_interface__")
+        flat = [a for f in frames for a in f]
+        self.handle = lib.L.fiasco_amd_batch_stage_device_ycbcr(self.n, arr, _stream_of(flat, stream), ctypes.c_float(quality),
+                                                                options.handle if options else None)
+        if not self.handle:
+            raise FiascoError(lib.error_message())
+        self._keep = frames
+        self._geom = [(a.width, a.height, 3) for a in arr[:self.n]]
+        return self
+
+    def upload_device_ycbcr(self, frames, stream=None, order="nv12"):
+        """fiasco_amd_batch_upload_device_ycbcr: upload_device with YCbCr frames (see from_device_ycbcr); may follow and be
+        followed by upload() and upload_device()."""
+        frames = [tuple(f) for f in frames]
+        if len(frames) != self.n:
+            raise FiascoError("upload_device_ycbcr: %d frames for a batch of %d" % (len(frames), self.n))
+        arr = _ycbcr_frames(frames, order, "__cuda_array_interface__")
+        flat = [a for f in frames for a in f]
+        if not self.lib.L.fiasco_amd_batch_upload_device_ycbcr(self.handle, arr, _stream_of(flat, stream)):
+            raise FiascoError(self.lib.error_message())
+        self._keep = frames
 
     def upload_device(self, frames, stream=None):
         """fiasco_amd_batch_upload_device: new frames for every slot, converted on the device from where they lie
@@ -844,6 +923,61 @@ def _device_targets_420(targets, order="nv12"):
     return arr
 
 
+def _byte_plane(i, what, a, ndim, iface):
+    """(address, shape, strides) of one uint8 array of `ndim` dimensions whose innermost elements are adjacent, read through
+    `iface` (__array_interface__: host memory, __cuda_array_interface__: device memory)"""
+    d = getattr(a, iface, None)
+    if d is None:
+        raise FiascoError("frame %d: the %s is not in %s memory (no %s)"
+                          % (i, what, "device" if "cuda" in iface else "host", iface))
+    if d["typestr"] not in ("|u1", "<u1", ">u1", "=u1"):
+        raise FiascoError("frame %d: the %s holds %s, not bytes (uint8)" % (i, what, d["typestr"]))
+    shape = tuple(int(v) for v in d["shape"])
+    if len(shape) != ndim:
+        raise FiascoError("frame %d: the %s has shape %s, %d dimensions expected" % (i, what, shape, ndim))
+    strides = d.get("strides")
+    strides = tuple(int(v) for v in (strides if strides is not None else _packed_strides(shape)))
+    if strides[-1] != 1 or (ndim == 3 and strides[1] != 2) or strides[0] <= 0:
+        raise FiascoError("frame %d: the strides %s of the %s cannot be described by a pitch" % (i, strides, what))
+    return int(d["data"][0]), shape, strides
+
+
+def _ycbcr_frames(frames, order, iface):
+    """The fiasco_amd_ycbcr_frame array of a list of frames: (y, cb, cr), three 2-D arrays, or (y, cbcr) with cbcr of shape
+    H/2 x W/2 x 2 and `order` "nv12" (Cb first) or "nv21" -- what _device_targets_420 accepts; `order` may also be a list, one
+    entry per frame.  The subsampling is inferred
+    from the chroma shape: full size is 4:4:4, half size 4:2:0, anything else raises."""
+    orders = [order] * len(frames) if isinstance(order, str) else list(order)
+    if len(orders) != len(frames):
+        raise FiascoError("%d orders for %d frames" % (len(orders), len(frames)))
+    arr = (YCbCrFrame * max(len(frames), 1))()
+    for i, t in enumerate(frames):
+        order = orders[i]
+        if order not in ("nv12", "nv21"):
+            raise FiascoError("order %r is neither \"nv12\" nor \"nv21\"" % (order,))
+        if len(t) not in (2, 3):
+            raise FiascoError("frame %d: (y, cb, cr) or (y, cbcr) expected, not %d arrays" % (i, len(t)))
+        d = arr[i]
+        y, (h, w), ys = _byte_plane(i, "Y plane", t[0], 2, iface)
+        d.y, d.y_pitch, d.width, d.height = y, ys[0], w, h
+        if len(t) == 3:
+            (cb, sb, stb), (cr, sr, str_) = _byte_plane(i, "Cb plane", t[1], 2, iface), _byte_plane(i, "Cr plane", t[2], 2, iface)
+            if sr != sb or sb not in ((h, w), (h // 2, w // 2)):
+                raise FiascoError("frame %d: chroma planes of %s and %s for a Y plane of %d x %d (%d x %d for 4:4:4 or %d x %d for 4:2:0 expected)"
+                                  % (i, sb[::-1], sr[::-1], w, h, w, h, w // 2, h // 2))
+            if stb[0] != str_[0]:
+                raise FiascoError("frame %d: the chroma planes have pitches %d and %d (one pitch expected)" % (i, stb[0], str_[0]))
+            d.cb, d.cr, d.c_pitch, d.c_step, d.subsampling = cb, cr, stb[0], 1, 0 if sb == (h, w) else 1
+        else:
+            c, sc, stc = _byte_plane(i, "chroma plane", t[1], 3, iface)
+            if sc != (h // 2, w // 2, 2):
+                raise FiascoError("frame %d: an interleaved chroma plane of shape %s for a Y plane of %d x %d (%d x %d x 2 expected)"
+                                  % (i, sc, w, h, h // 2, w // 2))
+            d.cb, d.cr = (c, c + 1) if order == "nv12" else (c + 1, c)
+            d.c_pitch, d.c_step, d.subsampling = stc[0], 2, 1
+    return arr
+
+
 def _device_surfaces(surfaces, bpp):
     """The fiasco_amd_device_surface array of a list of writable uint8 GPU arrays of shape (H, W, bpp // 8); the pitch is the
     first stride, the other two must be bpp // 8 and 1; None: data = NULL, skipped."""
@@ -1074,6 +1208,45 @@ class Sequence:
         if not self.handle:
             raise FiascoError(lib.error_message())
         self._geom = (arr[0].width, arr[0].height, 1 if arr[0].layout == FIASCO_AMD_GRAY8 else 3)
+        self._opened(len(frames), rank, world)
+        return self
+
+    @classmethod
+    def from_ycbcr(cls, lib, frames, quality=20.0, options=None, rank=0, world=1, order="nv12"):
+        """fiasco_amd_seq_open_ycbcr: a video of frames that are YCbCr already, in host memory and display order; frames as
+        Batch.from_ycbcr takes them.  The frames are converted during the call."""
+        if not hasattr(lib.L, "fiasco_amd_seq_open_ycbcr"):
+            raise FiascoError("%s has no fiasco_amd_seq_open_ycbcr" % lib.path)
+        self = cls.__new__(cls)
+        self.L, self.lib = lib.L, lib
+        frames = [tuple(f) for f in frames]
+        arr = _ycbcr_frames(frames, order, "__array_interface__")
+        self._keep = (None, options)
+        self.handle = lib.L.fiasco_amd_seq_open_ycbcr(len(frames), arr, ctypes.c_float(quality), options.handle if options else None,
+                                                      rank, world)
+        if not self.handle:
+            raise FiascoError(lib.error_message())
+        self._geom = (arr[0].width, arr[0].height, 3)
+        self._opened(len(frames), rank, world)
+        return self
+
+    @classmethod
+    def from_device_ycbcr(cls, lib, frames, quality=20.0, options=None, rank=0, world=1, stream=None, order="nv12"):
+        """fiasco_amd_seq_open_device_ycbcr: from_device with frames that are YCbCr already, as Batch.from_device_ycbcr takes
+        them.  Open converts the frames this rank searches and waits for that."""
+        if not hasattr(lib.L, "fiasco_amd_seq_open_device_ycbcr"):
+            raise FiascoError("%s has no fiasco_amd_seq_open_device_ycbcr: videos in device memory need the HIP library" % lib.path)
+        self = cls.__new__(cls)
+        self.L, self.lib = lib.L, lib
+        frames = [tuple(f) for f in frames]
+        arr = _ycbcr_frames(frames, order, "__cuda_array_interface__")
+        self._keep = (frames, options)
+        flat = [a for f in frames for a in f]
+        self.handle = lib.L.fiasco_amd_seq_open_device_ycbcr(len(frames), arr, _stream_of(flat, stream), ctypes.c_float(quality),
+                                                             options.handle if options else None, rank, world)
+        if not self.handle:
+            raise FiascoError(lib.error_message())
+        self._geom = (arr[0].width, arr[0].height, 3)
         self._opened(len(frames), rank, world)
         return self
 

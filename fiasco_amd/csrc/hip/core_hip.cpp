@@ -42,6 +42,7 @@
 #include "libfiasco_amd_display.h"
 #include "libfiasco_amd_render.h"
 #include "libfiasco_amd_420.h"
+#include "libfiasco_amd_ycbcr.h"
 
 /* Developer and test switches (FIASCO_AMD_SPEC, _NO_WIDE, _FORCE_TRI, _CAP_GUESS, _QUEUE_SLABS, _TRACE, ...)
  * are honoured only when FIASCO_AMD_DEBUG is set to something other than 0: a drop-in library must not
@@ -119,8 +120,33 @@ template <typename T> static bool grow_buffer(T *&p, size_t &n, size_t need, boo
 /* ------------------------------------------------------------------ the parts
  * What one of them uses of a later one: */
 struct Staged;                                  /* enc_stage.inc */
-/* input_convert.inc: the planes of every slot's frame from 8-bit pixels in device memory into up_dev[parity] */
-static bool ic_convert(Staged *S, const fiasco_amd_device_frame *frames, int parity, hipEvent_t ready, bool next, bool prepare_only);
+/* input_convert.inc: the planes of every slot's frame from 8-bit pixels in device memory into up_dev[parity].  The frames
+ * of a call are of ONE kind -- gray / RGB (fiasco_amd_device_frame, ic_convert_kernel) or YCbCr (fiasco_amd_ycbcr_frame,
+ * input_convert_ycbcr.inc icy_convert_kernel) -- and everything between the entry points and the launch sees them through
+ * the kind: "describe this frame" and "launch" */
+struct IcKind {
+    const char *what;               /* "device frame", "YCbCr frame": how the messages name a frame */
+    size_t frame_bytes;             /* the caller's struct, checked and with its pitches filled in */
+    size_t entry_bytes;             /* the kernel's descriptor of a frame */
+    void (*geometry)(const void *frame, unsigned *width, unsigned *height, int *color);
+    int  (*device_of)(const void *frame);           /* where the pixels lie; -1: unknown */
+    /* what to fetch over the peer link first when that is another device: bytes from *first on; 0: the kind has no peer copy */
+    size_t (*peer_extent)(const void *frame, const void **first);
+    /* the table entry of `frame', read at src (NULL: where the frame says; else a copy of peer_extent bytes) and written to
+     * dst; total: the work items of the frames before it, moved on */
+    void (*describe)(void *entry, const void *frame, const void *src, int16_t *dst, unsigned long long &total);
+    /* ONE launch for the n frames of the table at d_tab (device memory) on `stream' */
+    bool (*launch)(const void *d_tab, unsigned n, unsigned long long total, int ncu, hipStream_t stream);
+};
+/* room for a table entry of either kind: a share's table is allocated for this size per frame, so that uploads of both
+ * kinds may follow one another without the table ever being freed and allocated again on the hot call */
+enum { IC_ENTRY_MAX = 96 };
+struct IcInput {
+    const IcKind *kind;
+    const void   *frames;           /* one per job, kind->frame_bytes apart */
+    const void *at(size_t i) const { return (const char *) frames + i * kind->frame_bytes; }
+};
+static bool ic_convert(Staged *S, const IcInput &in, int parity, hipEvent_t ready, bool next, bool prepare_only);
 
 #include "log2_table.inc"       /* log2 on the device against the host's: self test kernel, comparison, correction table, its disk cache */
 #include "slab_pool.inc"        /* the pool of HBM slabs of a device: pool_device, slab_acquire, slab_release */
@@ -142,6 +168,7 @@ struct DsOut;                                   /* distortion.inc */
 static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const DsOut *ds, bool images = false);      /* frame_decoder.inc */
 
 #include "input_convert.inc"
+#include "input_convert_ycbcr.inc" /* beside input_convert.inc: NV12 / NV21 / I420 / planar 4:4:4 bytes instead of gray and RGB, through the same plumbing */
 #include "output_convert.inc"
 #include "distortion.inc"
 #include "smooth.inc"

@@ -75,8 +75,8 @@ struct Staged {
     hipEvent_t  ev_up = nullptr;
     /* frames handed over in device memory (input_convert.inc): the descriptor table of the conversion kernel, pinned
      * on the host and on the device, the event after its copy, and the staging buffer for sources of another device */
-    struct IcFrame *ic_tab = nullptr, *d_ic = nullptr;
-    size_t ic_cap = 0;
+    char  *ic_tab = nullptr, *d_ic = nullptr;     /* entries of the kind's descriptor (IcKind::entry_bytes) */
+    size_t ic_cap = 0;                            /* bytes: IC_ENTRY_MAX per slot, whatever the kind */
     hipEvent_t  ev_ic = nullptr;
     char  *peer_buf = nullptr;
     size_t peer_bytes = 0;
@@ -608,9 +608,9 @@ static void stage_frames(Staged *S)
     }
 }
 
-/* frames != NULL: frames[i] is the 8-bit picture of jobs[i] in device memory (jobs[i].image has no host planes), ready
+/* frames != NULL: frames->at(i) is the 8-bit picture of jobs[i] in device memory (jobs[i].image has no host planes), ready
  * once `ready' has happened */
-static void *core1_stage(unsigned n, fa_job *jobs, const fiasco_amd_device_frame *frames = nullptr, hipEvent_t ready = nullptr)
+static void *core1_stage(unsigned n, fa_job *jobs, const IcInput *frames = nullptr, hipEvent_t ready = nullptr)
 {
     Staged *S = new Staged;
     int ndev = 0;
@@ -677,7 +677,7 @@ static void *core1_stage(unsigned n, fa_job *jobs, const fiasco_amd_device_frame
     if (frames && !S->slots.empty()) {
         /* the planes never pass through the host: converted into the buffer the first pass reads, before any slot is
          * staged (a slot with ext_pix uploads no pixels) */
-        if (!ic_convert(S, frames, S->up_parity, ready, false, false) || hipStreamWaitEvent(S->stream, S->ev_up, 0) != hipSuccess) {
+        if (!ic_convert(S, *frames, S->up_parity, ready, false, false) || hipStreamWaitEvent(S->stream, S->ev_up, 0) != hipSuccess) {
             snprintf(S->ic_failed, sizeof S->ic_failed, "%s", fiasco_get_error_message());
             if (!S->ic_failed[0]) snprintf(S->ic_failed, sizeof S->ic_failed, "HIP error: the frames in device memory could not be converted");
             for (unsigned i = 0; i < n; i++)

@@ -157,28 +157,64 @@ static void ic_describe(IcFrame &d, const fiasco_amd_device_frame &f, const void
     total += (unsigned long long) d.cpr * f.height;
 }
 
-/* ONE launch for the n frames of the table at d_tab (device memory) on `stream': eight workgroups of four waves per CU,
- * fewer when the work is less */
-static bool ic_launch(const IcFrame *d_tab, unsigned n, unsigned long long total, int ncu, hipStream_t stream)
+/* eight workgroups of four waves per CU, fewer when the work is less */
+static unsigned ic_grid(unsigned long long total, int ncu)
 {
     unsigned long long grid = (unsigned long long) (ncu > 0 ? ncu : 256) * 8, tiles = (total + 255) / 256;
-    if (grid > tiles) grid = tiles;
+    return (unsigned) (grid > tiles ? tiles : grid);
+}
+
+/* ONE launch for the n frames of the table at d_tab (device memory) on `stream' */
+static bool ic_launch(const IcFrame *d_tab, unsigned n, unsigned long long total, int ncu, hipStream_t stream)
+{
+    const unsigned grid = ic_grid(total, ncu);
     if (!grid || !n) return true;
-    ic_convert_kernel<<<dim3((unsigned) grid), dim3(256), 0, stream>>>(d_tab, n, total);
+    ic_convert_kernel<<<dim3(grid), dim3(256), 0, stream>>>(d_tab, n, total);
     return hipGetLastError() == hipSuccess;
 }
 
+/* the device a pointer's memory lies on; -1: unknown */
+static int ic_device_of_pointer(const void *p)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) == hipSuccess) return at.device;
+    (void) hipGetLastError();
+    return -1;
+}
+
+static_assert(sizeof(IcFrame) <= IC_ENTRY_MAX, "IC_ENTRY_MAX (core_hip.cpp) is the room of a table entry");
+
+/* gray and RGB frames as a kind (core_hip.cpp IcKind) */
+static const IcKind IC_RGB = {
+    "device frame", sizeof(fiasco_amd_device_frame), sizeof(IcFrame),
+    [](const void *f, unsigned *w, unsigned *h, int *color) {
+        const fiasco_amd_device_frame &F = *(const fiasco_amd_device_frame *) f;
+        *w = F.width; *h = F.height; *color = F.layout != FIASCO_AMD_GRAY8;
+    },
+    [](const void *f) { return ic_device_of_pointer(((const fiasco_amd_device_frame *) f)->data); },
+    [](const void *f, const void **first) { *first = ((const fiasco_amd_device_frame *) f)->data; return ic_extent(*(const fiasco_amd_device_frame *) f); },
+    [](void *entry, const void *f, const void *src, int16_t *dst, unsigned long long &total) {
+        const fiasco_amd_device_frame &F = *(const fiasco_amd_device_frame *) f;
+        ic_describe(*(IcFrame *) entry, F, src ? src : F.data, dst, total);
+    },
+    [](const void *d_tab, unsigned n, unsigned long long total, int ncu, hipStream_t stream) { return ic_launch((const IcFrame *) d_tab, n, total, ncu, stream); },
+};
+
+/* the planes of a frame of the kind's geometry, as they lie in the input buffer */
+static size_t ic_planes_bytes(const fa_image *im) { return align_up((size_t) im->width * im->height * (im->color ? 3 : 1) * 2, 256); }
+
 /* The planes of every slot's frame into up_dev[parity], by one kernel launch on the upload stream after `ready'.
- * frames[j] belongs to jobs[j]; pitch and plane_stride are filled in and everything was checked (ic_check_frame).
+ * in.at(j) belongs to jobs[j]; its pitches are filled in and everything was checked (ic_check_frame, icy_check_frame).
  * next: the frames of the NEXT pass (ext_next, taken over by the next submit), else of the first pass (ext_pix).
  * Records ev_up behind the kernel.  Nothing here waits on the host for the device, but for the descriptor table of
  * the upload before this one, which a whole pass ago left the pinned memory.
  * prepare_only: everything that can run out of memory -- stream, events, the input buffer, the staging buffer, the
- * descriptor table -- and nothing else: no buffer is written, no slot changed.  fiasco_amd_batch_upload_device() prepares
+ * descriptor table -- and nothing else: no buffer is written, no slot changed.  The upload entries prepare
  * every share before any share converts, so that a share without memory refuses the upload while the batch is whole. */
-static bool ic_convert(Staged *S, const fiasco_amd_device_frame *frames, int parity, hipEvent_t ready, bool next, bool prepare_only)
+static bool ic_convert(Staged *S, const IcInput &in, int parity, hipEvent_t ready, bool next, bool prepare_only)
 {
     const size_t ns = S->slots.size();
+    const IcKind &K = *in.kind;
     if (!ns) return true;
     if (!S->ustream && hipStreamCreateWithFlags(&S->ustream, hipStreamNonBlocking) != hipSuccess) { S->ustream = nullptr; goto hip_failed; }
     if (!S->ev_up && hipEventCreateWithFlags(&S->ev_up, hipEventDisableTiming) != hipSuccess) { S->ev_up = nullptr; goto hip_failed; }
@@ -189,54 +225,62 @@ static bool ic_convert(Staged *S, const fiasco_amd_device_frame *frames, int par
         size_t need = 0, peer_need = 0;
         std::vector<int> srcdev(ns, here);
         for (size_t k = 0; k < ns; k++) {
-            const fa_image *im = S->jobs[S->slots[k].job].image;
-            const fiasco_amd_device_frame &f = frames[S->slots[k].job];
-            hipPointerAttribute_t at;
-            need += align_up((size_t) im->width * im->height * (im->color ? 3 : 1) * 2, 256);
-            if (hipPointerGetAttributes(&at, f.data) == hipSuccess) srcdev[k] = at.device; else (void) hipGetLastError();
-            if (srcdev[k] != here) peer_need += align_up(ic_extent(f), 256);
+            const void *f = in.at(S->slots[k].job);
+            const int dev = K.device_of(f);
+            need += ic_planes_bytes(S->jobs[S->slots[k].job].image);
+            if (dev >= 0) srcdev[k] = dev;
+            if (srcdev[k] == here) continue;
+            const void *first = nullptr;
+            const size_t ext = K.peer_extent(f, &first);
+            if (!ext) {
+                fa_set_error("<%s %u>: its planes live on device %d, the share that converts the frame works on device %d (no peer copy on this path).",
+                             K.what, S->slots[k].job, srcdev[k], here);
+                return false;
+            }
+            peer_need += align_up(ext, 256);
         }
         if (!grow_buffer(S->up_dev[parity], S->up_dev_bytes[parity], need)
             || (peer_need && !grow_buffer(S->peer_buf, S->peer_bytes, peer_need))) {
             fa_set_error("out of HBM: no room for %.1f MiB of frames", (need + peer_need) / 1048576.0);
             return false;
         }
-        if (ns > S->ic_cap) {
+        if (ns * IC_ENTRY_MAX > S->ic_cap) {        /* the slots of a share only grow at staging: once per batch */
             if (S->ic_tab) (void) hipHostFree(S->ic_tab);
             if (S->d_ic) (void) hipFree(S->d_ic);
             S->ic_tab = S->d_ic = nullptr; S->ic_cap = 0;
-            if (hipHostMalloc((void **) &S->ic_tab, ns * sizeof(IcFrame), hipHostMallocDefault) != hipSuccess
-                || hipMalloc((void **) &S->d_ic, ns * sizeof(IcFrame)) != hipSuccess) goto hip_failed;
-            S->ic_cap = ns;
+            if (hipHostMalloc((void **) &S->ic_tab, ns * IC_ENTRY_MAX, hipHostMallocDefault) != hipSuccess
+                || hipMalloc((void **) &S->d_ic, ns * IC_ENTRY_MAX) != hipSuccess) goto hip_failed;
+            S->ic_cap = ns * IC_ENTRY_MAX;
         }
         if (prepare_only) return true;
         if (hipEventSynchronize(S->ev_ic) != hipSuccess) goto hip_failed;
         if (hipStreamWaitEvent(S->ustream, ready, 0) != hipSuccess) goto hip_failed;
         unsigned long long total = 0;
         size_t at = 0, peer_at = 0;
+        std::vector<const int16_t *> planes(ns);
         for (size_t k = 0; k < ns; k++) {
-            const fa_image *im = S->jobs[S->slots[k].job].image;
-            const fiasco_amd_device_frame &f = frames[S->slots[k].job];
-            IcFrame &d = S->ic_tab[k];
-            const void *src = f.data;
+            const void *f = in.at(S->slots[k].job);
+            const void *src = nullptr;
             if (srcdev[k] != here) {
                 /* a source on another device: its bytes, rows and gaps as they lie, over the peer link first */
-                if (hipMemcpyPeerAsync(S->peer_buf + peer_at, here, f.data, srcdev[k], ic_extent(f), S->ustream) != hipSuccess) goto hip_failed;
+                const void *first = nullptr;
+                const size_t ext = K.peer_extent(f, &first);
+                if (hipMemcpyPeerAsync(S->peer_buf + peer_at, here, first, srcdev[k], ext, S->ustream) != hipSuccess) goto hip_failed;
                 src = S->peer_buf + peer_at;
-                peer_at += align_up(ic_extent(f), 256);
+                peer_at += align_up(ext, 256);
             }
-            ic_describe(d, f, src, (int16_t *) (S->up_dev[parity] + at), total);
-            at += align_up((size_t) im->width * im->height * (im->color ? 3 : 1) * 2, 256);
+            planes[k] = (const int16_t *) (S->up_dev[parity] + at);
+            K.describe(S->ic_tab + k * K.entry_bytes, f, src, (int16_t *) (S->up_dev[parity] + at), total);
+            at += ic_planes_bytes(S->jobs[S->slots[k].job].image);
         }
-        if (hipMemcpyAsync(S->d_ic, S->ic_tab, ns * sizeof(IcFrame), hipMemcpyHostToDevice, S->ustream) != hipSuccess
+        if (hipMemcpyAsync(S->d_ic, S->ic_tab, ns * K.entry_bytes, hipMemcpyHostToDevice, S->ustream) != hipSuccess
             || hipEventRecord(S->ev_ic, S->ustream) != hipSuccess) goto hip_failed;
-        if (!ic_launch(S->d_ic, (unsigned) ns, total, S->ncu, S->ustream) || hipEventRecord(S->ev_up, S->ustream) != hipSuccess) goto hip_failed;
+        if (!K.launch(S->d_ic, (unsigned) ns, total, S->ncu, S->ustream) || hipEventRecord(S->ev_up, S->ustream) != hipSuccess) goto hip_failed;
         for (size_t k = 0; k < ns; k++) {
             FrameSlot &fs = S->slots[k];
             fa_image *im = (fa_image *) S->jobs[fs.job].image;
-            const int16_t *planes = S->ic_tab[k].dst;
-            if (next) fs.ext_next = planes; else { fs.ext_pix = planes; fs.F.pix16 = planes; }
-            im->src_dev = planes; im->src_dev_id = here; im->src_owner = S;
+            if (next) fs.ext_next = planes[k]; else { fs.ext_pix = planes[k]; fs.F.pix16 = planes[k]; }
+            im->src_dev = planes[k]; im->src_dev_id = here; im->src_owner = S;
         }
         if (next) S->up_pending = true;
     }
@@ -264,6 +308,27 @@ static int ic_fetch(fa_image *im)
 
 /* ------------------------------------------------------------------ the entry points (include/libfiasco_amd_hip.h) */
 
+/* `bytes' from p on: device memory, inside the allocation the pointer belongs to (the kernel reads what the descriptor
+ * says).  name: "<device frame 3>"; what: "pixels are", "Y plane is"; rows: "rows", "Y rows" */
+static bool ic_check_memory(const char *name, const char *what, const char *rows, const void *p, size_t bytes)
+{
+    hipPointerAttribute_t at;
+    if (!p || hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice) {
+        (void) hipGetLastError();
+        fa_set_error("%s: the %s not in device memory.", name, what);
+        return false;
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) p) != hipSuccess) (void) hipGetLastError();
+    else if ((const char *) p + bytes > (const char *) base + size) {
+        fa_set_error("%s: the %s reach %lu bytes beyond the end of their device allocation.", name, rows,
+                     (unsigned long) ((const char *) p + bytes - ((const char *) base + size)));
+        return false;
+    }
+    return true;
+}
+
 /* one caller's frame (what: "device frame", or "device target" for output_convert.inc): the size rules and messages of the PNM reader, pitch, layout, and that its rows lie in device
  * memory.  *out = the frame with pitch and plane_stride filled in. */
 static bool ic_check_frame(const char *what, unsigned i, const fiasco_amd_device_frame *in, fiasco_amd_device_frame *out)
@@ -283,23 +348,7 @@ static bool ic_check_frame(const char *what, unsigned i, const fiasco_amd_device
         return false;
     }
     if (!out->plane_stride) out->plane_stride = out->pitch * in->height;
-    hipPointerAttribute_t at;
-    if (!in->data || hipPointerGetAttributes(&at, in->data) != hipSuccess || at.type != hipMemoryTypeDevice) {
-        (void) hipGetLastError();
-        fa_set_error("%s: the pixels are not in device memory.", name);
-        return false;
-    }
-    {   /* every row inside the allocation the pointer belongs to (the kernel reads what the descriptor says) */
-        hipDeviceptr_t base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) in->data) != hipSuccess) (void) hipGetLastError();
-        else if ((const char *) in->data + ic_extent(*out) > (const char *) base + size) {
-            fa_set_error("%s: the rows reach %lu bytes beyond the end of their device allocation.", name,
-                         (unsigned long) ((const char *) in->data + ic_extent(*out) - ((const char *) base + size)));
-            return false;
-        }
-    }
-    return true;
+    return ic_check_memory(name, "pixels are", "rows", in->data, ic_extent(*out));
 }
 
 static bool ic_have_device(void)
@@ -332,20 +381,24 @@ static void ic_release_source(MultiStaged *M, void *stream)
     }
 }
 
-extern "C" fiasco_amd_batch_t *fiasco_amd_batch_stage_device(unsigned n, const fiasco_amd_device_frame *frames, void *stream,
-                                                             float quality, const fiasco_c_options_t *options)
+/* a frame of the kind's geometry without host planes (fa_image_host_planes) */
+static fa_image *ic_image_of(const IcInput &in, unsigned i)
+{
+    fa_image *im = (fa_image *) calloc(1, sizeof(fa_image));
+    if (!im) { fa_set_error("Out of memory!"); return nullptr; }
+    in.kind->geometry(in.at(i), &im->width, &im->height, &im->color);
+    return im;
+}
+
+/* fiasco_amd_batch_stage_device() and its YCbCr sibling behind their checks: `in' holds n checked frames */
+static fiasco_amd_batch_t *ic_stage_batch(unsigned n, const IcInput &in, void *stream, float quality, const fiasco_c_options_t *options)
 {
     fiasco_c_options_t *defaults = nullptr;
     const fa_options *op;
     fiasco_amd_batch_t *b = nullptr;
     hipEvent_t ready = nullptr;
-    std::vector<fiasco_amd_device_frame> fr(n);
     bool ok = false;
 
-    if (!n || !frames) { fa_set_error("No frames to stage."); return nullptr; }
-    if (quality <= 0) { fa_set_error("Compression quality has to be positive."); return nullptr; }
-    if (!ic_have_device()) return nullptr;
-    for (unsigned i = 0; i < n; i++) if (!ic_check_frame("device frame", i, &frames[i], &fr[i])) return nullptr;
     if (options) { op = fa_cast_options(options); if (!op) return nullptr; }
     else { defaults = fiasco_c_options_new(); if (!defaults) return nullptr; op = fa_cast_options(defaults); }
     b = (fiasco_amd_batch_t *) calloc(1, sizeof *b);
@@ -361,16 +414,15 @@ extern "C" fiasco_amd_batch_t *fiasco_amd_batch_stage_device(unsigned n, const f
     b->prediction     = op->prediction;
     for (unsigned i = 0; i < n; i++) {
         fa_cparams cp;
-        b->ims[i] = (fa_image *) calloc(1, sizeof(fa_image));           /* no host planes: fa_image_host_planes */
-        if (!b->ims[i]) { fa_set_error("Out of memory!"); goto done; }
-        b->ims[i]->width = fr[i].width; b->ims[i]->height = fr[i].height; b->ims[i]->color = fr[i].layout != FIASCO_AMD_GRAY8;
-        if (!fa_setup_params(op, quality, fr[i].width, fr[i].height, b->ims[i]->color, 1, &b->infos[i], &cp)
+        b->ims[i] = ic_image_of(in, i);
+        if (!b->ims[i]) goto done;
+        if (!fa_setup_params(op, quality, b->ims[i]->width, b->ims[i]->height, b->ims[i]->color, 1, &b->infos[i], &cp)
             || !fa_prepare_job(&b->jobs[i], b->ims[i], &cp, op->basis_name)) goto done;
     }
     fa_image_fetch = ic_fetch;
     ready = ic_mark_ready(stream);
     if (!ready) goto done;
-    b->staged = stage_shares(n, b->jobs, fr.data(), ready);
+    b->staged = stage_shares(n, b->jobs, &in, ready);
     ic_release_source((MultiStaged *) b->staged, stream);
     ok = true;
     for (size_t k = 0; k < ((MultiStaged *) b->staged)->parts.size(); k++) {
@@ -386,9 +438,20 @@ done:
     return b;
 }
 
-/* what fiasco_amd_batch_upload_device() keeps of one share, to put it back when a share fails */
+extern "C" fiasco_amd_batch_t *fiasco_amd_batch_stage_device(unsigned n, const fiasco_amd_device_frame *frames, void *stream,
+                                                             float quality, const fiasco_c_options_t *options)
+{
+    std::vector<fiasco_amd_device_frame> fr(n);
+    if (!n || !frames) { fa_set_error("No frames to stage."); return nullptr; }
+    if (quality <= 0) { fa_set_error("Compression quality has to be positive."); return nullptr; }
+    if (!ic_have_device()) return nullptr;
+    for (unsigned i = 0; i < n; i++) if (!ic_check_frame("device frame", i, &frames[i], &fr[i])) return nullptr;
+    return ic_stage_batch(n, IcInput{ &IC_RGB, fr.data() }, stream, quality, options);
+}
+
+/* what an upload keeps of one share, to put it back when a share fails */
 struct IcShareUndo {
-    const fiasco_amd_device_frame       *frames = nullptr;   /* the share's frames in the order of its jobs (Part::frames_of) */
+    IcInput                              frames = { nullptr, nullptr };   /* the share's frames in the order of its jobs (Part::frames_of) */
     std::vector<const fa_image *>        image;     /* jobs[].image before */
     std::vector<const int16_t *>         ext_next;  /* slots[].ext_next before */
     bool up_pending = false;
@@ -396,17 +459,25 @@ struct IcShareUndo {
     char why[256] = "";                             /* the share's message: the error message is per thread */
 };
 
-extern "C" int fiasco_amd_batch_upload_device(fiasco_amd_batch_t *b, const fiasco_amd_device_frame *frames, void *stream)
+/* the staged batch takes replacement frames at all */
+static bool ic_upload_ready(fiasco_amd_batch_t *b, const void *frames)
 {
-    if (!b || !b->staged || !b->n) { fa_set_error("Batch is not staged."); return 0; }
-    if (!frames) { fa_set_error("No frames to stage."); return 0; }
+    if (!b || !b->staged || !b->n) { fa_set_error("Batch is not staged."); return false; }
+    if (!frames) { fa_set_error("No frames to stage."); return false; }
+    return true;
+}
+
+/* fiasco_amd_batch_upload_device() and its YCbCr sibling behind their checks: `in' holds b->n checked frames */
+static int ic_upload_batch(fiasco_amd_batch_t *b, const IcInput &in, void *stream)
+{
     MultiStaged *M = (MultiStaged *) b->staged;
-    std::vector<fiasco_amd_device_frame> fr(b->n);
     for (unsigned i = 0; i < b->n; i++) {
         const fa_image *old = b->ims[i];
-        if (!ic_check_frame("device frame", i, &frames[i], &fr[i])) return 0;
-        if (fr[i].width != old->width || fr[i].height != old->height || (fr[i].layout != FIASCO_AMD_GRAY8) != (old->color != 0)) {
-            fa_set_error("`<device frame %u>': replacement frames must keep the size and colour model of the batch.", i);
+        unsigned w, h;
+        int color;
+        in.kind->geometry(in.at(i), &w, &h, &color);
+        if (w != old->width || h != old->height || (color != 0) != (old->color != 0)) {
+            fa_set_error("`<%s %u>': replacement frames must keep the size and colour model of the batch.", in.kind->what, i);
             return 0;
         }
     }
@@ -419,9 +490,8 @@ extern "C" int fiasco_amd_batch_upload_device(fiasco_amd_batch_t *b, const fiasc
     bool ok = nims && ready;
     if (!nims) fa_set_error("Out of memory!");
     for (unsigned i = 0; ok && i < b->n; i++) {
-        nims[i] = (fa_image *) calloc(1, sizeof(fa_image));
-        if (!nims[i]) { fa_set_error("Out of memory!"); ok = false; break; }
-        nims[i]->width = fr[i].width; nims[i]->height = fr[i].height; nims[i]->color = fr[i].layout != FIASCO_AMD_GRAY8;
+        nims[i] = ic_image_of(in, i);
+        if (!nims[i]) { ok = false; break; }
     }
     if (ok) {
         /* the shares convert the frames of THEIR jobs.  First every share gets its memory (nothing is written: a share
@@ -435,7 +505,7 @@ extern "C" int fiasco_amd_batch_upload_device(fiasco_amd_batch_t *b, const fiasc
                 sh[k].image.push_back(S->jobs[j].image);
                 S->jobs[j].image = nims[M->parts[k].job_index(j)];
             }
-            sh[k].frames = M->parts[k].frames_of(fr.data());
+            sh[k].frames = M->parts[k].frames_of(in);
             for (size_t j = 0; j < S->slots.size(); j++) sh[k].ext_next.push_back(S->slots[j].ext_next);
             sh[k].up_pending = S->up_pending;
         }
@@ -483,13 +553,21 @@ extern "C" int fiasco_amd_batch_upload_device(fiasco_amd_batch_t *b, const fiasc
     return 1;
 }
 
+extern "C" int fiasco_amd_batch_upload_device(fiasco_amd_batch_t *b, const fiasco_amd_device_frame *frames, void *stream)
+{
+    if (!ic_upload_ready(b, frames)) return 0;
+    std::vector<fiasco_amd_device_frame> fr(b->n);
+    for (unsigned i = 0; i < b->n; i++) if (!ic_check_frame("device frame", i, &frames[i], &fr[i])) return 0;
+    return ic_upload_batch(b, IcInput{ &IC_RGB, fr.data() }, stream);
+}
+
 /* ------------------------------------------------------------------ videos in device memory
  *
  * fiasco_amd_seq_open_device(): the frames of a video as they lie in device memory.  Open converts ONCE every frame this
  * rank will ever search -- the frames of its groups of pictures and display frame 0, which fa_seq_probe searches on
  * every rank -- into int16 planes in a buffer the sequence owns, on the device of the share that searches the frame's
  * GOP (fa_share_of(gop + 1, ., shares); frame 0: share 0, where the probe runs and where GOP 0 is searched).  One launch
- * of ic_convert_kernel per share.  Open waits on the host for the conversions: the searches that follow have no ordering
+ * of the kind's kernel per share.  Open waits on the host for the conversions: the searches that follow have no ordering
  * question left, and the caller's stream is made to wait as well.  A search then stages the planes in place
  * (FrameSlot::ext_pix, core1_stage). */
 struct SeqPlanes { std::vector<std::pair<int, void *> > bufs; };     /* (device, allocation) */
@@ -508,20 +586,22 @@ static void seq_planes_release(void *ctx)
     delete P;
 }
 
-extern "C" fiasco_amd_seq_t *fiasco_amd_seq_open_device(unsigned n, const fiasco_amd_device_frame *frames, void *stream, float quality,
-                                                        const fiasco_c_options_t *options, unsigned rank, unsigned world)
+/* what every open of a video refuses before it looks at a frame */
+static bool ic_seq_open_ready(unsigned n, const void *frames, float quality, unsigned rank, unsigned world)
 {
-    if (!n || !frames) { fa_set_error("No frames to open."); return nullptr; }
-    if (quality <= 0) { fa_set_error("Compression quality has to be positive."); return nullptr; }
-    if (world == 0 || rank >= world) { fa_set_error("rank %d of %d?", (int) rank, (int) world); return nullptr; }
-    if (!ic_have_device()) return nullptr;
-    std::vector<fiasco_amd_device_frame> fr(n);
+    if (!n || !frames) { fa_set_error("No frames to open."); return false; }
+    if (quality <= 0) { fa_set_error("Compression quality has to be positive."); return false; }
+    if (world == 0 || rank >= world) { fa_set_error("rank %d of %d?", (int) rank, (int) world); return false; }
+    return ic_have_device();
+}
+
+/* fiasco_amd_seq_open_device() and its YCbCr sibling behind their checks: `in' holds n checked frames */
+static fiasco_amd_seq_t *ic_seq_open(unsigned n, const IcInput &in, void *stream, float quality, const fiasco_c_options_t *options,
+                                     unsigned rank, unsigned world)
+{
+    const IcKind &K = *in.kind;
     std::vector<int> srcdev(n, -1);
-    for (unsigned i = 0; i < n; i++) {
-        if (!ic_check_frame("device frame", i, &frames[i], &fr[i])) return nullptr;
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, fr[i].data) == hipSuccess) srcdev[i] = at.device; else (void) hipGetLastError();
-    }
+    for (unsigned i = 0; i < n; i++) srcdev[i] = K.device_of(in.at(i));
     fiasco_c_options_t *defaults = nullptr;
     const fa_options *op;
     if (options) { op = fa_cast_options(options); if (!op) return nullptr; }
@@ -530,9 +610,8 @@ extern "C" fiasco_amd_seq_t *fiasco_amd_seq_open_device(unsigned n, const fiasco
     fa_image **images = (fa_image **) calloc(n, sizeof *images);
     bool ok = images != nullptr;
     for (unsigned i = 0; ok && i < n; i++) {
-        images[i] = (fa_image *) calloc(1, sizeof(fa_image));           /* no host planes: fa_image_host_planes */
+        images[i] = ic_image_of(in, i);
         if (!images[i]) { ok = false; break; }
-        images[i]->width = fr[i].width; images[i]->height = fr[i].height; images[i]->color = fr[i].layout != FIASCO_AMD_GRAY8;
         images[i]->src_dev_id = -1;
     }
     if (!ok) {
@@ -561,7 +640,7 @@ extern "C" fiasco_amd_seq_t *fiasco_amd_seq_open_device(unsigned n, const fiasco
         taken[d] = 1;
         mine[fa_share_of(g + 1, 0, (unsigned) D)].push_back(d);
     }
-    const size_t frame_b = align_up((size_t) fr[0].width * fr[0].height * (fr[0].layout != FIASCO_AMD_GRAY8 ? 3 : 1) * 2, 256);
+    const size_t frame_b = ic_planes_bytes(images[0]);
     SeqPlanes *P = new SeqPlanes;
     hipEvent_t ready = ic_mark_ready(stream);
     std::vector<size_t> share;
@@ -576,16 +655,16 @@ extern "C" fiasco_amd_seq_t *fiasco_amd_seq_open_device(unsigned n, const fiasco
             int here = -1, ncu = 0;
             hipStream_t st = nullptr;
             char *buf = nullptr;
-            IcFrame *d_tab = nullptr;
-            std::vector<IcFrame> tab(ds.size());
+            char *d_tab = nullptr;
+            std::vector<char> tab(ds.size() * K.entry_bytes);
             unsigned long long total = 0;
             auto fail = [&](const char *msg) { why[part] = msg; (void) hipGetLastError(); };
             if (hipGetDevice(&here) != hipSuccess) { fail("HIP error: no current device"); return; }
             for (unsigned d : ds)
                 if (srcdev[d] != here) {
                     char msg[200];
-                    snprintf(msg, sizeof msg, "<device frame %u>: the pixels live on device %d, its group of pictures is searched on device %d "
-                             "(no peer copy on this path).", d, srcdev[d], here);
+                    snprintf(msg, sizeof msg, "<%s %u>: the pixels live on device %d, its group of pictures is searched on device %d "
+                             "(no peer copy on this path).", K.what, d, srcdev[d], here);
                     why[part] = msg;
                     return;
                 }
@@ -598,13 +677,13 @@ extern "C" fiasco_amd_seq_t *fiasco_amd_seq_open_device(unsigned n, const fiasco
                 return;
             }
             got[part] = buf; gotdev[part] = here;
-            for (size_t j = 0; j < ds.size(); j++) ic_describe(tab[j], fr[ds[j]], fr[ds[j]].data, (int16_t *) (buf + j * frame_b), total);
+            for (size_t j = 0; j < ds.size(); j++) K.describe(tab.data() + j * K.entry_bytes, in.at(ds[j]), nullptr, (int16_t *) (buf + j * frame_b), total);
             bool fine = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess
                         && hipEventCreateWithFlags(&done[part], hipEventDisableTiming) == hipSuccess
-                        && hipMalloc((void **) &d_tab, tab.size() * sizeof(IcFrame)) == hipSuccess
+                        && hipMalloc((void **) &d_tab, tab.size()) == hipSuccess
                         && hipStreamWaitEvent(st, ready, 0) == hipSuccess
-                        && hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(IcFrame), hipMemcpyHostToDevice, st) == hipSuccess
-                        && ic_launch(d_tab, (unsigned) tab.size(), total, ncu, st)
+                        && hipMemcpyAsync(d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, st) == hipSuccess
+                        && K.launch(d_tab, (unsigned) ds.size(), total, ncu, st)
                         && hipEventRecord(done[part], st) == hipSuccess
                         && hipStreamSynchronize(st) == hipSuccess;          /* the one host wait of open */
             if (!fine) { why[part] = std::string("HIP error: ") + hipGetErrorString(hipGetLastError()); }
@@ -636,4 +715,13 @@ extern "C" fiasco_amd_seq_t *fiasco_amd_seq_open_device(unsigned n, const fiasco
         return nullptr;
     }
     return q;
+}
+
+extern "C" fiasco_amd_seq_t *fiasco_amd_seq_open_device(unsigned n, const fiasco_amd_device_frame *frames, void *stream, float quality,
+                                                        const fiasco_c_options_t *options, unsigned rank, unsigned world)
+{
+    if (!ic_seq_open_ready(n, frames, quality, rank, world)) return nullptr;
+    std::vector<fiasco_amd_device_frame> fr(n);
+    for (unsigned i = 0; i < n; i++) if (!ic_check_frame("device frame", i, &frames[i], &fr[i])) return nullptr;
+    return ic_seq_open(n, IcInput{ &IC_RGB, fr.data() }, stream, quality, options, rank, world);
 }

@@ -159,7 +159,7 @@ struct MultiStaged {
     struct Part {
         std::vector<unsigned> idx;      /* dealt: the caller's jobs of this part, in its order; in place: empty */
         std::vector<fa_job>   sub;      /* dealt: the part's copies of them */
-        std::vector<fiasco_amd_device_frame> frames;    /* dealt: the part's frames in device memory (frames_of) */
+        std::vector<char>     frames;   /* dealt: the part's frames in device memory (frames_of) */
         fa_job  *jobs = nullptr;        /* what the part's Staged works on: sub, or the caller's jobs[] */
         unsigned n = 0;
         void    *staged = nullptr;
@@ -168,12 +168,13 @@ struct MultiStaged {
         /* the caller's job behind the part's job j */
         unsigned job_index(unsigned j) const { return idx.empty() ? j : idx[j]; }
         /* the part's frames out of one per job of the caller, in the part's order */
-        const fiasco_amd_device_frame *frames_of(const fiasco_amd_device_frame *all)
+        IcInput frames_of(const IcInput &all)
         {
             if (idx.empty()) return all;
             frames.clear();
-            for (size_t j = 0; j < idx.size(); j++) frames.push_back(all[idx[j]]);
-            return frames.data();
+            for (size_t j = 0; j < idx.size(); j++)
+                frames.insert(frames.end(), (const char *) all.at(idx[j]), (const char *) all.at(idx[j]) + all.kind->frame_bytes);
+            return IcInput{ all.kind, frames.data() };
         }
     };
     std::vector<Part> parts;
@@ -325,7 +326,7 @@ template <typename Fn> static int run_parts(MultiStaged *M, Fn fn)
     return sum;
 }
 
-static void *stage_shares(unsigned n, fa_job *jobs, const fiasco_amd_device_frame *frames, hipEvent_t ready)
+static void *stage_shares(unsigned n, fa_job *jobs, const IcInput *frames, hipEvent_t ready)
 {
     MultiStaged *M = new MultiStaged;
     M->jobs = jobs;
@@ -347,7 +348,8 @@ static void *stage_shares(unsigned n, fa_job *jobs, const fiasco_amd_device_fram
         }
     for_each_share(M, [&](size_t k) {
         MultiStaged::Part &P = M->parts[k];
-        P.staged = core1_stage(P.n, P.jobs, frames ? P.frames_of(frames) : nullptr, ready);      /* every share converts its own frames */
+        const IcInput mine = frames ? P.frames_of(*frames) : IcInput{ nullptr, nullptr };
+        P.staged = core1_stage(P.n, P.jobs, frames ? &mine : nullptr, ready);      /* every share converts its own frames */
     });
     each_dealt_job(M, [](const fa_job &mine, fa_job &callers) { callers = mine; });   /* what staging said about a job */
     return M;

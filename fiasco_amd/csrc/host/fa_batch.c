@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "fa_host.h"
+#include "libfiasco_amd_ycbcr.h"
 
 /* struct fiasco_amd_batch: fa_host.h (the device-input entry points of the core fill one too) */
 
@@ -55,9 +56,9 @@ void fiasco_amd_batch_free(fiasco_amd_batch_t *b)
     free(b);
 }
 
-fiasco_amd_batch_t *fiasco_amd_batch_stage(unsigned n, const unsigned char *const *pnm,
-                                           const size_t *pnm_len, float quality,
-                                           const fiasco_c_options_t *options)
+/* a staged batch of n frames, frame i being make(ctx, i) (NULL + message: the batch is refused) */
+static fiasco_amd_batch_t *stage_images(unsigned n, fa_image *(*make)(const void *ctx, unsigned i), const void *ctx, float quality,
+                                        const fiasco_c_options_t *options)
 {
     fiasco_c_options_t *defaults = NULL;
     const fa_options *op;
@@ -85,7 +86,7 @@ fiasco_amd_batch_t *fiasco_amd_batch_stage(unsigned n, const unsigned char *cons
     b->prediction     = op->prediction;
     for (i = 0; i < n; i++) {
         fa_cparams cp;
-        b->ims[i] = fa_image_from_pnm(pnm[i], pnm_len[i], "<memory>");
+        b->ims[i] = make(ctx, i);
         if (!b->ims[i] || !fa_setup_params(op, quality, b->ims[i]->width, b->ims[i]->height,
                                           b->ims[i]->color, 1, &b->infos[i], &cp)
             || !fa_prepare_job(&b->jobs[i], b->ims[i], &cp, op->basis_name)) {
@@ -96,6 +97,44 @@ fiasco_amd_batch_t *fiasco_amd_batch_stage(unsigned n, const unsigned char *cons
     }
     if (defaults) fiasco_c_options_delete(defaults);
     b->staged = fa_core_stage(n, b->jobs);
+    return b;
+}
+
+typedef struct { const unsigned char *const *pnm; const size_t *len; } pnm_frames;
+static fa_image *make_from_pnm(const void *ctx, unsigned i)
+{
+    const pnm_frames *f = (const pnm_frames *) ctx;
+    return fa_image_from_pnm(f->pnm[i], f->len[i], "<memory>");
+}
+
+fiasco_amd_batch_t *fiasco_amd_batch_stage(unsigned n, const unsigned char *const *pnm,
+                                           const size_t *pnm_len, float quality,
+                                           const fiasco_c_options_t *options)
+{
+    pnm_frames f;
+    f.pnm = pnm; f.len = pnm_len;
+    return stage_images(n, make_from_pnm, &f, quality, options);
+}
+
+/* include/libfiasco_amd_ycbcr.h: the same with YCbCr bytes in host memory; every frame is checked before anything is
+ * allocated */
+static fa_image *make_from_ycbcr(const void *ctx, unsigned i)
+{
+    return fa_image_from_ycbcr((const fiasco_amd_ycbcr_frame *) ctx + i, NULL);
+}
+
+fiasco_amd_batch_t *fiasco_amd_batch_stage_ycbcr(unsigned n, const fiasco_amd_ycbcr_frame *frames, float quality,
+                                                 const fiasco_c_options_t *options)
+{
+    fiasco_amd_ycbcr_frame *fr;
+    fiasco_amd_batch_t *b = NULL;
+    unsigned i;
+    if (!n || !frames) { fa_set_error("No frames to stage."); return NULL; }
+    fr = (fiasco_amd_ycbcr_frame *) calloc(n, sizeof *fr);
+    if (!fr) { fa_set_error("Out of memory!"); return NULL; }
+    for (i = 0; i < n; i++) if (!fa_ycbcr_check(i, &frames[i], &fr[i])) break;
+    if (i == n) b = stage_images(n, make_from_ycbcr, fr, quality, options);
+    free(fr);
     return b;
 }
 

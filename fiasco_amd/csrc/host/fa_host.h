@@ -123,6 +123,14 @@ fa_image *fa_image_alloc(unsigned width, unsigned height, int color);   /* zeroe
 /* the geometry rules of read_pnmheader / read_image (lib/image.c:194-195, :316-323) for a frame that does not come
  * from a PNM header; 0 + the reader's message */
 int       fa_image_check_size(unsigned width, unsigned height, const char *name);
+/* Frames that are YCbCr already (include/libfiasco_amd_ycbcr.h).  fa_ycbcr_check: everything that can be said about
+ * frame i without asking where its memory lies -- the planes, c_step, subsampling, the size, the pitches; *out: the
+ * frame with its pitches filled in; 0 + message.  fa_image_from_ycbcr: a checked frame in host memory as planes,
+ * (byte - 128) * 16, a 4:2:0 chroma sample replicated over its 2 x 2 pixels; planes: NULL (the image owns its planes),
+ * or where the three bands go back to back (borrowed, as fa_image_from_pnm_into). */
+struct fiasco_amd_ycbcr_frame;
+int       fa_ycbcr_check(unsigned i, const struct fiasco_amd_ycbcr_frame *in, struct fiasco_amd_ycbcr_frame *out);
+fa_image *fa_image_from_ycbcr(const struct fiasco_amd_ycbcr_frame *f, int16_t *planes);
 /* Host planes on demand.  The host never reads input pixels while it encodes; only the decoded-PSNR calls and
  * fiasco_amd_batch_input_planes() do.  For a frame that lives on the device the planes are allocated here and
  * filled by fa_image_fetch, which the product's core sets (the host C names no core function: the test oracle

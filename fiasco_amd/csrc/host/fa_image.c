@@ -12,6 +12,7 @@
 #include <ctype.h>
 #include <pthread.h>
 #include "fa_host.h"
+#include "libfiasco_amd_ycbcr.h"
 
 typedef struct cursor { const unsigned char *p, *end; } cursor;
 
@@ -214,5 +215,79 @@ fa_image *fa_image_from_pnm_into(const unsigned char *buf, size_t len, const cha
     im->width = w; im->height = h; im->color = color; im->borrowed = 1;
     for (b = 0; b < (color ? 3 : 1); b++) im->pixels[b] = planes + (size_t) b * n;
     convert_planes(buf + off, n, color, im->pixels);
+    return im;
+}
+
+/* ---------------------------------------------------------------- YCbCr bytes (include/libfiasco_amd_ycbcr.h) */
+
+int fa_ycbcr_check(unsigned i, const fiasco_amd_ycbcr_frame *in, fiasco_amd_ycbcr_frame *out)
+{
+    char name[32];
+    size_t crow;
+    snprintf(name, sizeof name, "<YCbCr frame %u>", i);
+    *out = *in;
+    if (!in->y || !in->cb || !in->cr) {
+        fa_set_error("%s: no %s plane.", name, !in->y ? "Y" : !in->cb ? "Cb" : "Cr");
+        return 0;
+    }
+    if (in->subsampling > 1) {
+        fa_set_error("%s: subsampling %u (0: 4:4:4, 1: 4:2:0).", name, in->subsampling);
+        return 0;
+    }
+    if (in->c_step != 1 && in->c_step != 2) {
+        fa_set_error("%s: c_step %u (1: two chroma planes, 2: one plane of interleaved pairs).", name, in->c_step);
+        return 0;
+    }
+    if (in->c_step == 2 && in->subsampling == 0) {
+        fa_set_error("%s: c_step 2 with subsampling 0 (interleaved 4:4:4 chroma, NV24, is not taken).", name);
+        return 0;
+    }
+    if (in->c_step == 2 && (const unsigned char *) in->cr != (const unsigned char *) in->cb + 1
+        && (const unsigned char *) in->cb != (const unsigned char *) in->cr + 1) {
+        fa_set_error("%s: c_step 2 with chroma pointers that are not one byte apart (cr == cb + 1: NV12, cb == cr + 1: NV21).", name);
+        return 0;
+    }
+    if (!fa_image_check_size(in->width, in->height, name)) return 0;
+    crow = (size_t) (in->width >> in->subsampling) * in->c_step;
+    if (!out->y_pitch) out->y_pitch = in->width;
+    if (!out->c_pitch) out->c_pitch = crow;
+    if (out->y_pitch < in->width) {
+        fa_set_error("%s: Y pitch of %lu bytes is smaller than a row of %u bytes.", name, (unsigned long) out->y_pitch, in->width);
+        return 0;
+    }
+    if (out->c_pitch < crow) {
+        fa_set_error("%s: chroma pitch of %lu bytes is smaller than a row of %lu bytes.", name, (unsigned long) out->c_pitch,
+                     (unsigned long) crow);
+        return 0;
+    }
+    return 1;
+}
+
+fa_image *fa_image_from_ycbcr(const fiasco_amd_ycbcr_frame *f, int16_t *planes)
+{
+    const unsigned w = f->width, h = f->height, s = f->subsampling;
+    const size_t n = (size_t) w * h;
+    const unsigned char *src[3];
+    unsigned x, y;
+    int b;
+    fa_image *im = (fa_image *) calloc(1, sizeof *im);
+    if (!im) { fa_set_error("Out of memory!"); return NULL; }
+    im->width = w; im->height = h; im->color = 1; im->borrowed = planes != NULL;
+    for (b = 0; b < 3; b++) {
+        im->pixels[b] = planes ? planes + (size_t) b * n : (int16_t *) malloc(n * sizeof(int16_t));
+        if (!im->pixels[b]) { fa_image_free(im); fa_set_error("Out of memory!"); return NULL; }
+    }
+    src[FA_Y] = (const unsigned char *) f->y; src[FA_CB] = (const unsigned char *) f->cb; src[FA_CR] = (const unsigned char *) f->cr;
+    for (y = 0; y < h; y++) {
+        const unsigned char *row = src[FA_Y] + (size_t) y * f->y_pitch;
+        int16_t *q = im->pixels[FA_Y] + (size_t) y * w;
+        for (x = 0; x < w; x++) q[x] = (int16_t) (((int) row[x] - 128) * 16);
+    }
+    for (b = FA_CB; b <= FA_CR; b++)
+        for (y = 0; y < h; y++) {
+            const unsigned char *row = src[b] + (size_t) (y >> s) * f->c_pitch;
+            int16_t *q = im->pixels[b] + (size_t) y * w;
+            for (x = 0; x < w; x++) q[x] = (int16_t) (((int) row[(size_t) (x >> s) * f->c_step] - 128) * 16);
+        }
     return im;
 }

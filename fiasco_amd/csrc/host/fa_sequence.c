@@ -28,6 +28,7 @@
 #include <math.h>
 #include <time.h>
 #include "fa_host.h"
+#include "libfiasco_amd_ycbcr.h"
 #include "libfiasco_amd_video.h"
 
 /* developer aid: FIASCO_AMD_SEQ_TIMING=1 prints where a sweep spends its time (stderr) */
@@ -325,6 +326,11 @@ static fa_image *seq_input(const fa_seq *s, unsigned d)
     if (!im) { fa_set_error("Out of memory!"); return NULL; }
     im->width = s->images[d]->width; im->height = s->images[d]->height; im->color = s->images[d]->color;
     im->src_dev = s->images[d]->src_dev; im->src_dev_id = s->images[d]->src_dev_id; im->src_owner = s->images[d]->src_owner;
+    if (s->images[d]->pixels[0] && !s->images[d]->src_dev) {          /* planes on the host alone (fiasco_amd_seq_open_ycbcr): lent */
+        int b;
+        for (b = 0; b < 3; b++) im->pixels[b] = s->images[d]->pixels[b];
+        im->borrowed = 1;
+    }
     return im;
 }
 
@@ -771,6 +777,51 @@ fiasco_amd_seq_t *fa_seq_handle(fa_seq *s, fiasco_c_options_t *defaults)
     fiasco_amd_seq_t *q = (fiasco_amd_seq_t *) calloc(1, sizeof *q);
     if (!q) { fa_set_error("Out of memory!"); return NULL; }
     q->s = s; q->defaults = defaults;
+    return q;
+}
+
+/* include/libfiasco_amd_ycbcr.h: a video of YCbCr frames in host memory.  Every frame is checked before anything is
+ * allocated; the frames are converted here, once, and kept as images (fa_seq_open_images) */
+fiasco_amd_seq_t *fiasco_amd_seq_open_ycbcr(unsigned n, const fiasco_amd_ycbcr_frame *frames, float quality,
+                                            const fiasco_c_options_t *options, unsigned rank, unsigned world)
+{
+    fiasco_c_options_t *defaults = NULL;
+    const fa_options *op;
+    fiasco_amd_seq_t *q;
+    fa_image **images;
+    fa_seq *s;
+    unsigned i;
+    if (!n || !frames) { fa_set_error("No frames to open."); return NULL; }
+    if (quality <= 0) { fa_set_error("Compression quality has to be positive."); return NULL; }
+    if (world == 0 || rank >= world) { fa_set_error("rank %d of %d?", (int) rank, (int) world); return NULL; }
+    for (i = 0; i < n; i++) {
+        fiasco_amd_ycbcr_frame f;
+        if (!fa_ycbcr_check(i, &frames[i], &f)) return NULL;
+    }
+    if (options) { op = fa_cast_options(options); if (!op) return NULL; }
+    else { defaults = fiasco_c_options_new(); if (!defaults) return NULL; op = fa_cast_options(defaults); }
+    images = (fa_image **) calloc(n, sizeof *images);
+    for (i = 0; images && i < n; i++) {
+        fiasco_amd_ycbcr_frame f;
+        (void) fa_ycbcr_check(i, &frames[i], &f);
+        images[i] = fa_image_from_ycbcr(&f, NULL);
+        if (images[i]) images[i]->src_dev_id = -1;
+        else break;
+    }
+    if (!images || i < n) {
+        if (!images) fa_set_error("Out of memory!");
+        for (i = 0; images && i < n; i++) fa_image_free(images[i]);
+        free(images);
+        if (defaults) fiasco_c_options_delete(defaults);
+        return NULL;
+    }
+    s = fa_seq_open_images(op, quality, n, images, rank, world);         /* takes the images, also when it refuses */
+    q = s ? fa_seq_handle(s, defaults) : NULL;
+    if (!q) {
+        fa_seq_free(s);
+        if (defaults) fiasco_c_options_delete(defaults);
+        return NULL;
+    }
     return q;
 }
 fa_seq *fa_seq_of_handle(const fiasco_amd_seq_t *q) { return q ? q->s : NULL; }
