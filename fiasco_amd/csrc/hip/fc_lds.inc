@@ -275,7 +275,12 @@ struct Sh {
         unsigned long long n_app_dealt, t_app_wait;
     } sl;
 #endif
+    /* where mp_tables() stores the logarithm of a lane whose role has no double / no float entry (every lane runs the
+     * same stores).  Behind everything else: a member in front of `pixels` would shift them. */
+    double   sink_d;
+    float    sink_f;
 };
+static_assert(offsetof(Sh, pixels) % 16 == 0, "op_d5 reads Sh::pixels with 128-bit LDS loads");
 #if FC_GM
 /* generic models: kinds, and the probability-index arrays of the quasi-arithmetic pools in DevFrame.gq */
 #define GM_QAC(k)   ((k) == FC_PK_ADAPTIVE || (k) == FC_PK_BASIS)

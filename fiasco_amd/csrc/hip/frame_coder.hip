@@ -17,7 +17,7 @@
  *                                  codec/prediction.c, codec/mwfa.c
  *    fc_models.inc     snapshot slots, generic models (FC_GM)
  *                                  codec/domain-pool.c:621-852, codec/coeff.c:215-267
- *    mp_device.inc     matching pursuit (and mp_reg.inc, which it includes)
+ *    mp_device.inc     matching pursuit (and mp_reg.inc and mp_roles.h, which it includes)
  *                                  codec/approx.c:74-271,317-699 (domain-parallel, see below)
  *    fc_serial.inc     partition search: serial state machine, lane 0, explicit LDS stack; bands
  *                                  codec/subdivide.c:60-502, codec/coder.c:738-833, codec/bintree.c:35-73

@@ -10,6 +10,7 @@
  *  registers through compile-time trip counts (templates on the step number n) and
  *  predication; wave-uniform step state is read from LDS once per pass.
  */
+#include "mp_roles.h"                 /* which table entry a lane of mp_tables() computes */
 
 /* ---- uniform state of one scan pass, held in scalar registers ----
  *
@@ -324,12 +325,21 @@ __device__ __forceinline__ void full_eval(const DevFrame &F, const Sh &sh, const
  *     om + 6              lglv_m1          (see below)
  *     om + 7, om + 8      tb[]             tree model: leaf / child of this level (default build)
  *     om + 9, om + 10     mp.wb_nd, wb_dc  placeholder weight 0.5 on no kept vector (default build)
- * (om = 64 + sy, or 128 when that would reach into the third wave).
+ * (om = 64 + sy, or 128 when that would reach into the third wave; the mapping itself is mp_role(), mp_roles.h).
  * Pass 2, after a barrier, lane om + 11: the nested domain-0 model and -- default build -- the position
  * pricing of the first step (no kept vector), which mp_step_prepare() would otherwise compute on
  * the serial lane.
- * Out of line: the double constants of log2 stay inside (inlined, they are materialised once
- * before the kernel's persistent loop and occupy registers for the whole kernel). */
+ * Out of line where machine LICM runs: the double constants of log2 stay inside (inlined, they are materialised
+ * once before the kernel's persistent loop and occupy registers for the whole kernel).  The builds compiled without
+ * machine LICM (csrc/Makefile KFLAGS: the ones with FC_SERIAL_LOOP) inline it: a call waits for every memory read in
+ * flight, and op_approx has the first reads of the scan in flight across the table pass. */
+#if defined(FC_SERIAL_LOOP) && FC_SERIAL_LOOP && !FC_HM
+#define MP_TABLES_INLINE 1
+#define MP_TABLES_ATTR __forceinline__
+#else
+#define MP_TABLES_INLINE 0
+#define MP_TABLES_ATTR __noinline__
+#endif
 #if FC_HM
 /* the same for models of up to 512 symbols per context (more roles than lanes): lane t takes the roles t,
  * t + B, ... -- DC symbols, the level's symbols, lglv_m1, the edge counts */
@@ -387,10 +397,15 @@ __device__ __noinline__ void mp_tables(const DevFrame &F, Sh &sh, int level, int
     }
 }
 #else
-__device__ __noinline__ void mp_tables(const DevFrame &F, Sh &sh, int level, int y)
+__device__ MP_TABLES_ATTR void mp_tables(const DevFrame &F, Sh &sh, int level, int y)
 {
     const int tid = threadIdx.x;
     const int ctx = level - sh.par.lc_min_opt, dcs = sh.par.dcs, sy = sh.par.sy;
+    /* everything uniform the role pass needs is asked for here, in one LDS round trip */
+    const int band = sh.band, half_nd = sh.par.half_nd, half_dc = sh.par.half_dc;
+#if !FC_VARIANT_BIG
+    const int ML = sh.par.ML;
+#endif
     /* The roles are packed into as few waves as they fit (a wave without a role skips the logarithm
      * altogether, ~250 instructions per call and wave): DC symbols in wave 0, the level's symbols from
      * lane 64 on, the eleven single roles right behind them when that still ends in wave 1 (CLI models:
@@ -413,7 +428,7 @@ __device__ __noinline__ void mp_tables(const DevFrame &F, Sh &sh, int level, int
         else        { q1 -= sh.m0tab[qac_shift(m.d0_index)];  q1 += (float) qac_shift(m.d0_index); }
         sh.Q0 = q0; sh.Q1 = q1;
 #if !FC_VARIANT_BIG
-        if (!sh.band) {
+        if (!band) {
             /* The first step of the call has no kept vector: what mp_step_prepare() would leave
              * for it depends on the models and the dictionary size only. */
             MPState &mp = sh.mp;
@@ -433,52 +448,50 @@ __device__ __noinline__ void mp_tables(const DevFrame &F, Sh &sh, int level, int
 #endif
     }
     if (tid < om + 12) {
-        /* role -> index of the count, index of the total (coefficient model: cb; else see below) */
-        int ci = 0, ti = 0, role = 0;              /* 0 none, 1 coefficient model, 2 pool, 3 tree */
-        const int r = tid - om;                    /* single roles: 0..5 edge counts, 6 m1, 7/8 tree, 9/10 placeholder prices */
-        if (tid < dcs) { role = 1; ci = tid; ti = 0; }
-        else if (tid >= 64 && tid < 64 + sy) { role = 1; ci = dcs + ctx * sy + tid - 64; ti = ctx + 1; }
-        else if (r == 6) {
-            /* A weight left over from another run of the same call (full_search, codec/approx.c:
-             * 439-446) may round to zero in this context's format: rtob() is then RPF_ZERO = -1
-             * and the reference prices it with the counter in FRONT of the context (coeff.c:228):
-             * the last symbol of the previous context. */
-            role = 1; ci = dcs + ctx * sy - 1; ti = ctx + 1;
-        }
-        else if (r >= 0 && r < MAXED + 1) { role = 2; ci = r; }
-#if !FC_VARIANT_BIG
-        else if (r == 7 || r == 8) role = 3;
-        else if (r == 9 && !sh.band) {
-            role = 1; ci = dcs + ctx * sy + sh.par.half_nd; ti = ctx + 1;
-        } else if (r == 10 && !sh.band) {
-            role = 1; ci = sh.par.half_dc; ti = 0;
-        }
-#endif
+        /* The role as selects (mp_roles.h), then one path for every role: each operand a role can ask for is read
+         * whatever the lane's role is (at index 0 where it has none), so the LDS reads are in flight together and
+         * a wave that holds several kinds of roles does not walk through one branch -- and one dependent LDS round
+         * trip -- per kind.  Each count is converted in its own type, as the reference's float casts do. */
+        const MpRole ro = mp_role(tid, dcs, sy, ctx, band, half_nd, half_dc, MAXED, FC_VARIANT_BIG);
+        const bool kc = ro.kind == MPR_COEFF, kp = ro.kind == MPR_POOL;
+        int pi = 0;                                /* cb.cnt[] holds every index a role gives, pool.count[] only a pool role's */
+        pi = kp ? ro.ci : pi;
+        const short c_num = sh.cb.cnt[ro.ci], c_den = sh.cb.tot[ro.ti], p_num = sh.pool.count[pi];
+        const unsigned short p_den = sh.pool.total;
+        const float c_numf = (float) c_num, c_denf = (float) c_den, p_numf = (float) p_num, p_denf = (float) p_den;
         float num = 1.0f, den = 1.0f;
-        if (role == 1)      { num = (float) sh.cb.cnt[ci]; den = (float) sh.cb.tot[ti]; }
-        else if (role == 2) { num = (float) sh.pool.count[ci]; den = (float) sh.pool.total; }
+        num = kp ? p_numf : num;   den = kp ? p_denf : den;
+        num = kc ? c_numf : num;   den = kc ? c_denf : den;
 #if !FC_VARIANT_BIG
-        else if (role == 3) {                      /* tree_bits_dev(): prob = counts[level] / (float) total */
-            const unsigned *counts = sh.tm;
-            num = (float) counts[level]; den = (float) counts[sh.par.ML + level];
+        {   /* tree_bits_dev(): prob = counts[level] / (float) total */
+            const bool kt = ro.kind == MPR_TREE;
+            const float t_numf = (float) sh.tm[level], t_denf = (float) sh.tm[ML + level];
+            num = kt ? t_numf : num;   den = kt ? t_denf : den;
         }
 #endif
         float p = num / den;
-#if !FC_VARIANT_BIG
-        if (r == 7) p = 1 - p;                     /* the leaf symbol */
-#endif
+        const float q = 1 - p;
+        p = ro.leaf ? q : p;                       /* the leaf symbol */
         const double lg = log2((double) p);        /* one call site for every role */
-        if (role == 1) {
-            if (tid < dcs) sh.lgdc[tid] = lg;
-            else if (r == 6) sh.lglv_m1 = lg;
+        const float nlg = (float) -lg;
+        /* A weight left over from another run of the same call (full_search, codec/approx.c:439-446) may round to
+         * zero in this context's format: rtob() is then RPF_ZERO = -1 and the reference prices it with the counter
+         * in FRONT of the context (coeff.c:228), the last symbol of the previous context: lglv_m1. */
+        double *const d_dc = &sh.lgdc[ro.di], *const d_lv = &sh.lglv[ro.di], *const d_m1 = &sh.lglv_m1;
+        float *const f_lt = &sh.Ltab[ro.di], *const f_tb = &sh.tb[ro.di];
+        const bool to_dc = ro.dest == MPD_LGDC, to_lv = ro.dest == MPD_LGLV, to_m1 = ro.dest == MPD_LGLV_M1;
+        const bool to_lt = ro.dest == MPD_LTAB, to_tb = ro.dest == MPD_TB;
+        double *dd = &sh.sink_d;
+        float *df = &sh.sink_f;
+        dd = to_dc ? d_dc : dd;   dd = to_lv ? d_lv : dd;   dd = to_m1 ? d_m1 : dd;
+        df = to_lt ? f_lt : df;   df = to_tb ? f_tb : df;
+        *dd = lg;
+        *df = nlg;
 #if !FC_VARIANT_BIG
-            else if (r == 9) sh.mp.wb_nd = sub_log2(sh, 0.0f, lg, ci, ti);
-            else if (r == 10) sh.mp.wb_dc = sub_log2(sh, 0.0f, lg, ci, ti);
-#endif
-            else sh.lglv[tid - 64] = lg;
-        } else if (role == 2) sh.Ltab[ci] = (float) -lg;
-#if !FC_VARIANT_BIG
-        else if (role == 3) sh.tb[r - 7] = (float) -lg;
+        if (ro.dest == MPD_WB_ND || ro.dest == MPD_WB_DC) {
+            const float wb = sub_log2(sh, 0.0f, lg, ro.ci, ro.ti);
+            if (ro.dest == MPD_WB_ND) sh.mp.wb_nd = wb; else sh.mp.wb_dc = wb;
+        }
 #endif
     }
 }
@@ -1123,21 +1136,37 @@ __device__ __forceinline__ void op_approx(DevFrame &F, Sh &sh)
 #else
 #define APX_MARK(i) do { } while (0)
 #endif
-    if (fr.coop) snap_coop_before(sh, fr, sh.sp, sh.par.ML);
-    mp_tables(F, sh, level, y);
-    __syncthreads();
-    APX_MARK(0);
     /* candidates are walked by STATE id (scratch, diag, Gram row, numerators are all state
      * indexed, so every load of phase A is direct and coalesced); pos[] gives the position in
      * the pool list that the rate model needs, -1 for states outside the pool.  State order ==
      * position order, so the 64-state blocks keep the reference's scan order. */
-    const int S = sh.states;
-    const bool regscan = !sh.band && S <= KREG * B && sh.par.max_elements <= FC_NIP + 1;   /* uniform */
-    Step0 pre;
+#define APX_REGSCAN() (!sh.band && sh.states <= KREG * B && sh.par.max_elements <= FC_NIP + 1)        /* uniform */
+    if (fr.coop) snap_coop_before(sh, fr, sh.sp, sh.par.ML);
 #if !FC_VARIANT_BIG
-    /* the scan's first reads are requested before lane 0 sets the call up */
+    /* The scan's first reads depend on nothing the call computes: they are requested in front of the table pass and
+     * cross it and lane 0's set-up in flight (MP_TABLES_INLINE; a call of the out-of-line mp_tables waits for them) */
+    const bool regscan = APX_REGSCAN();
+    Step0 pre;
+#if MP_TABLES_INLINE
+    /* vmcnt(0), as the call of the out-of-line mp_tables had it at this point: nothing an earlier operation requested
+     * is in flight here, but the compiler cannot tell (the barrier at the head of the operation loop does not wait for
+     * memory reads) and would otherwise wait for "them" -- in fact for the reads requested below -- in the middle of
+     * the table pass and of the set-up, wherever it reuses a register such a read once went to */
+    __builtin_amdgcn_s_waitcnt(0x0f70);
+#endif
     if (regscan) mp_step0_issue(sh, q, sh.par.ipis + (size_t) fr.lrange.image * P, pre);
 #endif
+    mp_tables(F, sh, level, y);
+#if MP_TABLES_INLINE && !FC_VARIANT_BIG
+    lds_barrier();                       /* the tables live in LDS */
+#else
+    __syncthreads();
+#endif
+#if FC_VARIANT_BIG
+    const bool regscan = APX_REGSCAN();  /* the row of the first reads is chosen by the set-up: requested behind it */
+    Step0 pre;
+#endif
+    APX_MARK(0);
 #if FC_VARIANT_BIG
     /* retries of approximate_range (codec/approx.c:103-206): second domain block, then removal
      * of vectors whose weight rounded to zero (underflow) or to the extreme value (overflow);
