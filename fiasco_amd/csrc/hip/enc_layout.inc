@@ -78,7 +78,7 @@ static bool needs_wide_variant(const fa_cparams *cp)
 /* ------------------------------------------------------------------ layout */
 
 struct Layout {
-    size_t gram, gcol, diag, ipis, d5, d4, img, imgT, imgT4, norms, num, den, est, ipdo, used, tree, into, weight,
+    size_t gram, gcol, diag, ipis, d5, ipt, d4, img, imgT, imgT4, norms, num, den, est, ipdo, used, tree, into, weight,
            final_d, level_of_state, domain_type, x, y, ycol, pool_states, pos, hits, ycol0, snap, pix16, total;
     size_t ipis_alt, d5_alt, d4_alt, pix_save, sv_gram, sv_img, sv_auto;   /* prediction only */
     size_t mv, past, future, mc_fwd, mc_bwd, pix_chroma;                    /* P frames only */
@@ -104,6 +104,7 @@ static Layout make_layout(int P, int PA, int NL, int NS, int NA, int NI, int il,
     CARVE(diag, (size_t) NL * P * 4);
     CARVE(ipis, (size_t) NS * P * 4);
     CARVE(d5, (size_t) NA * P * 4);
+    CARVE(ipt, (size_t) NA * P * 4);                 /* NA floats per state, one table per level (ipt_layout.h) */
     CARVE(d4, low ? (size_t) 2 * NA * P * 4 : 0);
     CARVE(img, (size_t) P * NI * 4);
     CARVE(imgT, ((size_t) 1 << il) * P * 4);

@@ -217,6 +217,7 @@ static void fill_frame(FrameSlot &fs, const fa_job *job)
     F.pix16 = (const int16_t *) (base + L.pix16);
     F.gram = (float *) (base + L.gram); F.diag = (float *) (base + L.diag);
     F.ipis = (float *) (base + L.ipis); F.d5 = (float *) (base + L.d5);
+    F.ipt = (float *) (base + L.ipt);
     F.gcol = (float *) (base + L.gcol);
     F.d4 = (float *) (base + L.d4); F.imgT4 = (float *) (base + L.imgT4);
     F.img = (float *) (base + L.img); F.imgT = (float *) (base + L.imgT);

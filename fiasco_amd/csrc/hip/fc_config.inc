@@ -1,7 +1,7 @@
 /*
  *  fc_config.inc -- the build configuration of the frame kernel: the geometry of each build
  *  (FC_VARIANT_WIDE, FC_VARIANT_BIG, FC_HM, FC_GM, FC_SPEC: csrc/Makefile), B, FC_KREG and the
- *  per-build kernel and launch symbol names; the FC_SPEC, FC_D5T and FC_PRIO_ROTATE defaults;
+ *  per-build kernel and launch symbol names; the FC_SPEC, FC_D5T, FC_IPT and FC_PRIO_ROTATE defaults;
  *  constants; the operation (OP_*) and phase (PH_*) enums; FC_DUP and FC_DEPTH.
  *
  *  Reference: no code of its own; the constants and phases are those of the partition search,
@@ -112,8 +112,22 @@
 /* FC_D5T: the table of level-images_level dots is kept state-major, d5T[state][label][NA / 2] (address a ->
  * label a & 1, column a >> 1), so that the first pass of op_ipis reads four consecutive slots of one term with
  * ONE 16-byte load instead of four 4-byte gathers from four rows.  Same values, same sums.  Not in the big
- * build: it reads d5 rows as matching pursuit numerators. */
+ * build: it reads d5 rows as matching pursuit numerators.  The levels above the first read their sources the same
+ * way where FC_IPT is set (below). */
 #define FC_D5T (!FC_VARIANT_BIG)
+/* FC_IPT: a state-major copy of the block's <sub-block, state> entries of the levels between images_level and lc_max,
+ * one table [P][entries of the level] per level (DevFrame.ipt, ipt_layout.h), beside the slot-major table.  Every level
+ * of op_ipis_t above the first then reads the `cnt` slots of a term with ONE load of up to 16 bytes from the domain's
+ * row, instead of one 4-byte gather per slot from a line per (slot, label, term).  Same values, same sums; the matching
+ * pursuit keeps reading slot-major rows.  Every writer of a slot-major entry that a later level may read also writes
+ * the ipt entry (op_ipis_t; op_ipis_sparse never mixes with it inside a block).  Not in the big builds, and not in the
+ * speculating ones: their blocks' tables live in ring buffers laid out as [NS][P] + [NA][P] (FcSpecCtl.tab_stride). */
+#ifndef FC_IPT
+#define FC_IPT (!FC_VARIANT_BIG && !FC_SPEC)
+#endif
+#if FC_IPT && !FC_D5T
+#error "FC_IPT goes with the state-major level-images_level dots (FC_D5T)"
+#endif
 #if FC_D5T
 #define D5_AT(P, NA, a, s) ((unsigned) (s) * (unsigned) (NA) + (unsigned) ((a) & 1) * ((unsigned) (NA) >> 1) + ((unsigned) (a) >> 1))
 #else

@@ -8,6 +8,7 @@
  *  Part of the frame kernel: frame_coder.hip includes it (see the map there); it does not
  *  compile alone.
  */
+#include "ipt_layout.h"               /* where the state-major copy of the recursion's sources keeps an entry (FC_IPT) */
 
 /* ------------------------------------------------------------------ parallel ops */
 
@@ -76,17 +77,30 @@ template <int E> __device__ __forceinline__ void load_edge_rows(const AutoTabs &
 
 /* <sub-block, state> tables for states [from, states) and the heap subtree under `image`
  * (codec/ip.c:72-154).  Per slot the additions run label 0 {child, edges}, label 1 {...}
- * onto zero, which is the reference's accumulation order onto its zeroed slots. */
+ * onto zero, which is the reference's accumulation order onto its zeroed slots.
+ * FC_IPT: the levels above the first read their sources from the state-major copy DevFrame.ipt, and every level
+ * below lc_max writes its results there as well as slot-major (fc_config.inc, ipt_layout.h). */
 /* E: edge slots per label read and summed (the build's E; 3 in the big build when neither the options nor
  * the basis allow more: dead slots still cost a gather per slot and state) */
 template <int E> __device__ __noinline__ void op_ipis_t(const DevFrame &__restrict__ F, Sh &__restrict__ sh, int image, int address, int level, int from, int lv_first)
 {
+#if FC_IPT
+    /* wave-uniform, so that the level, its slot count and the choice of the source table stay in scalar registers */
+    const int tid = threadIdx.x, il = __builtin_amdgcn_readfirstlane(F.images_level);
+#else
     const int tid = threadIdx.x, il = F.images_level;
+#endif
     const int P = __builtin_amdgcn_readfirstlane(F.P), states = __builtin_amdgcn_readfirstlane(table_states(sh));
     image = __builtin_amdgcn_readfirstlane(image); address = __builtin_amdgcn_readfirstlane(address);
     level = __builtin_amdgcn_readfirstlane(level); from = __builtin_amdgcn_readfirstlane(from);
     GLOBAL_AS float *const ipis = uniform_ptr(ACT_IPIS(F, sh));
     GLOBAL_AS const float *const d5 = uniform_ptr((const float *) ACT_D5(F, sh));
+#if FC_IPT
+    /* the state-major copy of the entries below level lc_max (ipt_layout.h): what the levels above the first read,
+     * and where every level below lc_max leaves its results beside the slot-major ones */
+    GLOBAL_AS float *const ipt = uniform_ptr(F.ipt);
+    const int lc_max = __builtin_amdgcn_readfirstlane(F.lc_max);
+#endif
     AutoTabs T;
     auto_tabs(F, T);
     lv_first = __builtin_amdgcn_readfirstlane(lv_first);
@@ -98,8 +112,21 @@ template <int E> __device__ __noinline__ void op_ipis_t(const DevFrame &__restri
 #if FC_D5T
         const bool first = lv == il + 1;
         const unsigned NAu = (unsigned) __builtin_amdgcn_readfirstlane(F.NA), NAh = NAu >> 1;
+#if FC_IPT
+        /* State-major sources at every level: the cnt slots of a term and label are cnt consecutive floats of the
+         * domain's row -- of d5 at the first level (NA floats per state), of the ipt table of the level below above
+         * it (2 n_lv floats per state) -- from float lb[label] + adr0 of the row on.  cnt is a power of two and adr0
+         * a multiple of it, and so are the rows and their halves wherever they hold cnt or more entries: every
+         * load is aligned to its width (tests/ipt_layout_check.cpp walks them all). */
+        const unsigned n_lv = ipt_n(lc_max, lv);
+        GLOBAL_AS const float *src0 = first ? d5 : (GLOBAL_AS const float *) ipt;
+        const unsigned Pu = (unsigned) P, rs = first ? NAu : 2u * n_lv;
+        const unsigned lb[2] = { first ? 0u : ipt_row(Pu, NAu, 2u * n_lv, 0u) + ipt_src_col(n_lv, 0u, 0u),
+                                 first ? NAh : ipt_row(Pu, NAu, 2u * n_lv, 0u) + ipt_src_col(n_lv, 1u, 0u) };
+#else
         const bool vec4 = first && cnt >= 4 && (NAh & 3u) == 0;          /* adr0 is a multiple of cnt */
         GLOBAL_AS const float *src0 = first ? d5 : ipis + (size_t) (slot0 * 2 + 1) * P;
+#endif
 #else
         GLOBAL_AS const float *src0 = (lv == il + 1) ? d5 + (size_t) (adr0 * 2) * P
                                                      : ipis + (size_t) (slot0 * 2 + 1) * P;
@@ -155,6 +182,45 @@ template <int E> __device__ __noinline__ void op_ipis_t(const DevFrame &__restri
             constexpr int JG = 4;          /* slots per group: 4 x 2 x (E + 1) gathers in flight per lane (8: -5 %) */
             for (int j0 = 0; j0 < cnt; j0 += JG) {
                 float v[JG][2][E + 1];
+#if FC_IPT
+                /* UNCONDITIONAL loads (a dead term reads the same columns of row 0, which lie inside the table
+                 * whatever they hold): a conditional load becomes a branch with its own s_waitcnt and the loads
+                 * would run one after the other instead of all in flight.  ONE load per term and label brings
+                 * all slots of the group: 16 bytes for four, 8 for the two slots of the level below the call's,
+                 * 4 for the call's own slot -- no slot is read that the group does not have. */
+                /* one scalar base and one 32-bit byte offset per term, whatever the width (ldg's addressing) */
+                unsigned ob[2][E + 1];
+#pragma unroll
+                for (int l = 0; l < 2; l++)
+#pragma unroll
+                    for (int i = 0; i <= E; i++) ob[l][i] = ((unsigned) idx[l][i] * rs + lb[l] + (unsigned) (adr0 + j0)) * 4u;
+                if (cnt >= 4) {
+                    typedef float f4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+                    for (int l = 0; l < 2; l++)
+#pragma unroll
+                        for (int i = 0; i <= E; i++) {
+                            const f4 q = *(GLOBAL_AS const f4 *) ((GLOBAL_AS const char *) src0 + ob[l][i]);
+                            v[0][l][i] = q.x; v[1][l][i] = q.y; v[2][l][i] = q.z; v[3][l][i] = q.w;
+                        }
+                } else if (cnt == 2) {
+                    typedef float f2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+                    for (int l = 0; l < 2; l++)
+#pragma unroll
+                        for (int i = 0; i <= E; i++) {
+                            const f2 q = *(GLOBAL_AS const f2 *) ((GLOBAL_AS const char *) src0 + ob[l][i]);
+                            v[0][l][i] = q.x; v[1][l][i] = q.y;
+                        }
+                } else {
+#pragma unroll
+                    for (int l = 0; l < 2; l++)
+#pragma unroll
+                        for (int i = 0; i <= E; i++)
+                            v[0][l][i] = *(GLOBAL_AS const float *) ((GLOBAL_AS const char *) src0 + ob[l][i]);
+                }
+                float res[JG];
+#else
 #if FC_D5T
                 if (vec4) {
                     typedef float f4 __attribute__((ext_vector_type(4)));
@@ -191,6 +257,7 @@ template <int E> __device__ __noinline__ void op_ipis_t(const DevFrame &__restri
                             const int jc = j0 + jj < cnt ? j0 + jj : cnt - 1;
                             v[jj][l][i] = ldg(src0, (unsigned) idx[l][i] + (unsigned) ((jc * 2 + l) * P));
                         }
+#endif
 #pragma unroll
                 for (int jj = 0; jj < JG; jj++) {
                     if (j0 + jj >= cnt) break;
@@ -203,7 +270,26 @@ template <int E> __device__ __noinline__ void op_ipis_t(const DevFrame &__restri
                             if ((msk[l] >> i) & 1u) acc += wt[l][i] * v[jj][l][i];
                     }
                     stg(ipis, (unsigned) s + (unsigned) ((slot0 + j0 + jj) * P), acc);
+#if FC_IPT
+                    res[jj] = acc;
+#endif
                 }
+#if FC_IPT
+                /* ... and, below level lc_max, into the state's row of this level's ipt table, for the level above: the
+                 * even and the odd addresses of a group of four are two neighbouring columns each */
+                if (lv < lc_max) {
+                    const unsigned a0 = (unsigned) (adr0 + j0), row = ipt_row(Pu, NAu, n_lv, (unsigned) s);
+                    if (cnt >= 4) {
+                        typedef float f2 __attribute__((ext_vector_type(2)));
+                        const f2 ev = { res[0], res[2] }, od = { res[1], res[3] };
+                        *(GLOBAL_AS f2 *) ((GLOBAL_AS char *) ipt + (row + ipt_col(n_lv, a0)) * 4u) = ev;
+                        *(GLOBAL_AS f2 *) ((GLOBAL_AS char *) ipt + (row + ipt_col(n_lv, a0 + 1u)) * 4u) = od;
+                    } else {
+                        stg(ipt, row + ipt_col(n_lv, a0), res[0]);
+                        if (cnt == 2) stg(ipt, row + ipt_col(n_lv, a0 + 1u), res[1]);
+                    }
+                }
+#endif
             }
         }
         __syncthreads();
@@ -537,7 +623,10 @@ __device__ void op_d5_sparse(const DevFrame &__restrict__ F, Sh &__restrict__ sh
 }
 
 /* op_ipis for the (state, level) pairs of the closure: per level the items (state, slot); the additions of an entry
- * in the reference's order -- label 0 {tree child, edges}, label 1 {...} onto zero (codec/ip.c:104-146) */
+ * in the reference's order -- label 0 {tree child, edges}, label 1 {...} onto zero (codec/ip.c:104-146).
+ * Slot-major only, sources and results, also where op_ipis_t keeps a state-major copy (FC_IPT): the two never mix
+ * inside a block -- a sparse block is built by this function alone, and the only later writer of a block's entries,
+ * OP_IPIS_INCR, is not issued in a chroma band (`!sh.band', fc_serial.inc). */
 __device__ void op_ipis_sparse(const DevFrame &__restrict__ F, Sh &__restrict__ sh, int level)
 {
     const int tid = threadIdx.x, il = F.images_level, P = F.P;

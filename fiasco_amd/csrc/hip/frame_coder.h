@@ -16,6 +16,10 @@
  *    ipis   [NS][P]    f32  <range sub-block, state>, heap slot major
  *                           (reference ip_images_state, codec/cwfa.h:89, is state major)
  *    d5     [NA][P]    f32  level-images_level dots of the current block, address major
+ *                           (default builds, FC_D5T: state major, [P][2][NA / 2])
+ *    ipt    [NA][P]    f32  state-major copy of the ipis entries of the levels between images_level and
+ *                           lc_max, one table [P][2^(lc_max - level)] per level: the sources of the level
+ *                           recursion (FC_IPT builds, ipt_layout.h)
  *    img    [P][NI]    f32  state images levels 0..images_level (reference layout)
  *    imgT   [2^il][P]  f32  level-images_level slice of img, pixel major (coalesced dots)
  *    d4, imgT4             the same one level lower, only when min block level is 4
@@ -160,6 +164,8 @@ typedef struct DevFrame {
                             * (measured with the oracle); their sweep reads this row instead of one 4-byte gather
                             * (a whole HBM line) per candidate */
     float   *d4, *imgT4;   /* level images_level-1 twins of d5 / imgT (block levels down to 4) */
+    float   *ipt;          /* NA * P floats: the block's ipis entries below level lc_max, state major level by level (FC_IPT
+                            * builds of the kernel, ipt_layout.h): what the level recursion reads; the other builds leave it alone */
     float   *num, *den, *est, *ipdo;
     uint8_t *used;
     int16_t *tree, *into;

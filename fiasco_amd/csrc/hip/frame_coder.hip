@@ -9,7 +9,8 @@
  *    fc_lds.inc        LDS layout: the range stack, model pools and snapshots, Sh
  *    fc_access.inc     small helpers, hand-offs between workgroups, Gram and image table access
  *                                  lib/rpf.c:59-169, lib/misc.c:223-244
- *    fc_tables.inc     inner-product tables, FcCoop, chroma-need closure, op_init_range
+ *    fc_tables.inc     inner-product tables, FcCoop, chroma-need closure, op_init_range (and ipt_layout.h,
+ *                      which it includes: the state-major copy of the recursion's sources, FC_IPT)
  *                                  codec/ip.c:46-323, codec/subdivide.c:504-541,612-644
  *    fc_append.inc     state append, chroma domain pool
  *                                  codec/control.c:48-131,205-258, codec/domain-pool.c:621-852
