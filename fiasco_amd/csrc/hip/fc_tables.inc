@@ -75,6 +75,31 @@ template <int E> __device__ __forceinline__ void load_edge_rows(const AutoTabs &
     }
 }
 
+#if FC_IPT
+/* term list of a state for the item loop of op_ipis_t: per label the tree child (weight 1, added plain) and
+ * the edges in stored order.  Fixed-trip, predicated loops so that all loads of a group of slots are in
+ * flight together (the chain is latency bound).  msk: bit 0 the child, bit e + 1 edge e; a dead term has
+ * index 0 and weight 0. */
+template <int E> __device__ __forceinline__ void ipis_terms(const EdgeRowsT<E> &cur, int (&idx)[2][E + 1], float (&wt)[2][E + 1], unsigned (&msk)[2])
+{
+#pragma unroll
+    for (int l = 0; l < 2; l++) {
+        int k = cur.tree[l];
+        msk[l] = k != RANGE_ ? 1u : 0u;
+        idx[l][0] = k != RANGE_ ? k : 0;
+        wt[l][0] = 1.0f;
+        bool live = true;
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            live = live && cur.rd[l][e] != NOEDGE;
+            idx[l][e + 1] = live ? cur.rd[l][e] : 0;
+            wt[l][e + 1] = live ? cur.rw[l][e] : 0.0f;
+            msk[l] |= live ? (2u << e) : 0u;
+        }
+    }
+}
+#endif
+
 /* <sub-block, state> tables for states [from, states) and the heap subtree under `image`
  * (codec/ip.c:72-154).  Per slot the additions run label 0 {child, edges}, label 1 {...}
  * onto zero, which is the reference's accumulation order onto its zeroed slots.
@@ -149,6 +174,96 @@ template <int E> __device__ __noinline__ void op_ipis_t(const DevFrame &__restri
             if (from < V.nb) s = V.nb + tid;
         }
 #endif
+#if FC_IPT
+        /* Work items, not states (ipt_layout.h): G = cnt / 4 neighbouring lanes serve one state where the level has 8 or
+         * more slots in the subtree, one group of four slots each -- the loads of a term by the lanes of a state are
+         * neighbouring 16-byte pieces of one row in ONE instruction, and a lane has one round of loads per level
+         * instead of cnt / 4 dependent ones.  G divides the wave and B: the lanes of a state are neighbours in one wave
+         * with the same state in every round (tests/ipis_items_check.cpp walks them all). */
+        const unsigned lgG = ipis_lanes_log2((unsigned) cnt), j0 = ipis_item_j0((unsigned) tid, lgG);
+        const int sB = B >> lgG;
+        s = from + (int) ipis_item_state((unsigned) tid, lgG);
+        /* the rows of the NEXT item of this lane are requested before the loads of the current one are waited for */
+        EdgeRowsT<E> nx;
+        if (s < states) load_edge_rows(T, s, nx);
+        for (; s < states; s += sB) {
+            const EdgeRowsT<E> cur = nx;
+            if (s + sB < states) load_edge_rows(T, s + sB, nx);
+            const bool tabled = cur.dt && !DEAD(sh, s);
+            if (!tabled) continue;
+            int   idx[2][E + 1];
+            float wt[2][E + 1];
+            unsigned msk[2];
+            ipis_terms<E>(cur, idx, wt, msk);
+            float v[4][2][E + 1];
+            /* UNCONDITIONAL loads (a dead term reads the same columns of row 0, which lie inside the table
+             * whatever they hold): a conditional load becomes a branch with its own s_waitcnt and the loads
+             * would run one after the other instead of all in flight.  ONE load per term and label brings
+             * all slots of the group: 16 bytes for four, 8 for the two slots of the level below the call's,
+             * 4 for the call's own slot -- no slot is read that the group does not have. */
+            /* one scalar base and one 32-bit byte offset per term, whatever the width (ldg's addressing) */
+            unsigned ob[2][E + 1];
+#pragma unroll
+            for (int l = 0; l < 2; l++)
+#pragma unroll
+                for (int i = 0; i <= E; i++) ob[l][i] = ((unsigned) idx[l][i] * rs + lb[l] + (unsigned) adr0 + j0) * 4u;
+            typedef float f4 __attribute__((ext_vector_type(4)));
+            typedef float f2 __attribute__((ext_vector_type(2)));
+            if (cnt >= 4) {
+#pragma unroll
+                for (int l = 0; l < 2; l++)
+#pragma unroll
+                    for (int i = 0; i <= E; i++) {
+                        const f4 q = *(GLOBAL_AS const f4 *) ((GLOBAL_AS const char *) src0 + ob[l][i]);
+                        v[0][l][i] = q.x; v[1][l][i] = q.y; v[2][l][i] = q.z; v[3][l][i] = q.w;
+                    }
+            } else if (cnt == 2) {
+#pragma unroll
+                for (int l = 0; l < 2; l++)
+#pragma unroll
+                    for (int i = 0; i <= E; i++) {
+                        const f2 q = *(GLOBAL_AS const f2 *) ((GLOBAL_AS const char *) src0 + ob[l][i]);
+                        v[0][l][i] = q.x; v[1][l][i] = q.y;
+                    }
+            } else {
+#pragma unroll
+                for (int l = 0; l < 2; l++)
+#pragma unroll
+                    for (int i = 0; i <= E; i++)
+                        v[0][l][i] = *(GLOBAL_AS const float *) ((GLOBAL_AS const char *) src0 + ob[l][i]);
+            }
+            float res[4];
+            /* slot-major, what the matching pursuit reads: plain 4-byte stores */
+            const unsigned os = (unsigned) s + j0 * Pu;
+#pragma unroll
+            for (int jj = 0; jj < 4; jj++) {
+                if (jj >= cnt) break;
+                float acc = 0;
+#pragma unroll
+                for (int l = 0; l < 2; l++) {
+                    if (msk[l] & 1u) acc += v[jj][l][0];
+#pragma unroll
+                    for (int i = 1; i <= E; i++)
+                        if ((msk[l] >> i) & 1u) acc += wt[l][i] * v[jj][l][i];
+                }
+                stg(ipis + (size_t) ((slot0 + jj) * P), os, acc);
+                res[jj] = acc;
+            }
+            /* ... and, below level lc_max, into the state's row of this level's ipt table, for the level above */
+            if (lv < lc_max) {
+                const unsigned a0 = (unsigned) adr0 + j0, row = ipt_row(Pu, NAu, n_lv, (unsigned) s);
+                if (cnt >= 4) {
+                    /* the even and the odd addresses of a group of four are two neighbouring columns each */
+                    const f2 ev = { res[0], res[2] }, od = { res[1], res[3] };
+                    *(GLOBAL_AS f2 *) ((GLOBAL_AS char *) ipt + (row + ipt_col(n_lv, a0)) * 4u) = ev;
+                    *(GLOBAL_AS f2 *) ((GLOBAL_AS char *) ipt + (row + ipt_col(n_lv, a0 + 1u)) * 4u) = od;
+                } else {
+                    stg(ipt, row + ipt_col(n_lv, a0), res[0]);
+                    if (cnt == 2) stg(ipt, row + ipt_col(n_lv, a0 + 1u), res[1]);
+                }
+            }
+        }
+#else
         /* the rows of the NEXT state of this lane are requested before the gathers of the
          * current one are waited for (one memory round trip per state instead of two) */
         EdgeRowsT<E> nx;
@@ -182,45 +297,6 @@ template <int E> __device__ __noinline__ void op_ipis_t(const DevFrame &__restri
             constexpr int JG = 4;          /* slots per group: 4 x 2 x (E + 1) gathers in flight per lane (8: -5 %) */
             for (int j0 = 0; j0 < cnt; j0 += JG) {
                 float v[JG][2][E + 1];
-#if FC_IPT
-                /* UNCONDITIONAL loads (a dead term reads the same columns of row 0, which lie inside the table
-                 * whatever they hold): a conditional load becomes a branch with its own s_waitcnt and the loads
-                 * would run one after the other instead of all in flight.  ONE load per term and label brings
-                 * all slots of the group: 16 bytes for four, 8 for the two slots of the level below the call's,
-                 * 4 for the call's own slot -- no slot is read that the group does not have. */
-                /* one scalar base and one 32-bit byte offset per term, whatever the width (ldg's addressing) */
-                unsigned ob[2][E + 1];
-#pragma unroll
-                for (int l = 0; l < 2; l++)
-#pragma unroll
-                    for (int i = 0; i <= E; i++) ob[l][i] = ((unsigned) idx[l][i] * rs + lb[l] + (unsigned) (adr0 + j0)) * 4u;
-                if (cnt >= 4) {
-                    typedef float f4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-                    for (int l = 0; l < 2; l++)
-#pragma unroll
-                        for (int i = 0; i <= E; i++) {
-                            const f4 q = *(GLOBAL_AS const f4 *) ((GLOBAL_AS const char *) src0 + ob[l][i]);
-                            v[0][l][i] = q.x; v[1][l][i] = q.y; v[2][l][i] = q.z; v[3][l][i] = q.w;
-                        }
-                } else if (cnt == 2) {
-                    typedef float f2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-                    for (int l = 0; l < 2; l++)
-#pragma unroll
-                        for (int i = 0; i <= E; i++) {
-                            const f2 q = *(GLOBAL_AS const f2 *) ((GLOBAL_AS const char *) src0 + ob[l][i]);
-                            v[0][l][i] = q.x; v[1][l][i] = q.y;
-                        }
-                } else {
-#pragma unroll
-                    for (int l = 0; l < 2; l++)
-#pragma unroll
-                        for (int i = 0; i <= E; i++)
-                            v[0][l][i] = *(GLOBAL_AS const float *) ((GLOBAL_AS const char *) src0 + ob[l][i]);
-                }
-                float res[JG];
-#else
 #if FC_D5T
                 if (vec4) {
                     typedef float f4 __attribute__((ext_vector_type(4)));
@@ -257,7 +333,6 @@ template <int E> __device__ __noinline__ void op_ipis_t(const DevFrame &__restri
                             const int jc = j0 + jj < cnt ? j0 + jj : cnt - 1;
                             v[jj][l][i] = ldg(src0, (unsigned) idx[l][i] + (unsigned) ((jc * 2 + l) * P));
                         }
-#endif
 #pragma unroll
                 for (int jj = 0; jj < JG; jj++) {
                     if (j0 + jj >= cnt) break;
@@ -270,28 +345,10 @@ template <int E> __device__ __noinline__ void op_ipis_t(const DevFrame &__restri
                             if ((msk[l] >> i) & 1u) acc += wt[l][i] * v[jj][l][i];
                     }
                     stg(ipis, (unsigned) s + (unsigned) ((slot0 + j0 + jj) * P), acc);
-#if FC_IPT
-                    res[jj] = acc;
-#endif
                 }
-#if FC_IPT
-                /* ... and, below level lc_max, into the state's row of this level's ipt table, for the level above: the
-                 * even and the odd addresses of a group of four are two neighbouring columns each */
-                if (lv < lc_max) {
-                    const unsigned a0 = (unsigned) (adr0 + j0), row = ipt_row(Pu, NAu, n_lv, (unsigned) s);
-                    if (cnt >= 4) {
-                        typedef float f2 __attribute__((ext_vector_type(2)));
-                        const f2 ev = { res[0], res[2] }, od = { res[1], res[3] };
-                        *(GLOBAL_AS f2 *) ((GLOBAL_AS char *) ipt + (row + ipt_col(n_lv, a0)) * 4u) = ev;
-                        *(GLOBAL_AS f2 *) ((GLOBAL_AS char *) ipt + (row + ipt_col(n_lv, a0 + 1u)) * 4u) = od;
-                    } else {
-                        stg(ipt, row + ipt_col(n_lv, a0), res[0]);
-                        if (cnt == 2) stg(ipt, row + ipt_col(n_lv, a0 + 1u), res[1]);
-                    }
-                }
-#endif
             }
         }
+#endif
         __syncthreads();
     }
 }

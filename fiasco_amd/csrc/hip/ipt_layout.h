@@ -39,4 +39,20 @@ IPT_FN unsigned ipt_src_col(unsigned n, unsigned l, unsigned a) { return l * n +
 /* floats per load and term of a level with `cnt` slots in the call's subtree (groups of at most four slots): 4, 2 or 1 */
 IPT_FN unsigned ipt_width(unsigned cnt) { return cnt >= 4u ? 4u : cnt; }
 
+/*
+ *  Work items of the level recursion: a level with `cnt` slots in the call's subtree gives every state
+ *  G = cnt >= 8 ? cnt / 4 : 1 neighbouring lanes, one per group of four slots (4 lanes at the first level of a whole
+ *  block of the default geometry, 2 at the second, 1 above).  Item i = tid + k B serves state `from` + i / G and the
+ *  slots j0 .. j0 + 3 of the subtree, j0 = 4 (i % G).  G is a power of two that divides the wave and the workgroup: the
+ *  lanes of a state are an aligned group of one wave, i % G is the same in every round k, and the G loads of a term are
+ *  G neighbouring 16-byte pieces of the domain's row in one instruction.  Every lane stores its own results, as pairs of
+ *  equal parity (whole rows through an exchange inside the quad measured slower: LABNOTES, experiments/ipis_items).
+ */
+/* log2 of the lanes per state (cnt is a power of two) */
+IPT_FN unsigned ipis_lanes_log2(unsigned cnt) { return cnt >= 8u ? (unsigned) __builtin_ctz(cnt) - 2u : 0u; }
+IPT_FN unsigned ipis_lanes(unsigned cnt) { return 1u << ipis_lanes_log2(cnt); }
+/* state of item i, counted from the call's first state; first slot of its group, counted from the subtree's first */
+IPT_FN unsigned ipis_item_state(unsigned i, unsigned lgG) { return i >> lgG; }
+IPT_FN unsigned ipis_item_j0(unsigned i, unsigned lgG) { return 4u * (i & ((1u << lgG) - 1u)); }
+
 #endif
