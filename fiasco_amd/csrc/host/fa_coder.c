@@ -283,6 +283,27 @@ int fiasco_coder(char const *const *inputname, const char *outputname, float qua
                      "path reads outside the reference frame).");
         goto done;
     }
+    /* A pattern that leaves a P or B frame without a reference frame (`ibbi'): the reference coder dies at that
+     * frame's first motion search, the cores refuse it there.  For gray frames the search is certain once the
+     * prediction window holds a level -- only the chroma bands of a colour frame move the minimum block level
+     * (codec/coder.c:785-797), and a colour frame that has moved it above the window is coded without a search, by
+     * the reference too -- so a gray sequence is refused here, with the cores' message.  A look at the first frame
+     * tells; whatever is wrong with that file is left to the reads below, in the reference's order. */
+    if (nframes > 1 && strcmp(names[0], "-") != 0 && fa_seq_pattern_lacks_reference(nframes, op->pattern, op->B_as_past_ref)) {
+        size_t len = 0, off;
+        unsigned w, h;
+        int color, certain = 0;
+        unsigned char *first = fa_read_whole_file(names[0], "FIASCO_IMAGES", &len);
+        if (first && fa_pnm_header(first, len, names[0], &w, &h, &color, &off) && !color) {
+            fa_info wi;
+            fa_cparams cp;
+            memset(&wi, 0, sizeof wi);
+            if (fa_setup_params(op, quality, w, h, color, nframes, &wi, &cp)) certain = wi.p_max_level >= cp.lc_min_level;
+            fa_info_free(&wi);
+        }
+        free(first);
+        if (certain) { fa_set_error("Motion search without a reference frame (frame pattern)."); goto done; }
+    }
 
     /* the reference opens (and truncates) the output stream before anything else can fail */
     fout = open_file(outputname, "FIASCO_DATA", WRITE_ACCESS);

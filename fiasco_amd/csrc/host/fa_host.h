@@ -394,6 +394,9 @@ int16_t *fa_compute_hits(unsigned from, unsigned to, unsigned n, const fa_wfa *w
 typedef struct fa_seq fa_seq;
 fa_seq *fa_seq_open(const fa_options *op, float quality, unsigned nframes, const unsigned char *const *bufs,
                     const size_t *lens, char const *const *names, unsigned rank, unsigned world);
+/* 1 if `pattern' over nframes frames codes a P or B frame one of whose reference frames is missing (`ibbi': an I frame
+ * as the future reference of a run of B frames drops the past reference); 0 if not, or if the pattern is not valid */
+int fa_seq_pattern_lacks_reference(unsigned nframes, const char *pattern, int B_as_past_ref);
 /* the same for frames that are images already (display order; no host planes needed: fa_image.src_dev): the sequence
  * takes images[] and its entries over, also when it refuses them.  release(ctx) runs when the sequence goes -- whoever
  * made the images gives back what their planes lie in (the host C names no core function) */

@@ -131,6 +131,27 @@ static int coding_order(unsigned nframes, const char *pattern, unsigned *order, 
     return (int) k;
 }
 
+/* The walk of fa_seq_search over the reference frames (codec/coder.c:580-628) with "there is one" in place of the
+ * frames: after a frame has been coded there always is a reconstruction. */
+int fa_seq_pattern_lacks_reference(unsigned nframes, const char *pattern, int B_as_past_ref)
+{
+    unsigned *order = (unsigned *) calloc(nframes ? nframes : 1, sizeof *order);
+    int *type = (int *) calloc(nframes ? nframes : 1, sizeof *type), *isfut = (int *) calloc(nframes ? nframes : 1, sizeof *isfut);
+    int n = order && type && isfut && nframes ? coding_order(nframes, pattern, order, type, isfut) : 0;
+    int past = 0, future = 0, reconst = 0, last_was_future = 0, lacks = 0, k;
+    for (k = 0; k < n && !lacks; k++) {
+        if (type[k] == FA_I_FRAME) past = future = 0;
+        else if (type[k] == FA_P_FRAME) { past = reconst; future = 0; }
+        else if (last_was_future) future = reconst;
+        else if (B_as_past_ref) past = reconst;
+        last_was_future = isfut[k];
+        lacks = (type[k] != FA_I_FRAME && !past) || (type[k] == FA_B_FRAME && !future);
+        reconst = 1;
+    }
+    free(order); free(type); free(isfut);
+    return lacks;
+}
+
 void fa_seq_free(fa_seq *s)
 {
     unsigned k;
