@@ -167,6 +167,8 @@ struct OcOut;                                   /* output_convert.inc */
 struct DsOut;                                   /* distortion.inc */
 static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const DsOut *ds, bool images = false);      /* frame_decoder.inc */
 
+#include "px_access.inc"          /* the partial 16-byte accesses of the pixel kernels below; the one host-replay switch */
+#include "frame_table.inc"        /* how those kernels walk the frames of a launch, how they are launched */
 #include "input_convert.inc"
 #include "input_convert_ycbcr.inc" /* beside input_convert.inc: NV12 / NV21 / I420 / planar 4:4:4 bytes instead of gray and RGB, through the same plumbing */
 #include "output_convert.inc"

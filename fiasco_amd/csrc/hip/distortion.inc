@@ -19,7 +19,7 @@
  *  8192 x 8192 reaches 4.4e12).
  *
  *  Shape: a work item is 16 neighbouring pixels of one row of one plane -- two 16-byte loads per side where the row
- *  allows it (oc_load16: a row of a plane is width * 2 bytes from the last and need not start on 16 bytes), pixels
+ *  allows it (px_load_values: a row of a plane is width * 2 bytes from the last and need not start on 16 bytes), pixels
  *  beyond the end of the row read as zero on both sides and add nothing.  blockIdx.y names the plane (DsPlane: one
  *  band of one frame), the workgroups of one plane stride over its items; a thread's sums go through the wave by
  *  shuffles, through the four waves by LDS, and ONE 64-bit atomicAdd and ONE atomicMax per workgroup reach the
@@ -51,12 +51,12 @@ __global__ void __launch_bounds__(256) ds_distortion_kernel(const DsPlane *__res
         const unsigned n = P.width - x0 < 16 ? P.width - x0 : 16;
         const size_t at = (size_t) row * P.width + x0;
         unsigned va[8], vb[8];
-        oc_load16(P.a + at, n, va);
-        oc_load16(P.b + at, n, vb);
+        px_load_values(P.a + at, n, va);
+        px_load_values(P.b + at, n, vb);
         unsigned part = 0;                                      /* <= 16 * 255 * 255 */
 #pragma unroll
         for (unsigned k = 0; k < 16; k++) {
-            const int d = (int) oc_clip255(oc_int(va, k) + 128) - (int) oc_clip255(oc_int(vb, k) + 128);
+            const int d = (int) px_clip255(px_int(va, k) + 128) - (int) px_clip255(px_int(vb, k) + 128);
             const unsigned ad = (unsigned) (d < 0 ? -d : d);
             part += ad * ad;
             mx = ad > mx ? ad : mx;
@@ -110,7 +110,7 @@ static bool ds_launch(const DsPlane *d_tab, const std::vector<DsPlane> &tab, voi
     if (tab.empty()) return true;
     unsigned most = 0;
     for (const DsPlane &p : tab) if (p.cpr * p.height > most) most = p.cpr * p.height;
-    unsigned gx = (most + 255) / 256, cap = (unsigned) ((size_t) (ncu > 0 ? ncu : 256) * 8 / tab.size());
+    unsigned gx = (most + 255) / 256, cap = (unsigned) (ft_groups(ncu) / tab.size());
     if (cap < 1) cap = 1;
     if (gx > cap) gx = cap;
     if (!gx) return true;
@@ -168,31 +168,6 @@ extern "C" int fiasco_amd_batch_decode_distortion_device(const fiasco_amd_batch_
     return ds_decode_batch(who, b, B, sse, maxdiff, targets, stream);
 }
 
-/* planes of `bytes' bytes at p: device memory, inside the allocation p belongs to.  *device: where they live */
-static bool ds_check_planes(const char *which, const int16_t *p, size_t bytes, int *device)
-{
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice) {
-        (void) hipGetLastError();
-        fa_set_error("fiasco_amd_planes_distortion_device: the planes `%s' are not in device memory.", which);
-        return false;
-    }
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) p) != hipSuccess) {
-        (void) hipGetLastError();
-        fa_set_error("fiasco_amd_planes_distortion_device: the device allocation of the planes `%s' cannot be determined.", which);
-        return false;
-    }
-    if ((const char *) p + bytes > (const char *) base + size) {
-        fa_set_error("fiasco_amd_planes_distortion_device: the planes `%s' reach %lu bytes beyond the end of their device allocation.", which,
-                     (unsigned long) ((const char *) p + bytes - ((const char *) base + size)));
-        return false;
-    }
-    *device = at.device;
-    return true;
-}
-
 extern "C" int fiasco_amd_planes_distortion_device(const int16_t *a, const int16_t *b, int bands, unsigned width, unsigned height,
                                                    unsigned long long sse[3], unsigned maxdiff[3], void *stream)
 {
@@ -206,7 +181,10 @@ extern "C" int fiasco_amd_planes_distortion_device(const int16_t *a, const int16
     if (!ic_have_device()) return 0;
     const size_t bytes = (size_t) width * height * (unsigned) bands * 2;
     int adev = -1, bdev = -1, cur = -1;
-    if (!ds_check_planes("a", a, bytes, &adev) || !ds_check_planes("b", b, bytes, &bdev)) return 0;
+    /* compared in place and only read, yet an allocation that cannot be told is refused here */
+    const char *who = "fiasco_amd_planes_distortion_device";
+    if (!ic_check_memory(who, "planes `a' are", "planes `a'", a, bytes, "planes `a'", &adev)
+        || !ic_check_memory(who, "planes `b' are", "planes `b'", b, bytes, "planes `b'", &bdev)) return 0;
     if (adev != bdev) {
         fa_set_error("fiasco_amd_planes_distortion_device: the planes `a' live on device %d, the planes `b' on device %d (no peer copy on this path).", adev, bdev);
         return 0;
@@ -223,7 +201,7 @@ extern "C" int fiasco_amd_planes_distortion_device(const int16_t *a, const int16
     bool ok = hipMalloc((void **) &buf, tab_b + DS_RES_BYTES) == hipSuccess
               && hipMemcpy(buf, tab.data(), tab.size() * sizeof(DsPlane), hipMemcpyHostToDevice) == hipSuccess
               && hipMemsetAsync(buf + tab_b, 0, DS_RES_BYTES, (hipStream_t) stream) == hipSuccess
-              && ds_launch((const DsPlane *) buf, tab, buf + tab_b, oc_cus(), (hipStream_t) stream)
+              && ds_launch((const DsPlane *) buf, tab, buf + tab_b, ft_cus(), (hipStream_t) stream)
               && hipStreamSynchronize((hipStream_t) stream) == hipSuccess
               && hipMemcpy(res.bytes, buf + tab_b, DS_RES_BYTES, hipMemcpyDeviceToHost) == hipSuccess;
     if (!ok) fa_set_error("HIP error: %s", hipGetErrorString(hipGetLastError()));

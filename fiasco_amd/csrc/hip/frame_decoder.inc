@@ -469,7 +469,7 @@ struct DecShare {
     const OcOut *out; const DsOut *ds;          /* the optional consumers */
     bool         images = false;                /* ... beside the host images, not instead of them (the frames of a video: the
                                                  * sequence engine goes on with the image, fa_dec_job's consumer fields) */
-    int          device = 0;                    /* the current one */
+    int          device = 0, ncu = 256;         /* the current one and its CUs, asked once per share */
     hipStream_t  stream = nullptr;
     hipEvent_t   ev0 = nullptr, ev1 = nullptr;  /* around the device work of a flight: decoder_us */
     char        *arena = nullptr; size_t arena_b = 0;       /* one per share, grown when a flight needs more */
@@ -799,7 +799,7 @@ static void dec_flight_measure(DecShare &S, DecFlight &F)
     if (ok && F.dstab.empty()) return;
     if (!ok || hipMemsetAsync(S.arena + F.res_off, 0, DS_RES_BYTES, S.stream) != hipSuccess
         || hipMemcpyAsync(S.arena + F.ds_off, F.dstab.data(), F.dstab.size() * sizeof(DsPlane), hipMemcpyHostToDevice, S.stream) != hipSuccess
-        || !ds_launch((const DsPlane *) (S.arena + F.ds_off), F.dstab, S.arena + F.res_off, oc_cus(), S.stream))
+        || !ds_launch((const DsPlane *) (S.arena + F.ds_off), F.dstab, S.arena + F.res_off, S.ncu, S.stream))
         dec_flight_fail(S, F, "device decoder: HIP error");
 }
 
@@ -827,14 +827,14 @@ static void dec_flight_write(DecShare &S, DecFlight &F)
     bool ok = hipStreamWaitEvent(S.stream, S.out->ready, 0) == hipSuccess;
     if (ok && !F.y4tab.empty())
         ok = hipMemcpyAsync(S.arena + F.oc_off, F.y4tab.data(), F.y4tab.size() * sizeof(Y4Frame), hipMemcpyHostToDevice, S.stream) == hipSuccess
-             && y4_launch((const Y4Frame *) (S.arena + F.oc_off), (unsigned) F.y4tab.size(), total, oc_cus(), S.stream);
+             && y4_launch((const Y4Frame *) (S.arena + F.oc_off), (unsigned) F.y4tab.size(), total, S.ncu, S.stream);
     if (ok && !F.octab.empty())
         ok = hipMemcpyAsync(S.arena + F.oc_off, F.octab.data(), F.octab.size() * sizeof(OcFrame), hipMemcpyHostToDevice, S.stream) == hipSuccess
-             && (S.out->render ? rd_launch((const OcFrame *) (S.arena + F.oc_off), (unsigned) F.octab.size(), total, S.out->render, oc_cus(), S.stream)
-                                : oc_launch((const OcFrame *) (S.arena + F.oc_off), (unsigned) F.octab.size(), total, oc_cus(), S.stream));
+             && (S.out->render ? rd_launch((const OcFrame *) (S.arena + F.oc_off), (unsigned) F.octab.size(), total, S.out->render, S.ncu, S.stream)
+                                : oc_launch((const OcFrame *) (S.arena + F.oc_off), (unsigned) F.octab.size(), total, S.ncu, S.stream));
     if (ok && !F.thoctab.empty())
         ok = hipMemcpyAsync(S.arena + F.thoc_off, F.thoctab.data(), F.thoctab.size() * sizeof(OcFrame), hipMemcpyHostToDevice, S.stream) == hipSuccess
-             && oc_launch((const OcFrame *) (S.arena + F.thoc_off), (unsigned) F.thoctab.size(), thtotal, oc_cus(), S.stream);
+             && oc_launch((const OcFrame *) (S.arena + F.thoc_off), (unsigned) F.thoctab.size(), thtotal, S.ncu, S.stream);
     if (!ok) dec_flight_fail(S, F, "device decoder: HIP error");
 }
 
@@ -935,6 +935,7 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine, con
     DecShare S;
     S.jobs = jobs; S.out = out; S.ds = ds; S.images = images;
     bool usable = hipGetDevice(&S.device) == hipSuccess && hipStreamCreate(&S.stream) == hipSuccess;
+    if (usable) S.ncu = ft_cus();
     if (!usable) (void) hipGetLastError();
     else if (hipEventCreate(&S.ev0) != hipSuccess || hipEventCreate(&S.ev1) != hipSuccess) (void) hipGetLastError();
     std::vector<unsigned> todo;

@@ -11,13 +11,14 @@
  *  right, * 16 last, truncated toward zero to int and narrowed.  Nothing may be contracted into a fused multiply-add:
  *  the file is built with -ffp-contract=off and the function says so again.
  *
- *  Shape: a work item is 16 neighbouring pixels of one row -- one 16-byte load per 8-bit plane (three for interleaved
- *  RGB) where the address allows it, byte loads otherwise (a ragged row end, a source that starts at an odd column),
- *  and 32 bytes of int16 per band, stored as 16-byte vectors (8- or 4-byte ones where a row of the plane does not start
- *  on a 16-byte boundary).  Neighbouring lanes take neighbouring items, so a wave reads 1 KiB and writes 2 KiB per
- *  band contiguously.  The items of all frames form one sequence (IcFrame::first = items before the frame); the grid
- *  is sized from the CU count and every workgroup of 256 takes one contiguous stretch of the sequence, so the frame
- *  of an item is found by one search per workgroup and a step forward now and then.
+ *  Shape: frame_table.inc's -- one table entry per frame (IcFrame), one sequence of work items.  A work item is 16
+ *  neighbouring pixels of one row -- one 16-byte load per 8-bit plane (three for interleaved RGB) where the address allows
+ *  it, byte loads otherwise (a ragged row end, a source that starts at an odd column), and 32 bytes of int16 per band,
+ *  stored as 16-byte vectors (8- or 4-byte ones where a row of the plane does not start on a 16-byte boundary).
+ *  Neighbouring lanes take neighbouring items, so a wave reads 1 KiB and writes 2 KiB per band contiguously.
+ *
+ *  Build (hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage): ic_convert_kernel 132 VGPRs, 56 SGPRs,
+ *  no scratch, no LDS, 3 waves per SIMD; global_ accesses only.
  */
 
 struct IcFrame {
@@ -28,114 +29,65 @@ struct IcFrame {
     unsigned            width, height, layout, cpr;    /* cpr: items per row */
 };
 
-/* sources and planes come out of the descriptor table: the compiler cannot see that they are global memory and would
- * use flat loads and stores */
-#define IC_GLOBAL __attribute__((address_space(1)))
-typedef unsigned ic_u4 __attribute__((ext_vector_type(4)));
-typedef unsigned ic_u2 __attribute__((ext_vector_type(2)));
+PX_DEV unsigned ic_byte(const unsigned *w, unsigned k) { return (w[k >> 2] >> (8 * (k & 3))) & 255u; }
+PX_DEV unsigned ic_pair(int lo, int hi) { return ((unsigned) lo & 0xffffu) | ((unsigned) hi << 16); }
 
-/* 16 bytes from p as four words: one vector load, or `n' byte loads (the rest reads as zero) */
-static __device__ __forceinline__ void ic_load16(const unsigned char *p, unsigned n, unsigned w[4])
+/* work item `local' of frame F */
+PX_DEV void ic_item(const IcFrame &F, unsigned local)
 {
-    if (n == 16 && ((size_t) p & 15) == 0) {
-        const ic_u4 v = *(const IC_GLOBAL ic_u4 *) p;
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-        return;
-    }
-    w[0] = w[1] = w[2] = w[3] = 0;
-#pragma unroll
-    for (unsigned k = 0; k < 16; k++)
-        if (k < n) w[k >> 2] |= (unsigned) ((const IC_GLOBAL unsigned char *) p)[k] << (8 * (k & 3));
-}
-
-/* 16 values (`n' of them valid, n even) as packed pairs to q, which is 4-byte aligned */
-static __device__ __forceinline__ void ic_store16(int16_t *q, unsigned n, const unsigned v[8])
-{
-    if (n == 16 && ((size_t) q & 15) == 0) {
-        ((IC_GLOBAL ic_u4 *) q)[0] = ic_u4{ v[0], v[1], v[2], v[3] };
-        ((IC_GLOBAL ic_u4 *) q)[1] = ic_u4{ v[4], v[5], v[6], v[7] };
-    } else if (n == 16 && ((size_t) q & 7) == 0) {
-#pragma unroll
-        for (unsigned k = 0; k < 4; k++) ((IC_GLOBAL ic_u2 *) q)[k] = ic_u2{ v[2 * k], v[2 * k + 1] };
-    } else {
+#pragma clang fp contract(off)
+    const unsigned row = local / F.cpr, x0 = (local - row * F.cpr) * 16;
+    const unsigned n = F.width - x0 < 16 ? F.width - x0 : 16;
+    const size_t npix = (size_t) F.width * F.height;
+    int16_t *q = F.dst + (size_t) row * F.width + x0;
+    const unsigned char *p = F.src + (size_t) row * F.pitch;
+    unsigned out[8];
+    if (F.layout == FIASCO_AMD_GRAY8) {
+        unsigned w[4];
+        px_load_bytes_vec(p + x0, n, w);
 #pragma unroll
         for (unsigned k = 0; k < 8; k++)
-            if (2 * k < n) ((IC_GLOBAL unsigned *) q)[k] = v[k];
+            out[k] = ic_pair(((int) ic_byte(w, 2 * k) - 128) * 16, ((int) ic_byte(w, 2 * k + 1) - 128) * 16);
+        px_store_values(q, n, out);
+        return;
     }
+    unsigned w[12];
+    if (F.layout == FIASCO_AMD_RGB8_INTERLEAVED) {
+        const unsigned char *s = p + (size_t) x0 * 3;
+        const unsigned nb = n * 3;
+        px_load_bytes_vec(s, nb >= 16 ? 16 : nb, w);
+        px_load_bytes_vec(s + 16, nb >= 32 ? 16 : nb > 16 ? nb - 16 : 0, w + 4);
+        px_load_bytes_vec(s + 32, nb >= 48 ? 16 : nb > 32 ? nb - 32 : 0, w + 8);
+    } else {
+        px_load_bytes_vec(p + x0, n, w);
+        px_load_bytes_vec(p + F.plane_stride + x0, n, w + 4);
+        px_load_bytes_vec(p + 2 * F.plane_stride + x0, n, w + 8);
+    }
+    int y[16], cb[16], cr[16];
+#pragma unroll
+    for (unsigned k = 0; k < 16; k++) {
+        int r, g, bl;
+        if (F.layout == FIASCO_AMD_RGB8_INTERLEAVED) { r = (int) ic_byte(w, 3 * k); g = (int) ic_byte(w, 3 * k + 1); bl = (int) ic_byte(w, 3 * k + 2); }
+        else { r = (int) ic_byte(w, k); g = (int) ic_byte(w + 4, k); bl = (int) ic_byte(w + 8, k); }
+        /* host/fa_image.c:108-110, character for character: double arithmetic, left to right, C truncation */
+        y[k]  = (int) ((+0.2989 * r + 0.5866 * g + 0.1145 * bl - 128) * 16);
+        cb[k] = (int) ((-0.1687 * r - 0.3312 * g + 0.5000 * bl) * 16);
+        cr[k] = (int) ((+0.5000 * r - 0.4183 * g - 0.0816 * bl) * 16);
+    }
+#pragma unroll
+    for (unsigned k = 0; k < 8; k++) out[k] = ic_pair(y[2 * k], y[2 * k + 1]);
+    px_store_values(q, n, out);
+#pragma unroll
+    for (unsigned k = 0; k < 8; k++) out[k] = ic_pair(cb[2 * k], cb[2 * k + 1]);
+    px_store_values(q + npix, n, out);
+#pragma unroll
+    for (unsigned k = 0; k < 8; k++) out[k] = ic_pair(cr[2 * k], cr[2 * k + 1]);
+    px_store_values(q + 2 * npix, n, out);
 }
-
-static __device__ __forceinline__ unsigned ic_byte(const unsigned *w, unsigned k) { return (w[k >> 2] >> (8 * (k & 3))) & 255u; }
-static __device__ __forceinline__ unsigned ic_pair(int lo, int hi) { return ((unsigned) lo & 0xffffu) | ((unsigned) hi << 16); }
 
 __global__ void __launch_bounds__(256) ic_convert_kernel(const IcFrame *__restrict__ frames, unsigned nframes, unsigned long long total)
 {
-#pragma clang fp contract(off)
-    const unsigned long long tiles = (total + 255) / 256;
-    const unsigned long long t0 = tiles * blockIdx.x / gridDim.x, t1 = tiles * (blockIdx.x + 1) / gridDim.x;
-    if (t0 >= t1) return;
-    unsigned f = 0;
-    {   /* the frame of the stretch's first item: the last one that starts at or before it */
-        unsigned lo = 0, hi = nframes;
-        while (hi - lo > 1) {
-            const unsigned mid = (lo + hi) / 2;
-            if (frames[mid].first <= t0 * 256) lo = mid; else hi = mid;
-        }
-        f = lo;
-    }
-    for (unsigned long long t = t0; t < t1; t++) {
-        const unsigned long long it = t * 256 + threadIdx.x;
-        if (it >= total) break;
-        while (f + 1 < nframes && frames[f + 1].first <= it) f++;
-        const IcFrame F = frames[f];
-        const unsigned local = (unsigned) (it - F.first);
-        const unsigned row = local / F.cpr, x0 = (local - row * F.cpr) * 16;
-        const unsigned n = F.width - x0 < 16 ? F.width - x0 : 16;
-        const size_t npix = (size_t) F.width * F.height;
-        int16_t *q = F.dst + (size_t) row * F.width + x0;
-        const unsigned char *p = F.src + (size_t) row * F.pitch;
-        unsigned out[8];
-        if (F.layout == FIASCO_AMD_GRAY8) {
-            unsigned w[4];
-            ic_load16(p + x0, n, w);
-#pragma unroll
-            for (unsigned k = 0; k < 8; k++)
-                out[k] = ic_pair(((int) ic_byte(w, 2 * k) - 128) * 16, ((int) ic_byte(w, 2 * k + 1) - 128) * 16);
-            ic_store16(q, n, out);
-            continue;
-        }
-        unsigned w[12];
-        if (F.layout == FIASCO_AMD_RGB8_INTERLEAVED) {
-            const unsigned char *s = p + (size_t) x0 * 3;
-            const unsigned nb = n * 3;
-            ic_load16(s, nb >= 16 ? 16 : nb, w);
-            ic_load16(s + 16, nb >= 32 ? 16 : nb > 16 ? nb - 16 : 0, w + 4);
-            ic_load16(s + 32, nb >= 48 ? 16 : nb > 32 ? nb - 32 : 0, w + 8);
-        } else {
-            ic_load16(p + x0, n, w);
-            ic_load16(p + F.plane_stride + x0, n, w + 4);
-            ic_load16(p + 2 * F.plane_stride + x0, n, w + 8);
-        }
-        int y[16], cb[16], cr[16];
-#pragma unroll
-        for (unsigned k = 0; k < 16; k++) {
-            int r, g, bl;
-            if (F.layout == FIASCO_AMD_RGB8_INTERLEAVED) { r = (int) ic_byte(w, 3 * k); g = (int) ic_byte(w, 3 * k + 1); bl = (int) ic_byte(w, 3 * k + 2); }
-            else { r = (int) ic_byte(w, k); g = (int) ic_byte(w + 4, k); bl = (int) ic_byte(w + 8, k); }
-            /* host/fa_image.c:108-110, character for character: double arithmetic, left to right, C truncation */
-            y[k]  = (int) ((+0.2989 * r + 0.5866 * g + 0.1145 * bl - 128) * 16);
-            cb[k] = (int) ((-0.1687 * r - 0.3312 * g + 0.5000 * bl) * 16);
-            cr[k] = (int) ((+0.5000 * r - 0.4183 * g - 0.0816 * bl) * 16);
-        }
-#pragma unroll
-        for (unsigned k = 0; k < 8; k++) out[k] = ic_pair(y[2 * k], y[2 * k + 1]);
-        ic_store16(q, n, out);
-#pragma unroll
-        for (unsigned k = 0; k < 8; k++) out[k] = ic_pair(cb[2 * k], cb[2 * k + 1]);
-        ic_store16(q + npix, n, out);
-#pragma unroll
-        for (unsigned k = 0; k < 8; k++) out[k] = ic_pair(cr[2 * k], cr[2 * k + 1]);
-        ic_store16(q + 2 * npix, n, out);
-    }
+    ft_walk<ic_item>(frames, nframes, total);
 }
 
 /* ------------------------------------------------------------------ one share */
@@ -157,20 +109,9 @@ static void ic_describe(IcFrame &d, const fiasco_amd_device_frame &f, const void
     total += (unsigned long long) d.cpr * f.height;
 }
 
-/* eight workgroups of four waves per CU, fewer when the work is less */
-static unsigned ic_grid(unsigned long long total, int ncu)
-{
-    unsigned long long grid = (unsigned long long) (ncu > 0 ? ncu : 256) * 8, tiles = (total + 255) / 256;
-    return (unsigned) (grid > tiles ? tiles : grid);
-}
-
-/* ONE launch for the n frames of the table at d_tab (device memory) on `stream' */
 static bool ic_launch(const IcFrame *d_tab, unsigned n, unsigned long long total, int ncu, hipStream_t stream)
 {
-    const unsigned grid = ic_grid(total, ncu);
-    if (!grid || !n) return true;
-    ic_convert_kernel<<<dim3(grid), dim3(256), 0, stream>>>(d_tab, n, total);
-    return hipGetLastError() == hipSuccess;
+    return ft_launch(ic_convert_kernel, d_tab, n, total, ncu, stream);
 }
 
 /* the device a pointer's memory lies on; -1: unknown */
@@ -308,9 +249,12 @@ static int ic_fetch(fa_image *im)
 
 /* ------------------------------------------------------------------ the entry points (include/libfiasco_amd_hip.h) */
 
-/* `bytes' from p on: device memory, inside the allocation the pointer belongs to (the kernel reads what the descriptor
- * says).  name: "<device frame 3>"; what: "pixels are", "Y plane is"; rows: "rows", "Y rows" */
-static bool ic_check_memory(const char *name, const char *what, const char *rows, const void *p, size_t bytes)
+/* `bytes' from p on: device memory, inside the allocation the pointer belongs to (the kernel reads or writes what the
+ * descriptor says).  name: "<device frame 3>"; what: "pixels are", "Y plane is"; rows: "rows", "Y rows" (one: a singular,
+ * "plane").  An allocation that the runtime cannot tell passes where the memory is only read (unknown == NULL) and is
+ * refused where it is written: unknown names what the message then speaks of, "pixels", "Y plane".  *device: where p lives */
+static bool ic_check_memory(const char *name, const char *what, const char *rows, const void *p, size_t bytes,
+                            const char *unknown = nullptr, int *device = nullptr, bool one = false)
 {
     hipPointerAttribute_t at;
     if (!p || hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice) {
@@ -320,12 +264,18 @@ static bool ic_check_memory(const char *name, const char *what, const char *rows
     }
     hipDeviceptr_t base = nullptr;
     size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) p) != hipSuccess) (void) hipGetLastError();
-    else if ((const char *) p + bytes > (const char *) base + size) {
-        fa_set_error("%s: the %s reach %lu bytes beyond the end of their device allocation.", name, rows,
-                     (unsigned long) ((const char *) p + bytes - ((const char *) base + size)));
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) p) != hipSuccess) {
+        (void) hipGetLastError();
+        if (unknown) {
+            fa_set_error("%s: the device allocation of the %s cannot be determined.", name, unknown);
+            return false;
+        }
+    } else if ((const char *) p + bytes > (const char *) base + size) {
+        fa_set_error("%s: the %s %s %lu bytes beyond the end of %s device allocation.", name, rows, one ? "reaches" : "reach",
+                     (unsigned long) ((const char *) p + bytes - ((const char *) base + size)), one ? "its" : "their");
         return false;
     }
+    if (device) *device = at.device;
     return true;
 }
 
@@ -652,7 +602,7 @@ static fiasco_amd_seq_t *ic_seq_open(unsigned n, const IcInput &in, void *stream
     if (ready)
         for_shares(share, [&](size_t part) {
             const std::vector<unsigned> &ds = mine[share[part]];
-            int here = -1, ncu = 0;
+            int here = -1;
             hipStream_t st = nullptr;
             char *buf = nullptr;
             char *d_tab = nullptr;
@@ -668,7 +618,6 @@ static fiasco_amd_seq_t *ic_seq_open(unsigned n, const IcInput &in, void *stream
                     why[part] = msg;
                     return;
                 }
-            if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, here) != hipSuccess || ncu <= 0) { (void) hipGetLastError(); ncu = 256; }
             if (hipMalloc((void **) &buf, frame_b * ds.size()) != hipSuccess) {
                 char msg[200];
                 snprintf(msg, sizeof msg, "out of HBM: no room for %.1f MiB of frames", frame_b * ds.size() / 1048576.0);
@@ -683,7 +632,7 @@ static fiasco_amd_seq_t *ic_seq_open(unsigned n, const IcInput &in, void *stream
                         && hipMalloc((void **) &d_tab, tab.size()) == hipSuccess
                         && hipStreamWaitEvent(st, ready, 0) == hipSuccess
                         && hipMemcpyAsync(d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, st) == hipSuccess
-                        && K.launch(d_tab, (unsigned) ds.size(), total, ncu, st)
+                        && K.launch(d_tab, (unsigned) ds.size(), total, ft_cus(), st)
                         && hipEventRecord(done[part], st) == hipSuccess
                         && hipStreamSynchronize(st) == hipSuccess;          /* the one host wait of open */
             if (!fine) { why[part] = std::string("HIP error: ") + hipGetErrorString(hipGetLastError()); }

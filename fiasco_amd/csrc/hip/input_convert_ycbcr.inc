@@ -5,38 +5,30 @@
  *  include/libfiasco_amd_ycbcr.h has the definition: every plane (byte - 128) * 16, a 4:2:0 chroma sample replicated over
  *  its 2 x 2 pixels.  Integer arithmetic, nothing is rounded; host/fa_image.c fa_image_from_ycbcr() is the same in C.
  *
- *  Shape: ic_convert_kernel's -- the items of all frames form one sequence (IcyFrame::first), the grid is sized from the
- *  CU count, every workgroup of 256 takes one contiguous stretch of it and finds the frame of its first item by one
- *  search.  Neighbouring lanes take neighbouring items of a row, so a wave reads 1 KiB of Y per load instruction and
- *  writes 2 KiB per band and row contiguously.
+ *  Shape: frame_table.inc's -- one table entry per frame (IcyFrame), one sequence of work items.  Neighbouring lanes take
+ *  neighbouring items of a row, so a wave reads 1 KiB of Y per load instruction and writes 2 KiB per band and row
+ *  contiguously.
  *    4:2:0   an item is 16 neighbouring pixels of a ROW PAIR: two 16-byte Y loads, and one 16-byte load of 8 interleaved
  *            pairs (c_step 2) or two 8-byte loads (c_step 1) -- every chroma byte is read exactly once --, six stores of
  *            32 bytes of int16 (2 rows x 3 bands); a replicated chroma pair is one word, (v & 0xffff) * 0x10001
  *    4:4:4   an item is 16 pixels of one row: three 16-byte loads, three 32-byte stores
  *  Loads are 16-, 8- or 4-byte vectors where the address allows it (a plane whose rows start on 4 or 8 bytes only) and
- *  byte loads otherwise (a ragged row end that is no multiple of 4, a source at an odd address); stores are ic_store16's:
- *  16-, 8- or 4-byte, a row of a plane always begins on 4 bytes (even width).  Global accesses, everything in registers.
+ *  byte loads otherwise (a ragged row end that is no multiple of 4, a source at an odd address: px_load_bytes_wide); stores
+ *  are 16-, 8- or 4-byte, a row of a plane always begins on 4 bytes (even width).  Global accesses, everything in registers.
  *  The kernel moves 1.5 + 6 bytes per pixel (4:2:0; 3 + 6 for 4:4:4).  Measured (tests/gpu_ycbcr_input_probe.py under a
  *  rocprofv3 kernel trace, profiles/ycbcr_input.json; 32 frames of 1080p, median of 22 launches): NV12 133 us, I420 130 us,
  *  4:4:4 151 us, ic_convert_kernel on interleaved RGB 156 us -- 3.7 .. 4.0 TB/s of the bytes each has to move.
  *
  *  Build (hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage): icy_convert_kernel 39 VGPRs, 44 SGPRs,
- *  no scratch, no LDS, 8 waves per SIMD; global_ accesses only, no flat_ one (ic_convert_kernel beside it: 132 VGPRs, 53
- *  SGPRs, no scratch, 3 waves per SIMD -- its code is what it was before this file existed, instruction for instruction).
+ *  no scratch, no LDS, 8 waves per SIMD; global_ accesses only, no flat_ one (ic_convert_kernel beside it: 132 VGPRs, 56
+ *  SGPRs, no scratch, 3 waves per SIMD).
  *
  *  YCBCR_IN_HOST_REPLAY: the per-item function alone as plain C++ (tests/ycbcr_in_step_check.cpp, for the sanitizers).
  */
 #ifdef YCBCR_IN_HOST_REPLAY
-#define ICY_DEV static inline
-#define ICY_GLOBAL
-struct alignas(16) icy_u4 { unsigned x, y, z, w; };
-struct alignas(8) icy_u2 { unsigned x, y; };
-#else
-#define ICY_DEV static __device__ __forceinline__
-#define ICY_GLOBAL IC_GLOBAL
-typedef ic_u4 icy_u4;
-typedef ic_u2 icy_u2;
+#define PX_HOST_REPLAY 1
 #endif
+#include "px_access.inc"
 
 struct IcyFrame {
     const unsigned char *y, *c0, *c1;    /* first bytes: Y; Cb (c_step 2: the plane of pairs, the lower pointer); Cr (c_step 2: unused) */
@@ -48,67 +40,14 @@ struct IcyFrame {
     unsigned            cpr;             /* items per row (4:4:4) or row pair (4:2:0) */
 };
 
-/* `n' bytes (at most 16) from p into w[0 .. 3], the rest reads as zero; reads exactly the n bytes */
-ICY_DEV void icy_load16(const unsigned char *p, unsigned n, unsigned w[4])
-{
-    if (n == 16 && ((size_t) p & 15) == 0) {
-        const icy_u4 v = *(const ICY_GLOBAL icy_u4 *) p;
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    } else if (n == 16 && ((size_t) p & 7) == 0) {
-        const icy_u2 a = ((const ICY_GLOBAL icy_u2 *) p)[0], b = ((const ICY_GLOBAL icy_u2 *) p)[1];
-        w[0] = a.x; w[1] = a.y; w[2] = b.x; w[3] = b.y;
-    } else if (!(n & 3) && ((size_t) p & 3) == 0) {
-#pragma unroll
-        for (unsigned k = 0; k < 4; k++) w[k] = 4 * k < n ? ((const ICY_GLOBAL unsigned *) p)[k] : 0u;
-    } else {
-        w[0] = w[1] = w[2] = w[3] = 0;
-#pragma unroll
-        for (unsigned k = 0; k < 16; k++)
-            if (k < n) w[k >> 2] |= (unsigned) ((const ICY_GLOBAL unsigned char *) p)[k] << (8 * (k & 3));
-    }
-}
-
-/* the same for at most 8 bytes into w[0 .. 1] */
-ICY_DEV void icy_load8(const unsigned char *p, unsigned n, unsigned w[2])
-{
-    if (n == 8 && ((size_t) p & 7) == 0) {
-        const icy_u2 a = *(const ICY_GLOBAL icy_u2 *) p;
-        w[0] = a.x; w[1] = a.y;
-    } else if (!(n & 3) && ((size_t) p & 3) == 0) {
-#pragma unroll
-        for (unsigned k = 0; k < 2; k++) w[k] = 4 * k < n ? ((const ICY_GLOBAL unsigned *) p)[k] : 0u;
-    } else {
-        w[0] = w[1] = 0;
-#pragma unroll
-        for (unsigned k = 0; k < 8; k++)
-            if (k < n) w[k >> 2] |= (unsigned) ((const ICY_GLOBAL unsigned char *) p)[k] << (8 * (k & 3));
-    }
-}
-
-/* 16 values (`n' of them valid, n even) as packed pairs to q, which is 4-byte aligned */
-ICY_DEV void icy_store16(int16_t *q, unsigned n, const unsigned v[8])
-{
-    if (n == 16 && ((size_t) q & 15) == 0) {
-        ((ICY_GLOBAL icy_u4 *) q)[0] = icy_u4{ v[0], v[1], v[2], v[3] };
-        ((ICY_GLOBAL icy_u4 *) q)[1] = icy_u4{ v[4], v[5], v[6], v[7] };
-    } else if (n == 16 && ((size_t) q & 7) == 0) {
-#pragma unroll
-        for (unsigned k = 0; k < 4; k++) ((ICY_GLOBAL icy_u2 *) q)[k] = icy_u2{ v[2 * k], v[2 * k + 1] };
-    } else {
-#pragma unroll
-        for (unsigned k = 0; k < 8; k++)
-            if (2 * k < n) ((ICY_GLOBAL unsigned *) q)[k] = v[k];
-    }
-}
-
 /* byte k of packed bytes as its 12.4 value, (b - 128) * 16, in the low half of a word */
-ICY_DEV unsigned icy_value(const unsigned *w, unsigned k)
+PX_DEV unsigned icy_value(const unsigned *w, unsigned k)
 {
     return (unsigned) (((int) ((w[k >> 2] >> (8 * (k & 3))) & 255u) - 128) * 16) & 0xffffu;
 }
 
 /* 16 bytes, one per pixel, as 16 values in packed pairs */
-ICY_DEV void icy_row(const unsigned w[4], unsigned out[8])
+PX_DEV void icy_row(const unsigned w[4], unsigned out[8])
 {
 #pragma unroll
     for (unsigned k = 0; k < 8; k++) out[k] = icy_value(w, 2 * k) | (icy_value(w, 2 * k + 1) << 16);
@@ -116,7 +55,7 @@ ICY_DEV void icy_row(const unsigned w[4], unsigned out[8])
 
 /* work item `local' of frame F.  All loads of an item are issued before its first store: the compiler cannot know that
  * the planes and the sources do not overlap and keeps a load behind every store that precedes it in the text. */
-ICY_DEV void icy_item(const IcyFrame &F, unsigned local)
+PX_DEV void icy_item(const IcyFrame &F, unsigned local)
 {
     const unsigned row = local / F.cpr, x0 = (local - row * F.cpr) * 16;
     const unsigned n = F.width - x0 < 16 ? F.width - x0 : 16;             /* even: the width is */
@@ -126,31 +65,31 @@ ICY_DEV void icy_item(const IcyFrame &F, unsigned local)
         /* 4:4:4: 16 pixels of row `row' of the three planes */
         unsigned wy[4], wb[4], wr[4];
         int16_t *q = F.dst + (size_t) row * F.width + x0;
-        icy_load16(F.y + (size_t) row * F.y_pitch + x0, n, wy);
-        icy_load16(F.c0 + (size_t) row * F.c_pitch + x0, n, wb);
-        icy_load16(F.c1 + (size_t) row * F.c_pitch + x0, n, wr);
+        px_load_bytes_wide(F.y + (size_t) row * F.y_pitch + x0, n, wy);
+        px_load_bytes_wide(F.c0 + (size_t) row * F.c_pitch + x0, n, wb);
+        px_load_bytes_wide(F.c1 + (size_t) row * F.c_pitch + x0, n, wr);
         icy_row(wy, out);
-        icy_store16(q, n, out);
+        px_store_values(q, n, out);
         icy_row(wb, out);
-        icy_store16(q + npix, n, out);
+        px_store_values(q + npix, n, out);
         icy_row(wr, out);
-        icy_store16(q + 2 * npix, n, out);
+        px_store_values(q + 2 * npix, n, out);
         return;
     }
     /* 4:2:0: 16 pixels of the rows 2 row and 2 row + 1, n / 2 samples of chroma row `row' */
     unsigned w0[4], w1[4], wc[4] = { 0, 0, 0, 0 }, u[2] = { 0, 0 }, v[2] = { 0, 0 };
     int16_t *q = F.dst + (size_t) (2 * row) * F.width + x0;
-    icy_load16(F.y + (size_t) (2 * row) * F.y_pitch + x0, n, w0);
-    icy_load16(F.y + (size_t) (2 * row + 1) * F.y_pitch + x0, n, w1);
-    if (F.c_step == 2) icy_load16(F.c0 + (size_t) row * F.c_pitch + x0, n, wc);          /* pair k at byte 2 (x0 / 2 + k) */
+    px_load_bytes_wide(F.y + (size_t) (2 * row) * F.y_pitch + x0, n, w0);
+    px_load_bytes_wide(F.y + (size_t) (2 * row + 1) * F.y_pitch + x0, n, w1);
+    if (F.c_step == 2) px_load_bytes_wide(F.c0 + (size_t) row * F.c_pitch + x0, n, wc);          /* pair k at byte 2 (x0 / 2 + k) */
     else {
-        icy_load8(F.c0 + (size_t) row * F.c_pitch + (x0 >> 1), n >> 1, u);
-        icy_load8(F.c1 + (size_t) row * F.c_pitch + (x0 >> 1), n >> 1, v);
+        px_load_bytes8(F.c0 + (size_t) row * F.c_pitch + (x0 >> 1), n >> 1, u);
+        px_load_bytes8(F.c1 + (size_t) row * F.c_pitch + (x0 >> 1), n >> 1, v);
     }
     icy_row(w0, out);
-    icy_store16(q, n, out);
+    px_store_values(q, n, out);
     icy_row(w1, out);
-    icy_store16(q + F.width, n, out);
+    px_store_values(q + F.width, n, out);
     unsigned cb[8], cr[8];               /* a sample, replicated over its two pixels of a row: one word each */
     if (F.c_step == 2) {
 #pragma unroll
@@ -162,35 +101,17 @@ ICY_DEV void icy_item(const IcyFrame &F, unsigned local)
 #pragma unroll
         for (unsigned k = 0; k < 8; k++) { cb[k] = icy_value(u, k) * 0x10001u; cr[k] = icy_value(v, k) * 0x10001u; }
     }
-    icy_store16(q + npix, n, cb);
-    icy_store16(q + npix + F.width, n, cb);
-    icy_store16(q + 2 * npix, n, cr);
-    icy_store16(q + 2 * npix + F.width, n, cr);
+    px_store_values(q + npix, n, cb);
+    px_store_values(q + npix + F.width, n, cb);
+    px_store_values(q + 2 * npix, n, cr);
+    px_store_values(q + 2 * npix + F.width, n, cr);
 }
 
 #ifndef YCBCR_IN_HOST_REPLAY
 
 __global__ void __launch_bounds__(256) icy_convert_kernel(const IcyFrame *__restrict__ frames, unsigned nframes, unsigned long long total)
 {
-    const unsigned long long tiles = (total + 255) / 256;
-    const unsigned long long t0 = tiles * blockIdx.x / gridDim.x, t1 = tiles * (blockIdx.x + 1) / gridDim.x;
-    if (t0 >= t1) return;
-    unsigned f = 0;
-    {   /* the frame of the stretch's first item: the last one that starts at or before it */
-        unsigned lo = 0, hi = nframes;
-        while (hi - lo > 1) {
-            const unsigned mid = (lo + hi) / 2;
-            if (frames[mid].first <= t0 * 256) lo = mid; else hi = mid;
-        }
-        f = lo;
-    }
-    for (unsigned long long t = t0; t < t1; t++) {
-        const unsigned long long it = t * 256 + threadIdx.x;
-        if (it >= total) break;
-        while (f + 1 < nframes && frames[f + 1].first <= it) f++;
-        const IcyFrame F = frames[f];
-        icy_item(F, (unsigned) (it - F.first));
-    }
+    ft_walk<icy_item>(frames, nframes, total);
 }
 
 /* ------------------------------------------------------------------ the kind (core_hip.cpp IcKind) */
@@ -218,10 +139,7 @@ static void icy_describe(IcyFrame &d, const fiasco_amd_ycbcr_frame &f, int16_t *
 
 static bool icy_launch(const IcyFrame *d_tab, unsigned n, unsigned long long total, int ncu, hipStream_t stream)
 {
-    const unsigned grid = ic_grid(total, ncu);
-    if (!grid || !n) return true;
-    icy_convert_kernel<<<dim3(grid), dim3(256), 0, stream>>>(d_tab, n, total);
-    return hipGetLastError() == hipSuccess;
+    return ft_launch(icy_convert_kernel, d_tab, n, total, ncu, stream);
 }
 
 static_assert(sizeof(IcyFrame) <= IC_ENTRY_MAX, "IC_ENTRY_MAX (core_hip.cpp) is the room of a table entry");

@@ -22,11 +22,13 @@
  *  beyond -128 .. 127.  Wherever its indices stay inside them the two agree; outside the reference reads past its
  *  arrays, and this code clamps.
  *
- *  Shape: a work item is 16 neighbouring pixels of one row -- two 16-byte loads per band where the row of the plane
- *  allows it (a row of odd width / 8 does not start on 16 bytes: 8-, 4- or 2-byte loads then), one 16-byte store for
- *  gray and per plane, three for interleaved RGB, byte stores at a ragged row end or an unaligned target.  The items
- *  of all frames form one sequence (OcFrame::first); the grid is sized from the CU count and every workgroup of 256
- *  walks one contiguous stretch of it, so the frame of an item costs one search per workgroup.
+ *  Shape: frame_table.inc's -- one table entry per frame (OcFrame), one sequence of work items.  A work item is 16
+ *  neighbouring pixels of one row -- two 16-byte loads per band where the row of the plane allows it (a row of odd
+ *  width / 8 does not start on 16 bytes: 8-, 4- or 2-byte loads then), one 16-byte store for gray and per plane, three
+ *  for interleaved RGB, byte stores at a ragged row end or an unaligned target.
+ *
+ *  Build (hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage): oc_convert_kernel 65 VGPRs, 51 SGPRs,
+ *  no scratch, no LDS, 7 waves per SIMD; global_ accesses only.
  */
 
 struct OcFrame {
@@ -37,109 +39,62 @@ struct OcFrame {
     unsigned            width, height, layout, cpr;    /* cpr: items per row */
 };
 
-typedef unsigned short oc_h;
+/* byte k of 16 in four words that begin as zero */
+PX_DEV void oc_put(unsigned *w, unsigned k, unsigned byte) { w[k >> 2] |= byte << (8 * (k & 3)); }
 
-/* 16 values from p (`n' of them valid, the rest read as zero) as packed pairs */
-static __device__ __forceinline__ void oc_load16(const int16_t *p, unsigned n, unsigned v[8])
+/* work item `local' of frame F */
+PX_DEV void oc_item(const OcFrame &F, unsigned local)
 {
-    if (n == 16 && ((size_t) p & 15) == 0) {
-        const ic_u4 a = ((const IC_GLOBAL ic_u4 *) p)[0], b = ((const IC_GLOBAL ic_u4 *) p)[1];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    } else if (n == 16 && ((size_t) p & 7) == 0) {
+#pragma clang fp contract(off)
+    const unsigned row = local / F.cpr, x0 = (local - row * F.cpr) * 16;
+    const unsigned n = F.width - x0 < 16 ? F.width - x0 : 16;
+    const size_t npix = (size_t) F.width * F.height;
+    const int16_t *p = F.src + (size_t) row * F.width + x0;
+    unsigned char *q = F.dst + (size_t) row * F.pitch;
+    unsigned y[8];
+    px_load_values(p, n, y);
+    if (F.layout == FIASCO_AMD_GRAY8) {
+        unsigned w[4] = { 0, 0, 0, 0 };
 #pragma unroll
-        for (unsigned k = 0; k < 4; k++) { const ic_u2 a = ((const IC_GLOBAL ic_u2 *) p)[k]; v[2 * k] = a.x; v[2 * k + 1] = a.y; }
-    } else if (!(n & 1) && ((size_t) p & 3) == 0) {
+        for (unsigned k = 0; k < 16; k++) oc_put(w, k, px_clip255(px_int(y, k) + 128));
+        px_store_bytes_vec(q + x0, n, w);
+        return;
+    }
+    unsigned cbv[8], crv[8];
+    px_load_values(p + npix, n, cbv);
+    px_load_values(p + 2 * npix, n, crv);
+    unsigned w[12] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 #pragma unroll
-        for (unsigned k = 0; k < 8; k++) v[k] = 2 * k < n ? ((const IC_GLOBAL unsigned *) p)[k] : 0u;
+    for (unsigned k = 0; k < 16; k++) {
+        const int yval = px_int(y, k) + 128;
+        int cb = px_int(cbv, k), cr = px_int(crv, k);
+        cb = cb < -128 ? -128 : cb > 127 ? 127 : cb;
+        cr = cr < -128 ? -128 : cr > 127 ? 127 : cr;
+        /* lib/image.c:508-511, character for character: double arithmetic, C truncation */
+        const int rr = (int) ( 1.4022 * cr + 0.5);
+        const int rg = (int) (-0.7145 * cr + 0.5);
+        const int bg = (int) (-0.3456 * cb + 0.5);
+        const int bb = (int) ( 1.7710 * cb + 0.5);
+        const unsigned r = px_clip255(yval + rr), g = px_clip255(yval + rg + bg), bl = px_clip255(yval + bb);
+        if (F.layout == FIASCO_AMD_RGB8_INTERLEAVED) { oc_put(w, 3 * k, r); oc_put(w, 3 * k + 1, g); oc_put(w, 3 * k + 2, bl); }
+        else { oc_put(w, k, r); oc_put(w + 4, k, g); oc_put(w + 8, k, bl); }
+    }
+    if (F.layout == FIASCO_AMD_RGB8_INTERLEAVED) {
+        unsigned char *d = q + (size_t) x0 * 3;
+        const unsigned nb = n * 3;
+        px_store_bytes_vec(d, nb >= 16 ? 16 : nb, w);
+        px_store_bytes_vec(d + 16, nb >= 32 ? 16 : nb > 16 ? nb - 16 : 0, w + 4);
+        px_store_bytes_vec(d + 32, nb >= 48 ? 16 : nb > 32 ? nb - 32 : 0, w + 8);
     } else {
-#pragma unroll
-        for (unsigned k = 0; k < 8; k++) {
-            const unsigned lo = 2 * k < n ? ((const IC_GLOBAL oc_h *) p)[2 * k] : 0u, hi = 2 * k + 1 < n ? ((const IC_GLOBAL oc_h *) p)[2 * k + 1] : 0u;
-            v[k] = lo | (hi << 16);
-        }
+        px_store_bytes_vec(q + x0, n, w);
+        px_store_bytes_vec(q + F.plane_stride + x0, n, w + 4);
+        px_store_bytes_vec(q + 2 * F.plane_stride + x0, n, w + 8);
     }
 }
-
-/* 16 bytes per word group: `nb' bytes of w to q, one vector store or byte stores */
-static __device__ __forceinline__ void oc_store16(unsigned char *q, unsigned nb, const unsigned w[4])
-{
-    if (nb == 16 && ((size_t) q & 15) == 0) { *(IC_GLOBAL ic_u4 *) q = ic_u4{ w[0], w[1], w[2], w[3] }; return; }
-#pragma unroll
-    for (unsigned k = 0; k < 16; k++)
-        if (k < nb) ((IC_GLOBAL unsigned char *) q)[k] = (unsigned char) (w[k >> 2] >> (8 * (k & 3)));
-}
-
-/* value k of 16 packed ones, arithmetically shifted: the integer part of a 12.4 pixel */
-static __device__ __forceinline__ int oc_int(const unsigned *v, unsigned k) { return (int) (int16_t) (v[k >> 1] >> (16 * (k & 1))) >> 4; }
-static __device__ __forceinline__ unsigned oc_clip255(int v) { return (unsigned) (v < 0 ? 0 : v > 255 ? 255 : v); }
-static __device__ __forceinline__ void oc_put(unsigned *w, unsigned k, unsigned byte) { w[k >> 2] |= byte << (8 * (k & 3)); }
 
 __global__ void __launch_bounds__(256) oc_convert_kernel(const OcFrame *__restrict__ frames, unsigned nframes, unsigned long long total)
 {
-#pragma clang fp contract(off)
-    const unsigned long long tiles = (total + 255) / 256;
-    const unsigned long long t0 = tiles * blockIdx.x / gridDim.x, t1 = tiles * (blockIdx.x + 1) / gridDim.x;
-    if (t0 >= t1) return;
-    unsigned f = 0;
-    {   /* the frame of the stretch's first item: the last one that starts at or before it */
-        unsigned lo = 0, hi = nframes;
-        while (hi - lo > 1) {
-            const unsigned mid = (lo + hi) / 2;
-            if (frames[mid].first <= t0 * 256) lo = mid; else hi = mid;
-        }
-        f = lo;
-    }
-    for (unsigned long long t = t0; t < t1; t++) {
-        const unsigned long long it = t * 256 + threadIdx.x;
-        if (it >= total) break;
-        while (f + 1 < nframes && frames[f + 1].first <= it) f++;
-        const OcFrame F = frames[f];
-        const unsigned local = (unsigned) (it - F.first);
-        const unsigned row = local / F.cpr, x0 = (local - row * F.cpr) * 16;
-        const unsigned n = F.width - x0 < 16 ? F.width - x0 : 16;
-        const size_t npix = (size_t) F.width * F.height;
-        const int16_t *p = F.src + (size_t) row * F.width + x0;
-        unsigned char *q = F.dst + (size_t) row * F.pitch;
-        unsigned y[8];
-        oc_load16(p, n, y);
-        if (F.layout == FIASCO_AMD_GRAY8) {
-            unsigned w[4] = { 0, 0, 0, 0 };
-#pragma unroll
-            for (unsigned k = 0; k < 16; k++) oc_put(w, k, oc_clip255(oc_int(y, k) + 128));
-            oc_store16(q + x0, n, w);
-            continue;
-        }
-        unsigned cbv[8], crv[8];
-        oc_load16(p + npix, n, cbv);
-        oc_load16(p + 2 * npix, n, crv);
-        unsigned w[12] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-#pragma unroll
-        for (unsigned k = 0; k < 16; k++) {
-            const int yval = oc_int(y, k) + 128;
-            int cb = oc_int(cbv, k), cr = oc_int(crv, k);
-            cb = cb < -128 ? -128 : cb > 127 ? 127 : cb;
-            cr = cr < -128 ? -128 : cr > 127 ? 127 : cr;
-            /* lib/image.c:508-511, character for character: double arithmetic, C truncation */
-            const int rr = (int) ( 1.4022 * cr + 0.5);
-            const int rg = (int) (-0.7145 * cr + 0.5);
-            const int bg = (int) (-0.3456 * cb + 0.5);
-            const int bb = (int) ( 1.7710 * cb + 0.5);
-            const unsigned r = oc_clip255(yval + rr), g = oc_clip255(yval + rg + bg), bl = oc_clip255(yval + bb);
-            if (F.layout == FIASCO_AMD_RGB8_INTERLEAVED) { oc_put(w, 3 * k, r); oc_put(w, 3 * k + 1, g); oc_put(w, 3 * k + 2, bl); }
-            else { oc_put(w, k, r); oc_put(w + 4, k, g); oc_put(w + 8, k, bl); }
-        }
-        if (F.layout == FIASCO_AMD_RGB8_INTERLEAVED) {
-            unsigned char *d = q + (size_t) x0 * 3;
-            const unsigned nb = n * 3;
-            oc_store16(d, nb >= 16 ? 16 : nb, w);
-            oc_store16(d + 16, nb >= 32 ? 16 : nb > 16 ? nb - 16 : 0, w + 4);
-            oc_store16(d + 32, nb >= 48 ? 16 : nb > 32 ? nb - 32 : 0, w + 8);
-        } else {
-            oc_store16(q + x0, n, w);
-            oc_store16(q + F.plane_stride + x0, n, w + 4);
-            oc_store16(q + 2 * F.plane_stride + x0, n, w + 8);
-        }
-    }
+    ft_walk<oc_item>(frames, nframes, total);
 }
 
 /* ------------------------------------------------------------------ launching */
@@ -171,25 +126,9 @@ static void oc_describe(OcFrame &d, const int16_t *planes, const fiasco_amd_devi
     total += (unsigned long long) d.cpr * t.height;
 }
 
-/* one launch for the `n' frames of the table at d_tab (device memory): eight workgroups of four waves per CU, fewer
- * when the work is less */
 static bool oc_launch(const OcFrame *d_tab, unsigned n, unsigned long long total, int ncu, hipStream_t stream)
 {
-    unsigned long long grid = (unsigned long long) (ncu > 0 ? ncu : 256) * 8, tiles = (total + 255) / 256;
-    if (grid > tiles) grid = tiles;
-    if (!grid) return true;
-    oc_convert_kernel<<<dim3((unsigned) grid), dim3(256), 0, stream>>>(d_tab, n, total);
-    return hipGetLastError() == hipSuccess;
-}
-
-static int oc_cus(void)
-{
-    int dev = 0, ncu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) {
-        (void) hipGetLastError();
-        ncu = 256;
-    }
-    return ncu;
+    return ft_launch(oc_convert_kernel, d_tab, n, total, ncu, stream);
 }
 
 /* ------------------------------------------------------------------ the entry points (include/libfiasco_amd_hip.h) */
@@ -214,16 +153,9 @@ static bool oc_check_target(unsigned i, const fiasco_amd_device_target *in, unsi
         return false;
     }
     /* these rows are WRITTEN: a target whose allocation cannot be told (ic_check_frame lets that pass) is refused */
-    hipPointerAttribute_t at;
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipPointerGetAttributes(&at, in->data) != hipSuccess || hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) in->data) != hipSuccess) {
-        (void) hipGetLastError();
-        fa_set_error("<device target %u>: the device allocation of the pixels cannot be determined.", i);
-        return false;
-    }
-    *device = at.device;
-    return true;
+    char name[32];
+    snprintf(name, sizeof name, "<device target %u>", i);
+    return ic_check_memory(name, "pixels are", "rows", in->data, ic_extent(*out), "pixels", device);
 }
 
 /* What the two batch entry points (this one and fiasco_amd_batch_decode_distortion_device, distortion.inc) have in
@@ -336,44 +268,19 @@ extern "C" int fiasco_amd_planes_to_pixels_device(const int16_t *planes, int col
     if (!planes || !target || !target->data) { fa_set_error("fiasco_amd_planes_to_pixels_device: no planes or no target"); return 0; }
     if (!ic_have_device()) return 0;
     fiasco_amd_device_frame t;
-    int tdev = -1, cur = -1;
+    int tdev = -1, pdev = -1;
     if (!oc_check_target(0, target, target->width, target->height, color, &t, &tdev)) return 0;
     const size_t bytes = (size_t) t.width * t.height * (color ? 3 : 1) * 2;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, planes) != hipSuccess || at.type != hipMemoryTypeDevice) {
-        (void) hipGetLastError();
-        fa_set_error("fiasco_amd_planes_to_pixels_device: the planes are not in device memory.");
+    if (!ic_check_memory("fiasco_amd_planes_to_pixels_device", "planes are", "planes", planes, bytes, nullptr, &pdev)) return 0;
+    if (pdev != tdev) {
+        fa_set_error("<device target 0>: the target lives on device %d, the planes on device %d (no peer copy on this path).", tdev, pdev);
         return 0;
     }
-    {
-        hipDeviceptr_t base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) planes) != hipSuccess) (void) hipGetLastError();
-        else if ((const char *) planes + bytes > (const char *) base + size) {
-            fa_set_error("fiasco_amd_planes_to_pixels_device: the planes reach %lu bytes beyond the end of their device allocation.",
-                         (unsigned long) ((const char *) planes + bytes - ((const char *) base + size)));
-            return 0;
-        }
-    }
-    if (at.device != tdev) {
-        fa_set_error("<device target 0>: the target lives on device %d, the planes on device %d (no peer copy on this path).", tdev, at.device);
-        return 0;
-    }
-    if (hipGetDevice(&cur) != hipSuccess) { (void) hipGetLastError(); cur = -1; }
-    if (cur != tdev && hipSetDevice(tdev) != hipSuccess) { fa_set_error("HIP error: %s", hipGetErrorString(hipGetLastError())); return 0; }
-    /* on the caller's stream itself: behind what it holds, before what follows.  The table of one frame is copied
-     * with a blocking call and freed once the kernel has read it: this call waits on the host. */
-    OcFrame h, *d_tab = nullptr;
+    OcFrame h;
     unsigned long long total = 0;
     oc_describe(h, planes, t, total);
-    bool ok = hipMalloc((void **) &d_tab, sizeof h) == hipSuccess
-              && hipMemcpy(d_tab, &h, sizeof h, hipMemcpyHostToDevice) == hipSuccess
-              && oc_launch(d_tab, 1, total, oc_cus(), (hipStream_t) stream)
-              && hipStreamSynchronize((hipStream_t) stream) == hipSuccess;
-    if (!ok) fa_set_error("HIP error: %s", hipGetErrorString(hipGetLastError()));
-    if (d_tab) (void) hipFree(d_tab);
-    if (cur >= 0 && cur != tdev) (void) hipSetDevice(cur);
-    return ok ? 1 : 0;
+    return ft_run_alone(&h, sizeof h, [&](const void *d_tab, int ncu) { return oc_launch((const OcFrame *) d_tab, 1, total, ncu, (hipStream_t) stream); },
+                        tdev, (hipStream_t) stream);
 }
 
 /* ------------------------------------------------------------------ the outputs of a video

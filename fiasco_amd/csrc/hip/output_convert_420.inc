@@ -8,8 +8,8 @@
  *  clip255((p >> 4) + 128) for every plane, inside buffers the caller owns: a Y plane, and either two chroma planes
  *  (c_step 1) or one plane of interleaved pairs (c_step 2, either order).
  *
- *  Shape: oc_convert_kernel's -- the items of all frames form one sequence (Y4Frame::first), the grid is sized from the CU
- *  count and every workgroup of 256 walks one contiguous stretch of it.  A frame's items are of two kinds:
+ *  Shape: frame_table.inc's -- one table entry per frame (Y4Frame), one sequence of work items.  A frame's items are of two
+ *  kinds:
  *    Y        16 neighbouring pixels of one Y row: two 16-byte loads where the row allows it, one 16-byte store
  *    chroma   a row segment of its own kind, behind the frame's Y items: c_step 1: 16 samples of one row of one chroma
  *             plane, loaded and stored as a Y item's; c_step 2: 16 samples of one row of BOTH planes -- four 16-byte
@@ -20,16 +20,9 @@
  *  Y420_HOST_REPLAY: the per-item function alone as plain C++ (tests/yuv420_step_check.cpp, for the sanitizers).
  */
 #ifdef Y420_HOST_REPLAY
-#define Y4_DEV static inline
-#define Y4_GLOBAL
-struct alignas(16) y4_u4 { unsigned x, y, z, w; };
-struct alignas(8) y4_u2 { unsigned x, y; };
-#else
-#define Y4_DEV static __device__ __forceinline__
-#define Y4_GLOBAL IC_GLOBAL
-typedef ic_u4 y4_u4;
-typedef ic_u2 y4_u2;
+#define PX_HOST_REPLAY 1
 #endif
+#include "px_access.inc"
 
 struct Y4Frame {
     const int16_t      *sy, *s0, *s1;    /* the planes: Y; the chroma plane of d0 (c_step 2: of the even bytes); the other one */
@@ -40,47 +33,15 @@ struct Y4Frame {
     unsigned            cpr, ccpr, ny;   /* items per Y row and per chroma row; Y items: the chroma items follow them */
 };
 
-typedef unsigned short y4_h;
-
-/* 16 values from p (`n' of them valid, the rest read as zero) as packed pairs; reads exactly the n values */
-Y4_DEV void y4_load16(const int16_t *p, unsigned n, unsigned v[8])
-{
-    if (n == 16 && ((size_t) p & 15) == 0) {
-        const y4_u4 a = ((const Y4_GLOBAL y4_u4 *) p)[0], b = ((const Y4_GLOBAL y4_u4 *) p)[1];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    } else if (n == 16 && ((size_t) p & 7) == 0) {
-#pragma unroll
-        for (unsigned k = 0; k < 4; k++) { const y4_u2 a = ((const Y4_GLOBAL y4_u2 *) p)[k]; v[2 * k] = a.x; v[2 * k + 1] = a.y; }
-    } else if (!(n & 1) && ((size_t) p & 3) == 0) {
-#pragma unroll
-        for (unsigned k = 0; k < 8; k++) v[k] = 2 * k < n ? ((const Y4_GLOBAL unsigned *) p)[k] : 0u;
-    } else {
-#pragma unroll
-        for (unsigned k = 0; k < 8; k++) {
-            const unsigned lo = 2 * k < n ? ((const Y4_GLOBAL y4_h *) p)[2 * k] : 0u, hi = 2 * k + 1 < n ? ((const Y4_GLOBAL y4_h *) p)[2 * k + 1] : 0u;
-            v[k] = lo | (hi << 16);
-        }
-    }
-}
-
-/* `nb' bytes (at most 16) of w to q: one vector store, or byte stores */
-Y4_DEV void y4_store16(unsigned char *q, unsigned nb, const unsigned w[4])
-{
-    if (nb == 16 && ((size_t) q & 15) == 0) { *(Y4_GLOBAL y4_u4 *) q = y4_u4{ w[0], w[1], w[2], w[3] }; return; }
-#pragma unroll
-    for (unsigned k = 0; k < 16; k++)
-        if (k < nb) ((Y4_GLOBAL unsigned char *) q)[k] = (unsigned char) (w[k >> 2] >> (8 * (k & 3)));
-}
-
 /* value k of 16 packed ones as its byte: clip255((p >> 4) + 128), arithmetic shift */
-Y4_DEV unsigned y4_byte(const unsigned *v, unsigned k)
+PX_DEV unsigned y4_byte(const unsigned *v, unsigned k)
 {
     const int b = ((int) (int16_t) (v[k >> 1] >> (16 * (k & 1))) >> 4) + 128;
     return (unsigned) (b < 0 ? 0 : b > 255 ? 255 : b);
 }
 
 /* 16 packed values as 16 bytes in four words */
-Y4_DEV void y4_bytes(const unsigned v[8], unsigned w[4])
+PX_DEV void y4_bytes(const unsigned v[8], unsigned w[4])
 {
     w[0] = w[1] = w[2] = w[3] = 0;
 #pragma unroll
@@ -88,15 +49,15 @@ Y4_DEV void y4_bytes(const unsigned v[8], unsigned w[4])
 }
 
 /* work item `local' of frame F (Y4Frame::ny Y items, then the chroma items) */
-Y4_DEV void y4_item(const Y4Frame &F, unsigned local)
+PX_DEV void y4_item(const Y4Frame &F, unsigned local)
 {
     unsigned v[8], w[4];
     if (local < F.ny) {
         const unsigned row = local / F.cpr, x0 = (local - row * F.cpr) * 16;
         const unsigned n = F.width - x0 < 16 ? F.width - x0 : 16;
-        y4_load16(F.sy + (size_t) row * F.width + x0, n, v);
+        px_load_values(F.sy + (size_t) row * F.width + x0, n, v);
         y4_bytes(v, w);
-        y4_store16(F.dy + (size_t) row * F.y_pitch + x0, n, w);
+        px_store_bytes_vec(F.dy + (size_t) row * F.y_pitch + x0, n, w);
         return;
     }
     const unsigned cw = F.width >> 1, ch = F.height >> 1;
@@ -106,47 +67,29 @@ Y4_DEV void y4_item(const Y4Frame &F, unsigned local)
         if (second) c -= per;
         const unsigned row = c / F.ccpr, x0 = (c - row * F.ccpr) * 16;
         const unsigned n = cw - x0 < 16 ? cw - x0 : 16;
-        y4_load16((second ? F.s1 : F.s0) + (size_t) row * cw + x0, n, v);
+        px_load_values((second ? F.s1 : F.s0) + (size_t) row * cw + x0, n, v);
         y4_bytes(v, w);
-        y4_store16((second ? F.d1 : F.d0) + (size_t) row * F.c_pitch + x0, n, w);
+        px_store_bytes_vec((second ? F.d1 : F.d0) + (size_t) row * F.c_pitch + x0, n, w);
         return;
     }
     const unsigned row = c / F.ccpr, x0 = (c - row * F.ccpr) * 16;
     const unsigned n = cw - x0 < 16 ? cw - x0 : 16;
     unsigned u[8], p[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    y4_load16(F.s0 + (size_t) row * cw + x0, n, v);
-    y4_load16(F.s1 + (size_t) row * cw + x0, n, u);
+    px_load_values(F.s0 + (size_t) row * cw + x0, n, v);
+    px_load_values(F.s1 + (size_t) row * cw + x0, n, u);
 #pragma unroll
     for (unsigned k = 0; k < 16; k++) p[k >> 1] |= (y4_byte(v, k) | (y4_byte(u, k) << 8)) << (16 * (k & 1));
     unsigned char *q = F.d0 + (size_t) row * F.c_pitch + (size_t) x0 * 2;
     const unsigned nb = 2 * n;
-    y4_store16(q, nb >= 16 ? 16 : nb, p);
-    y4_store16(q + 16, nb > 16 ? nb - 16 : 0, p + 4);
+    px_store_bytes_vec(q, nb >= 16 ? 16 : nb, p);
+    px_store_bytes_vec(q + 16, nb > 16 ? nb - 16 : 0, p + 4);
 }
 
 #ifndef Y420_HOST_REPLAY
 
 __global__ void __launch_bounds__(256) oc420_convert_kernel(const Y4Frame *__restrict__ frames, unsigned nframes, unsigned long long total)
 {
-    const unsigned long long tiles = (total + 255) / 256;
-    const unsigned long long t0 = tiles * blockIdx.x / gridDim.x, t1 = tiles * (blockIdx.x + 1) / gridDim.x;
-    if (t0 >= t1) return;
-    unsigned f = 0;
-    {   /* the frame of the stretch's first item: the last one that starts at or before it */
-        unsigned lo = 0, hi = nframes;
-        while (hi - lo > 1) {
-            const unsigned mid = (lo + hi) / 2;
-            if (frames[mid].first <= t0 * 256) lo = mid; else hi = mid;
-        }
-        f = lo;
-    }
-    for (unsigned long long t = t0; t < t1; t++) {
-        const unsigned long long it = t * 256 + threadIdx.x;
-        if (it >= total) break;
-        while (f + 1 < nframes && frames[f + 1].first <= it) f++;
-        const Y4Frame F = frames[f];
-        y4_item(F, (unsigned) (it - F.first));
-    }
+    ft_walk<y4_item>(frames, nframes, total);
 }
 
 /* ------------------------------------------------------------------ launching */
@@ -174,11 +117,7 @@ static void y4_describe_packed(Y4Frame &d, const int16_t *planes, const fiasco_a
 
 static bool y4_launch(const Y4Frame *d_tab, unsigned n, unsigned long long total, int ncu, hipStream_t stream)
 {
-    unsigned long long grid = (unsigned long long) (ncu > 0 ? ncu : 256) * 8, tiles = (total + 255) / 256;
-    if (grid > tiles) grid = tiles;
-    if (!grid) return true;
-    oc420_convert_kernel<<<dim3((unsigned) grid), dim3(256), 0, stream>>>(d_tab, n, total);
-    return hipGetLastError() == hipSuccess;
+    return ft_launch(oc420_convert_kernel, d_tab, n, total, ncu, stream);
 }
 
 /* ------------------------------------------------------------------ the entry points (include/libfiasco_amd_420.h) */
@@ -243,31 +182,21 @@ static bool y4_check_memory(unsigned i, const fiasco_amd_device_target_420 &t, i
     const void *first[3] = { t.y, t.c_step == 2 ? (cb < cr ? t.cb : t.cr) : t.cb, t.cr };
     const size_t ext[3] = { (size_t) (t.height - 1) * t.y_pitch + t.width, (ch - 1) * t.c_pitch + cw * t.c_step, (ch - 1) * t.c_pitch + cw };
     const char *name[3] = { "Y", t.c_step == 2 ? "chroma" : "Cb", "Cr" };
+    char who[32];
+    snprintf(who, sizeof who, "<4:2:0 target %u>", i);
     *device = -1;
     for (unsigned k = 0; k < (t.c_step == 2 ? 2u : 3u); k++) {
-        hipPointerAttribute_t at;
-        hipDeviceptr_t base = nullptr;
-        size_t size = 0;
-        if (hipPointerGetAttributes(&at, first[k]) != hipSuccess || at.type != hipMemoryTypeDevice) {
-            (void) hipGetLastError();
-            fa_set_error("<4:2:0 target %u>: the %s plane is not in device memory.", i, name[k]);
+        char is[24], rows[24], plane[24];
+        int dev = -1;
+        snprintf(is, sizeof is, "%s plane is", name[k]);
+        snprintf(rows, sizeof rows, "%s rows", name[k]);
+        snprintf(plane, sizeof plane, "%s plane", name[k]);
+        if (!ic_check_memory(who, is, rows, first[k], ext[k], plane, &dev)) return false;
+        if (*device >= 0 && dev != *device) {
+            fa_set_error("<4:2:0 target %u>: its planes live on devices %d and %d.", i, *device, dev);
             return false;
         }
-        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) first[k]) != hipSuccess) {
-            (void) hipGetLastError();
-            fa_set_error("<4:2:0 target %u>: the device allocation of the %s plane cannot be determined.", i, name[k]);
-            return false;
-        }
-        if ((const char *) first[k] + ext[k] > (const char *) base + size) {
-            fa_set_error("<4:2:0 target %u>: the %s rows reach %lu bytes beyond the end of their device allocation.", i, name[k],
-                         (unsigned long) ((const char *) first[k] + ext[k] - ((const char *) base + size)));
-            return false;
-        }
-        if (*device >= 0 && at.device != *device) {
-            fa_set_error("<4:2:0 target %u>: its planes live on devices %d and %d.", i, *device, at.device);
-            return false;
-        }
-        *device = at.device;
+        *device = dev;
     }
     return true;
 }
@@ -319,45 +248,23 @@ extern "C" int fiasco_amd_planes_to_420_device(const int16_t *planes_y, const in
     fiasco_amd_device_target_420 t;
     if (!y4_check_geometry(0, target, width, height, &t)) return 0;
     if (!ic_have_device()) return 0;
-    int tdev = -1, cur = -1;
+    int tdev = -1;
     if (!y4_check_memory(0, t, &tdev)) return 0;
     const int16_t *src[3] = { planes_y, planes_cb, planes_cr };
     const size_t bytes[3] = { (size_t) width * height * 2, (size_t) (width >> 1) * (height >> 1) * 2, (size_t) (width >> 1) * (height >> 1) * 2 };
     for (unsigned k = 0; k < 3; k++) {
-        hipPointerAttribute_t at;
-        hipDeviceptr_t base = nullptr;
-        size_t size = 0;
-        if (hipPointerGetAttributes(&at, src[k]) != hipSuccess || at.type != hipMemoryTypeDevice) {
-            (void) hipGetLastError();
-            fa_set_error("%s: the planes are not in device memory.", who);
-            return 0;
-        }
-        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) src[k]) != hipSuccess) (void) hipGetLastError();
-        else if ((const char *) src[k] + bytes[k] > (const char *) base + size) {
-            fa_set_error("%s: the planes reach %lu bytes beyond the end of their device allocation.", who,
-                         (unsigned long) ((const char *) src[k] + bytes[k] - ((const char *) base + size)));
-            return 0;
-        }
-        if (at.device != tdev) {
-            fa_set_error("<4:2:0 target 0>: the target lives on device %d, the planes on device %d (no peer copy on this path).", tdev, at.device);
+        int pdev = -1;
+        if (!ic_check_memory(who, "planes are", "planes", src[k], bytes[k], nullptr, &pdev)) return 0;
+        if (pdev != tdev) {
+            fa_set_error("<4:2:0 target 0>: the target lives on device %d, the planes on device %d (no peer copy on this path).", tdev, pdev);
             return 0;
         }
     }
-    if (hipGetDevice(&cur) != hipSuccess) { (void) hipGetLastError(); cur = -1; }
-    if (cur != tdev && hipSetDevice(tdev) != hipSuccess) { fa_set_error("HIP error: %s", hipGetErrorString(hipGetLastError())); return 0; }
-    /* on the caller's stream itself, as fiasco_amd_planes_to_pixels_device(): the table of one frame is copied with a
-     * blocking call and freed once the kernel has read it */
-    Y4Frame h, *d_tab = nullptr;
+    Y4Frame h;
     unsigned long long total = 0;
     y4_describe(h, planes_y, planes_cb, planes_cr, t, total);
-    bool ok = hipMalloc((void **) &d_tab, sizeof h) == hipSuccess
-              && hipMemcpy(d_tab, &h, sizeof h, hipMemcpyHostToDevice) == hipSuccess
-              && y4_launch(d_tab, 1, total, oc_cus(), (hipStream_t) stream)
-              && hipStreamSynchronize((hipStream_t) stream) == hipSuccess;
-    if (!ok) fa_set_error("HIP error: %s", hipGetErrorString(hipGetLastError()));
-    if (d_tab) (void) hipFree(d_tab);
-    if (cur >= 0 && cur != tdev) (void) hipSetDevice(cur);
-    return ok ? 1 : 0;
+    return ft_run_alone(&h, sizeof h, [&](const void *d_tab, int ncu) { return y4_launch((const Y4Frame *) d_tab, 1, total, ncu, (hipStream_t) stream); },
+                        tdev, (hipStream_t) stream);
 }
 
 #endif      /* Y420_HOST_REPLAY */

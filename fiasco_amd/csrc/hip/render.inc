@@ -10,67 +10,39 @@
  *  them (nothing contracted into a fused multiply-add); the pixel word is packed arithmetically from the renderer's
  *  shift counts, which travel as a kernel argument: no lookup table.  Blue is not shifted, as in the reference.
  *
- *  Shape: oc_convert_kernel's.  A work item is 16 neighbouring pixels of one source row, loaded with oc_load16; the items
- *  of all frames form one sequence over the flight's table of OcFrame (dst, pitch: the surface's; width, height: the
- *  frame's; layout: GRAY8 for a gray frame, anything else Y, Cb, Cr); the grid is sized from the CU count.  An item owns
- *  16 * bpp / 8 contiguous bytes of its row, twice that and in two rows when doubled -- 32 .. 128 bytes per row -- and
- *  writes them in pieces of 16 bytes: one vector store each where the address allows it, 4-, 2- or 1-byte stores at a
- *  ragged row end or on a surface that is not aligned to 16 bytes.  The doubled row is written in the same pass, not by a
- *  second one.  Doubled, the lanes of a wave would store 64 .. 128 bytes apart and every store instruction would touch 64 lines; there
- *  the wave exchanges its pieces through LDS first (RdWave: every lane puts the bytes of its row, then takes the 16 bytes
+ *  Shape: frame_table.inc's, over the flight's table of OcFrame (dst, pitch: the surface's; width, height: the frame's;
+ *  layout: GRAY8 for a gray frame, anything else Y, Cb, Cr).  A work item is 16 neighbouring pixels of one source row,
+ *  loaded as oc_convert_kernel loads them.  An item owns 16 * bpp / 8 contiguous bytes of its row, twice that and in two
+ *  rows when doubled -- 32 .. 128 bytes per row -- and writes them in pieces of 16 bytes: one vector store each where the
+ *  address allows it, 4-, 2- or 1-byte stores at a ragged row end or on a surface that is not aligned to 16 bytes
+ *  (px_store_bytes_wide).  The doubled row is written in the same pass, not by a second one.  Doubled, the lanes of a wave
+ *  would store 64 .. 128 bytes apart and every store instruction would touch 64 lines; there the wave exchanges its pieces through LDS first (RdWave: every lane puts the bytes of its row, then takes the 16 bytes
  *  that follow its left neighbour's), so that neighbouring lanes store neighbouring bytes wherever their items are
  *  neighbours in a row.  Same bytes, same owners of every byte's value; only which lane issues the store changes.
  *
  *  RENDER_HOST_REPLAY: the per-item functions alone as plain C++ (tests/render_step_check.cpp, for the sanitizers).
  */
 #ifdef RENDER_HOST_REPLAY
-#define RD_DEV static inline
-#define RD_GLOBAL
-struct alignas(16) rd_u4 { unsigned x, y, z, w; };
-#else
-#define RD_DEV static __device__ __forceinline__
-#define RD_GLOBAL IC_GLOBAL
-typedef ic_u4 rd_u4;
+#define PX_HOST_REPLAY 1
 #endif
+#include "px_access.inc"
 
 /* the renderer as the kernel takes it (fiasco_amd_renderer without the shift it does not apply) */
 struct RdParams { unsigned bpp, doubled, rgb, r_drop, g_drop, b_drop, r_up, g_up; };
 
-/* `nb' bytes (at most 16) of w to q: one 16-byte store, or the widest stores the address allows */
-RD_DEV void rd_store16(unsigned char *q, unsigned nb, const unsigned w[4])
-{
-    if (nb == 16 && ((size_t) q & 15) == 0) { *(RD_GLOBAL rd_u4 *) q = rd_u4{ w[0], w[1], w[2], w[3] }; return; }
-    const unsigned unit = ((size_t) q & 3) == 0 ? 4 : ((size_t) q & 1) == 0 ? 2 : 1;
-#pragma unroll
-    for (unsigned k = 0; k < 4; k++) {
-        if (unit == 4 && 4 * k + 4 <= nb) { ((RD_GLOBAL unsigned *) q)[k] = w[k]; continue; }
-#pragma unroll
-        for (unsigned h = 0; h < 2; h++) {
-            const unsigned at = 4 * k + 2 * h, half = (w[k] >> (16 * h)) & 0xffffu;
-            if (unit >= 2 && at + 2 <= nb) { ((RD_GLOBAL unsigned short *) q)[2 * k + h] = (unsigned short) half; continue; }
-            if (at < nb) ((RD_GLOBAL unsigned char *) q)[at] = (unsigned char) half;
-            if (at + 1 < nb) ((RD_GLOBAL unsigned char *) q)[at + 1] = (unsigned char) (half >> 8);
-        }
-    }
-}
-
-/* value k of 16 packed ones, arithmetically shifted: the integer part of a 12.4 pixel */
-RD_DEV int rd_int(const unsigned *v, unsigned k) { return (int) (int16_t) (v[k >> 1] >> (16 * (k & 1))) >> 4; }
-RD_DEV unsigned rd_clip255(int v) { return (unsigned) (v < 0 ? 0 : v > 255 ? 255 : v); }
-
 /* the 16 pixels of an item as they lie in memory: the pixel word at 16 and 32 bpp, three bytes at 24 bpp.  y, cbv, crv:
  * 16 packed values each (cbv, crv unused for gray) */
-RD_DEV void rd_pixels(const RdParams &P, bool color, const unsigned y[8], const unsigned cbv[8], const unsigned crv[8], unsigned pw[16])
+PX_DEV void rd_pixels(const RdParams &P, bool color, const unsigned y[8], const unsigned cbv[8], const unsigned crv[8], unsigned pw[16])
 {
 #ifndef RENDER_HOST_REPLAY
 #pragma clang fp contract(off)
 #endif
 #pragma unroll
     for (unsigned k = 0; k < 16; k++) {
-        const int yval = rd_int(y, k) + 128;
+        const int yval = px_int(y, k) + 128;
         unsigned r, g, bl;
         if (color) {
-            int cb = rd_int(cbv, k), cr = rd_int(crv, k);
+            int cb = px_int(cbv, k), cr = px_int(crv, k);
             cb = cb < -128 ? -128 : cb > 127 ? 127 : cb;
             cr = cr < -128 ? -128 : cr > 127 ? 127 : cr;
             /* lib/dither.c:155-158, character for character: double arithmetic, C truncation */
@@ -78,15 +50,15 @@ RD_DEV void rd_pixels(const RdParams &P, bool color, const unsigned y[8], const 
             const int rg = (int) (-0.7145 * cr + 0.5);
             const int bg = (int) (-0.3456 * cb + 0.5);
             const int bb = (int) ( 1.7710 * cb + 0.5);
-            r = rd_clip255(yval + rr); g = rd_clip255(yval + rg + bg); bl = rd_clip255(yval + bb);
-        } else r = g = bl = rd_clip255(yval);
+            r = px_clip255(yval + rr); g = px_clip255(yval + rg + bg); bl = px_clip255(yval + bb);
+        } else r = g = bl = px_clip255(yval);
         if (P.bpp == 24) pw[k] = P.rgb ? r | (g << 8) | (bl << 16) : bl | (g << 8) | (r << 16);
         else pw[k] = ((r >> P.r_drop) << P.r_up) | ((g >> P.g_drop) << P.g_up) | (bl >> P.b_drop);      /* blue: not shifted (lib/dither.c:205-208) */
     }
 }
 
 /* word m of the bytes an item writes into one row: B bytes per pixel, every pixel DUP times */
-template <unsigned B, unsigned DUP> RD_DEV unsigned rd_word(const unsigned pw[16], unsigned m)
+template <unsigned B, unsigned DUP> PX_DEV unsigned rd_word(const unsigned pw[16], unsigned m)
 {
     if (B == 4) return pw[m / DUP];
     if (B == 2) return (pw[(2 * m) / DUP] & 0xffffu) | (pw[(2 * m + 1) / DUP] << 16);
@@ -100,7 +72,7 @@ template <unsigned B, unsigned DUP> RD_DEV unsigned rd_word(const unsigned pw[16
 }
 
 /* the `n' pixels of an item into q0 (and q1, the row below, when DUP == 2): 16 * B * DUP bytes at most, in pieces of 16 */
-template <unsigned B, unsigned DUP> RD_DEV void rd_emit(const unsigned pw[16], unsigned n, unsigned char *q0, unsigned char *q1)
+template <unsigned B, unsigned DUP> PX_DEV void rd_emit(const unsigned pw[16], unsigned n, unsigned char *q0, unsigned char *q1)
 {
     const unsigned nb = n * B * DUP;
 #pragma unroll
@@ -108,21 +80,21 @@ template <unsigned B, unsigned DUP> RD_DEV void rd_emit(const unsigned pw[16], u
         if (16 * c < nb) {
             const unsigned w[4] = { rd_word<B, DUP>(pw, 4 * c), rd_word<B, DUP>(pw, 4 * c + 1), rd_word<B, DUP>(pw, 4 * c + 2), rd_word<B, DUP>(pw, 4 * c + 3) };
             const unsigned k = nb - 16 * c < 16 ? nb - 16 * c : 16;
-            rd_store16(q0 + 16 * c, k, w);
-            if (DUP == 2) rd_store16(q1 + 16 * c, k, w);
+            px_store_bytes_wide(q0 + 16 * c, k, w);
+            if (DUP == 2) px_store_bytes_wide(q1 + 16 * c, k, w);
         }
     }
 }
 
 /* the first byte an item owns: column x0 of source row `row' in the surface at dst */
-RD_DEV unsigned char *rd_first(const RdParams &P, unsigned char *dst, unsigned long long pitch, unsigned row, unsigned x0)
+PX_DEV unsigned char *rd_first(const RdParams &P, unsigned char *dst, unsigned long long pitch, unsigned row, unsigned x0)
 {
     const unsigned dup = P.doubled ? 2 : 1;
     return dst + (size_t) row * dup * pitch + (size_t) x0 * dup * (P.bpp / 8);
 }
 
 /* one work item: `n' (1 .. 16) pixels that begin at column x0 of source row `row', into the surface at dst */
-RD_DEV void rd_item(const RdParams &P, bool color, const unsigned y[8], const unsigned cbv[8], const unsigned crv[8], unsigned n,
+PX_DEV void rd_item(const RdParams &P, bool color, const unsigned y[8], const unsigned cbv[8], const unsigned crv[8], unsigned n,
                     unsigned char *dst, unsigned long long pitch, unsigned row, unsigned x0)
 {
     unsigned pw[16];
@@ -147,69 +119,61 @@ struct alignas(16) RdWave {
     unsigned           nb[RD_LANES];
 };
 
-template <unsigned B> RD_DEV void rd_wave_put(RdWave &W, unsigned lane, const unsigned pw[16], unsigned n, unsigned char *q0, unsigned long long pitch)
+template <unsigned B> PX_DEV void rd_wave_put(RdWave &W, unsigned lane, const unsigned pw[16], unsigned n, unsigned char *q0, unsigned long long pitch)
 {
     const unsigned CH = 2 * B;
     W.q0[lane] = (unsigned long long) (size_t) q0; W.pitch[lane] = pitch; W.nb[lane] = n * B * 2;
 #pragma unroll
     for (unsigned c = 0; c < CH; c++)
-        *(rd_u4 *) (W.piece + 4 * (lane * CH + (c + lane) % CH)) = rd_u4{ rd_word<B, 2>(pw, 4 * c), rd_word<B, 2>(pw, 4 * c + 1), rd_word<B, 2>(pw, 4 * c + 2),
+        *(px_u4 *) (W.piece + 4 * (lane * CH + (c + lane) % CH)) = px_u4{ rd_word<B, 2>(pw, 4 * c), rd_word<B, 2>(pw, 4 * c + 1), rd_word<B, 2>(pw, 4 * c + 2),
                                                                         rd_word<B, 2>(pw, 4 * c + 3) };
 }
 
-template <unsigned B> RD_DEV void rd_wave_store(const RdWave &W, unsigned lane)
+template <unsigned B> PX_DEV void rd_wave_store(const RdWave &W, unsigned lane)
 {
     const unsigned CH = 2 * B;
 #pragma unroll
     for (unsigned c = 0; c < CH; c++) {
         const unsigned piece = c * RD_LANES + lane, j = piece / CH, cj = piece - j * CH, off = 16 * cj, nb = W.nb[j];
         if (off < nb) {
-            const rd_u4 v = *(const rd_u4 *) (W.piece + 4 * (j * CH + (cj + j) % CH));
+            const px_u4 v = *(const px_u4 *) (W.piece + 4 * (j * CH + (cj + j) % CH));
             const unsigned w[4] = { v.x, v.y, v.z, v.w }, k = nb - off < 16 ? nb - off : 16;
             unsigned char *q = (unsigned char *) (size_t) W.q0[j] + off;
-            rd_store16(q, k, w);
-            rd_store16(q + W.pitch[j], k, w);
+            px_store_bytes_wide(q, k, w);
+            px_store_bytes_wide(q + W.pitch[j], k, w);
         }
     }
 }
 
 /* a lane's part before the barrier (n == 0: no item) and after it */
-RD_DEV void rd_wave_put_any(const RdParams &P, RdWave &W, unsigned lane, const unsigned pw[16], unsigned n, unsigned char *q0, unsigned long long pitch)
+PX_DEV void rd_wave_put_any(const RdParams &P, RdWave &W, unsigned lane, const unsigned pw[16], unsigned n, unsigned char *q0, unsigned long long pitch)
 {
     if (P.bpp == 16) rd_wave_put<2>(W, lane, pw, n, q0, pitch); else if (P.bpp == 24) rd_wave_put<3>(W, lane, pw, n, q0, pitch); else rd_wave_put<4>(W, lane, pw, n, q0, pitch);
 }
-RD_DEV void rd_wave_store_any(const RdParams &P, const RdWave &W, unsigned lane)
+PX_DEV void rd_wave_store_any(const RdParams &P, const RdWave &W, unsigned lane)
 {
     if (P.bpp == 16) rd_wave_store<2>(W, lane); else if (P.bpp == 24) rd_wave_store<3>(W, lane); else rd_wave_store<4>(W, lane);
 }
 
 #ifndef RENDER_HOST_REPLAY
 
-/* EXCHANGE: the doubled renderers; every thread of the workgroup then stays in the loop to the end (the barriers) */
+/* EXCHANGE: the doubled renderers; every thread of the workgroup then stays in the loop to the end (the barriers).  So
+ * this kernel keeps a loop of its own, for both builds, around frame_table.inc's stretch, search and step */
 template <bool EXCHANGE>
 __global__ void __launch_bounds__(256) rd_render_kernel(const OcFrame *__restrict__ frames, unsigned nframes, unsigned long long total, RdParams P)
 {
-    const unsigned long long tiles = (total + 255) / 256;
-    const unsigned long long t0 = tiles * blockIdx.x / gridDim.x, t1 = tiles * (blockIdx.x + 1) / gridDim.x;
-    if (t0 >= t1) return;
-    unsigned f = 0;
-    {   /* the frame of the stretch's first item: the last one that starts at or before it */
-        unsigned lo = 0, hi = nframes;
-        while (hi - lo > 1) {
-            const unsigned mid = (lo + hi) / 2;
-            if (frames[mid].first <= t0 * 256) lo = mid; else hi = mid;
-        }
-        f = lo;
-    }
+    unsigned long long t0, t1;
+    if (!ft_stretch(total, t0, t1)) return;
+    unsigned f = ft_find(frames, nframes, t0 * FT_TILE);
     for (unsigned long long t = t0; t < t1; t++) {
-        const unsigned long long it = t * 256 + threadIdx.x;
+        const unsigned long long it = t * FT_TILE + threadIdx.x;
         const bool valid = it < total;
         if (!EXCHANGE && !valid) break;
         unsigned pw[16] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 }, n = 0;
         unsigned char *q0 = nullptr;
         unsigned long long pitch = 0;
         if (valid) {
-            while (f + 1 < nframes && frames[f + 1].first <= it) f++;
+            f = ft_step(frames, nframes, f, it);
             const OcFrame F = frames[f];
             const unsigned local = (unsigned) (it - F.first);
             const unsigned row = local / F.cpr, x0 = (local - row * F.cpr) * 16;
@@ -218,8 +182,8 @@ __global__ void __launch_bounds__(256) rd_render_kernel(const OcFrame *__restric
             const int16_t *p = F.src + (size_t) row * F.width + x0;
             const bool color = F.layout != FIASCO_AMD_GRAY8;
             unsigned y[8], cbv[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, crv[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-            oc_load16(p, n, y);
-            if (color) { oc_load16(p + npix, n, cbv); oc_load16(p + 2 * npix, n, crv); }
+            px_load_values(p, n, y);
+            if (color) { px_load_values(p + npix, n, cbv); px_load_values(p + 2 * npix, n, crv); }
             if (!EXCHANGE) { rd_item(P, color, y, cbv, crv, n, F.dst, F.pitch, row, x0); continue; }
             rd_pixels(P, color, y, cbv, crv, pw);
             q0 = rd_first(P, F.dst, F.pitch, row, x0); pitch = F.pitch;
@@ -245,12 +209,7 @@ static RdParams rd_params(const fiasco_amd_renderer *r)
 /* oc_launch for the rendering kernel: the table is one oc_describe filled, with the surface as the target */
 static bool rd_launch(const OcFrame *d_tab, unsigned n, unsigned long long total, const fiasco_amd_renderer *r, int ncu, hipStream_t stream)
 {
-    unsigned long long grid = (unsigned long long) (ncu > 0 ? ncu : 256) * 8, tiles = (total + 255) / 256;
-    if (grid > tiles) grid = tiles;
-    if (!grid) return true;
-    if (r->doubled) rd_render_kernel<true><<<dim3((unsigned) grid), dim3(256), 0, stream>>>(d_tab, n, total, rd_params(r));
-    else rd_render_kernel<false><<<dim3((unsigned) grid), dim3(256), 0, stream>>>(d_tab, n, total, rd_params(r));
-    return hipGetLastError() == hipSuccess;
+    return ft_launch(r->doubled ? rd_render_kernel<true> : rd_render_kernel<false>, d_tab, n, total, ncu, stream, rd_params(r));
 }
 
 /* ------------------------------------------------------------------ the entry points (include/libfiasco_amd_render.h) */
@@ -278,29 +237,12 @@ static bool rd_check_surface(unsigned i, const fiasco_amd_device_surface *in, co
         fa_set_error("<device surface %u>: the pixels and the pitch must be aligned to the %lu bytes of a pixel.", i, (unsigned long) unit);
         return false;
     }
-    hipPointerAttribute_t at;
-    if (!in->data || hipPointerGetAttributes(&at, in->data) != hipSuccess || at.type != hipMemoryTypeDevice) {
-        (void) hipGetLastError();
-        fa_set_error("<device surface %u>: the pixels are not in device memory.", i);
-        return false;
-    }
     /* these rows are WRITTEN: a surface whose allocation cannot be told is refused */
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) in->data) != hipSuccess) {
-        (void) hipGetLastError();
-        fa_set_error("<device surface %u>: the device allocation of the pixels cannot be determined.", i);
-        return false;
-    }
-    const size_t extent = (size_t) (sh - 1) * pitch + row;
-    if ((const char *) in->data + extent > (const char *) base + size) {
-        fa_set_error("<device surface %u>: the rows reach %lu bytes beyond the end of their device allocation.", i,
-                     (unsigned long) ((const char *) in->data + extent - ((const char *) base + size)));
-        return false;
-    }
+    char name[32];
+    snprintf(name, sizeof name, "<device surface %u>", i);
+    if (!ic_check_memory(name, "pixels are", "rows", in->data, (size_t) (sh - 1) * pitch + row, "pixels", device)) return false;
     out->data = in->data; out->pitch = pitch; out->plane_stride = 0;
     out->width = width; out->height = height; out->layout = color ? FIASCO_AMD_RGB8_INTERLEAVED : FIASCO_AMD_GRAY8;
-    *device = at.device;
     return true;
 }
 
@@ -311,44 +253,20 @@ extern "C" int fiasco_amd_planes_render_device(const int16_t *planes, int color,
     if (!planes || !r || !surface || !surface->data) { fa_set_error("%s: no planes, no renderer or no surface", who); return 0; }
     if (!ic_have_device()) return 0;
     fiasco_amd_device_frame t;
-    int tdev = -1, cur = -1;
+    int tdev = -1, pdev = -1;
     if (!rd_check_surface(0, surface, r, width, height, color, &t, &tdev)) return 0;
     const size_t bytes = (size_t) width * height * (color ? 3 : 1) * 2;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, planes) != hipSuccess || at.type != hipMemoryTypeDevice) {
-        (void) hipGetLastError();
-        fa_set_error("%s: the planes are not in device memory.", who);
-        return 0;
-    }
-    {
-        hipDeviceptr_t base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) planes) != hipSuccess) (void) hipGetLastError();
-        else if ((const char *) planes + bytes > (const char *) base + size) {
-            fa_set_error("%s: the planes reach %lu bytes beyond the end of their device allocation.", who,
-                         (unsigned long) ((const char *) planes + bytes - ((const char *) base + size)));
-            return 0;
-        }
-    }
+    if (!ic_check_memory(who, "planes are", "planes", planes, bytes, nullptr, &pdev)) return 0;
     if ((size_t) planes & 1) { fa_set_error("%s: the planes are not aligned to their 16-bit values.", who); return 0; }
-    if (at.device != tdev) {
-        fa_set_error("<device surface 0>: the surface lives on device %d, the planes on device %d (no peer copy on this path).", tdev, at.device);
+    if (pdev != tdev) {
+        fa_set_error("<device surface 0>: the surface lives on device %d, the planes on device %d (no peer copy on this path).", tdev, pdev);
         return 0;
     }
-    if (hipGetDevice(&cur) != hipSuccess) { (void) hipGetLastError(); cur = -1; }
-    if (cur != tdev && hipSetDevice(tdev) != hipSuccess) { fa_set_error("HIP error: %s", hipGetErrorString(hipGetLastError())); return 0; }
-    /* on the caller's stream itself, as fiasco_amd_planes_to_pixels_device(): this call waits on the host */
-    OcFrame h, *d_tab = nullptr;
+    OcFrame h;
     unsigned long long total = 0;
     oc_describe(h, planes, t, total);
-    bool ok = hipMalloc((void **) &d_tab, sizeof h) == hipSuccess
-              && hipMemcpy(d_tab, &h, sizeof h, hipMemcpyHostToDevice) == hipSuccess
-              && rd_launch(d_tab, 1, total, r, oc_cus(), (hipStream_t) stream)
-              && hipStreamSynchronize((hipStream_t) stream) == hipSuccess;
-    if (!ok) fa_set_error("HIP error: %s", hipGetErrorString(hipGetLastError()));
-    if (d_tab) (void) hipFree(d_tab);
-    if (cur >= 0 && cur != tdev) (void) hipSetDevice(cur);
-    return ok ? 1 : 0;
+    return ft_run_alone(&h, sizeof h, [&](const void *d_tab, int ncu) { return rd_launch((const OcFrame *) d_tab, 1, total, r, ncu, (hipStream_t) stream); },
+                        tdev, (hipStream_t) stream);
 }
 
 /* fiasco_amd_batch_decode_device_shown()'s path (smooth.inc) with surfaces for targets: the jobs, the devices and the

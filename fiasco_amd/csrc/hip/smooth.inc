@@ -26,7 +26,7 @@
  *  `side' is one power of two: item i of a pass is border i >> log2(side), pair i & (side - 1), idle when that is
  *  >= len (a border clipped at the frame).  No prefix sums.
  *
- *  What a wave reads and writes (one 16-bit load and one 16-bit store per pixel, IC_GLOBAL address space):
+ *  What a wave reads and writes (one 16-bit load and one 16-bit store per pixel, global address space):
  *    horizontal, side >= 64   64 neighbouring pairs of one border: 128 contiguous bytes of row y - 1 and 128 of row y,
  *                             read and written back: two cache lines per instruction where the row is aligned
  *    horizontal, side < 64    64 / side borders, from each side * 2 contiguous bytes of its two rows
@@ -46,14 +46,12 @@
  */
 
 #ifdef SMOOTH_HOST_REPLAY
-#define SM_GLOBAL
-#define SM_ITEM static inline
+#define PX_HOST_REPLAY 1
 #define SM_BOTH static inline
 #else
-#define SM_GLOBAL IC_GLOBAL
-#define SM_ITEM static __device__ __forceinline__
 #define SM_BOTH static __host__ __device__ __forceinline__
 #endif
+#include "px_access.inc"
 
 enum { SM_MAX_LEVEL = 32 };          /* side 2^16: beyond what the 16-bit coordinates of a border can reach */
 
@@ -70,11 +68,11 @@ struct SmDesc {
 SM_BOTH unsigned sm_log2_side(unsigned level) { return level & 1 ? level >> 1 : (level + 1) >> 1; }
 
 /* item i of pass `pass' of the frame d: one pixel pair, or nothing */
-SM_ITEM void sm_item(const SmDesc &d, unsigned pass, unsigned long long i)
+PX_DEV void sm_item(const SmDesc &d, unsigned pass, unsigned long long i)
 {
     if (pass >= d.npasses) return;
-    const SM_GLOBAL unsigned *first = (const SM_GLOBAL unsigned *) d.first;
-    const SM_GLOBAL fiasco_amd_border *bd = (const SM_GLOBAL fiasco_amd_border *) d.borders;
+    const PX_GLOBAL unsigned *first = (const PX_GLOBAL unsigned *) d.first;
+    const PX_GLOBAL fiasco_amd_border *bd = (const PX_GLOBAL fiasco_amd_border *) d.borders;
     const unsigned b0 = first[pass], nb = first[pass + 1] - b0;
     if (!nb) return;
     const unsigned level = bd[b0].level, lg = sm_log2_side(level);
@@ -85,18 +83,18 @@ SM_ITEM void sm_item(const SmDesc &d, unsigned pass, unsigned long long i)
     size_t ia, ib;
     if (level & 1) { ia = (y - 1) * W + x + pair; ib = ia + W; }
     else           { ia = (y + pair) * W + x - 1; ib = ia + 1; }
-    SM_GLOBAL int16_t *p = (SM_GLOBAL int16_t *) d.plane;
+    PX_GLOBAL int16_t *p = (PX_GLOBAL int16_t *) d.plane;
     const int a = p[ia], b = p[ib], is = d.is, inegs = d.inegs;
     p[ia] = (int16_t) (((is * a) >> 10) * 2 + ((inegs * b) >> 10) * 2);
     p[ib] = (int16_t) (((is * b) >> 10) * 2 + ((inegs * a) >> 10) * 2);
 }
 
 /* the items of pass `pass' of the frame d, read where the kernel reads them: borders << log2(side); 0 beyond the last pass */
-SM_ITEM unsigned long long sm_items(const SmDesc &d, unsigned pass)
+PX_DEV unsigned long long sm_items(const SmDesc &d, unsigned pass)
 {
     if (pass >= d.npasses) return 0;
-    const SM_GLOBAL unsigned *first = (const SM_GLOBAL unsigned *) d.first;
-    const SM_GLOBAL fiasco_amd_border *bd = (const SM_GLOBAL fiasco_amd_border *) d.borders;
+    const PX_GLOBAL unsigned *first = (const PX_GLOBAL unsigned *) d.first;
+    const PX_GLOBAL fiasco_amd_border *bd = (const PX_GLOBAL fiasco_amd_border *) d.borders;
     const unsigned b0 = first[pass], nb = first[pass + 1] - b0;
     return nb ? (unsigned long long) nb << sm_log2_side(bd[b0].level) : 0ull;
 }
@@ -105,7 +103,7 @@ SM_ITEM unsigned long long sm_items(const SmDesc &d, unsigned pass)
  * owns -- the items t, t + nt, ... of that pass, each through sm_item().  The items of a pass touch disjoint pixels, so
  * their order within the pass is free; the barrier between two passes is the caller's (the kernel: __syncthreads(); a
  * replay on the CPU: finishing every t of a pass before the next pass begins). */
-SM_ITEM void sm_frame_step(const SmDesc &d, unsigned pass, unsigned t, unsigned nt)
+PX_DEV void sm_frame_step(const SmDesc &d, unsigned pass, unsigned t, unsigned nt)
 {
     const unsigned long long n = sm_items(d, pass);
     for (unsigned long long i = t; i < n; i += nt) sm_item(d, pass, i);
@@ -322,26 +320,9 @@ static int sm_planes_device(const char *who, bool fused, int16_t *y_plane, unsig
         return 0;
     }
     if (!ic_have_device()) return 0;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, y_plane) != hipSuccess || at.type != hipMemoryTypeDevice) {
-        (void) hipGetLastError();
-        fa_set_error("%s: the plane is not in device memory.", who);
-        return 0;
-    }
     /* the plane is WRITTEN: an allocation that cannot be told is refused */
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    const size_t bytes = (size_t) width * height * 2;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) y_plane) != hipSuccess) {
-        (void) hipGetLastError();
-        fa_set_error("%s: the device allocation of the plane cannot be determined.", who);
-        return 0;
-    }
-    if ((const char *) y_plane + bytes > (const char *) base + size) {
-        fa_set_error("%s: the plane reaches %lu bytes beyond the end of its device allocation.", who,
-                     (unsigned long) ((const char *) y_plane + bytes - ((const char *) base + size)));
-        return 0;
-    }
+    int dev = -1;
+    if (!ic_check_memory(who, "plane is", "plane", y_plane, (size_t) width * height * 2, "plane", &dev, true)) return 0;
     unsigned npasses = 0;
     unsigned long long pairs = 0;
     char msg[200];
@@ -350,7 +331,7 @@ static int sm_planes_device(const char *who, bool fused, int16_t *y_plane, unsig
     if (!sm_factors(smoothing, &is, &inegs) || !npasses) return 1;             /* nothing to blend */
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess) { (void) hipGetLastError(); cur = -1; }
-    if (cur != at.device && hipSetDevice(at.device) != hipSuccess) { fa_set_error("HIP error: %s", hipGetErrorString(hipGetLastError())); return 0; }
+    if (cur != dev && hipSetDevice(dev) != hipSuccess) { fa_set_error("HIP error: %s", hipGetErrorString(hipGetLastError())); return 0; }
     /* on the caller's stream itself: behind what it holds, before what follows.  Descriptor and tables share one small
      * allocation, filled with ONE blocking copy from a host block that lives to the end of this function, and freed once
      * the last pass has run: this call waits on the host. */
@@ -372,7 +353,7 @@ static int sm_planes_device(const char *who, bool fused, int16_t *y_plane, unsig
     if (buf && hipStreamSynchronize((hipStream_t) stream) != hipSuccess) ok = false;
     if (!ok) fa_set_error("HIP error: %s", hipGetErrorString(hipGetLastError()));
     if (buf) (void) hipFree(buf);
-    if (cur >= 0 && cur != at.device) (void) hipSetDevice(cur);
+    if (cur >= 0 && cur != dev) (void) hipSetDevice(cur);
     return ok ? 1 : 0;
 }
 

@@ -3,7 +3,7 @@
  *  the CPU, for the sanitizers.
  *
  *  A stand-alone program: it includes render.inc with RENDER_HOST_REPLAY defined -- the per-item function rd_item and what
- *  it calls (rd_pixels, rd_word, rd_emit, the store helper rd_store16) and the exchange inside a wave that the doubled build
+ *  it calls (rd_pixels, rd_word, rd_emit, the store helper px_store_bytes_wide of px_access.inc) and the exchange inside a wave that the doubled build
  *  runs between two barriers (rd_wave_put, rd_wave_store) as plain C++, no HIP, no library, no device -- and is
  *  built by tests/test_render_step_host.py with -fsanitize=address,undefined and linked with csrc/host/fa_render.c, the
  *  plain host loop.
@@ -42,7 +42,7 @@ static unsigned rnd(unsigned n)
     return (unsigned) ((rng_state >> 11) % n);
 }
 
-/* what oc_load16 hands the item: `n' values packed in pairs, the rest zero; reads exactly n values */
+/* what px_load_values hands the item: `n' values packed in pairs, the rest zero; reads exactly n values */
 static void load16(const int16_t *p, unsigned n, unsigned v[8])
 {
     for (unsigned k = 0; k < 8; k++) {

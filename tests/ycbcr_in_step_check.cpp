@@ -3,8 +3,8 @@
  *  icy_convert_kernel) replayed on the CPU, for the sanitizers.
  *
  *  A stand-alone program: it includes input_convert_ycbcr.inc with YCBCR_IN_HOST_REPLAY defined -- the per-item function
- *  icy_item and what it calls (icy_load16, icy_load8, icy_store16, icy_value, icy_row) as plain C++, no HIP, no library, no
- *  device -- and is built by tests/test_ycbcr_input_step_host.py with -fsanitize=address,undefined.
+ *  icy_item and what it calls (px_load_bytes_wide, px_load_bytes8, px_store_values of px_access.inc, icy_value, icy_row)
+ *  as plain C++, no HIP, no library, no device -- and is built by tests/test_ycbcr_input_step_host.py with -fsanitize=address,undefined.
  *    frames     widths 32, 34, 38 and 50, heights 32 and 34; 4:2:0 with two chroma planes (c_step 1) and with one plane of
  *               pairs in both orders (c_step 2: NV12, NV21), 4:4:4 with two planes; packed, and with pitches larger than
  *               the row; beginning at a 16-byte aligned address and one byte off it.  Every source plane is a heap block

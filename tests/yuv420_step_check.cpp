@@ -3,7 +3,7 @@
  *  oc420_convert_kernel) replayed on the CPU, for the sanitizers.
  *
  *  A stand-alone program: it includes output_convert_420.inc with Y420_HOST_REPLAY defined -- the per-item function y4_item
- *  and what it calls (y4_load16, y4_store16, y4_byte, y4_bytes) as plain C++, no HIP, no library, no device -- and is built
+ *  and what it calls (px_load_values, px_store_bytes_vec of px_access.inc, y4_byte, y4_bytes) as plain C++, no HIP, no library, no device -- and is built
  *  by tests/test_420_step_host.py with -fsanitize=address,undefined.
  *    planes     widths 2, 30, 34 and 50, heights 2 and 6; Y of exactly W x H values, Cb and Cr of exactly (W / 2) x (H / 2), heap
  *               blocks of their own, so an item that loads a value it does not own is caught; every plane meets the clip
