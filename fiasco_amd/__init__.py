@@ -245,6 +245,19 @@ def _render_abi():
     }
 
 
+def _render420_abi():
+    """the same for include/libfiasco_amd_render_420.h: frames decoded in 4:2:0 in the pixel formats of a display (the size
+    rule and the host loop in host code that needs no device; the kernel and the batch entry in the HIP library)"""
+    c = ctypes
+    P, ptr, i, u, size, surfaces = c.POINTER, c.c_void_p, c.c_int, c.c_uint, c.c_size_t, c.POINTER(DeviceSurface)
+    return {
+        "fiasco_amd_renderer_surface_size_420": (i, [ptr, u, u, P(u), P(u), P(size)]),
+        "fiasco_amd_renderer_render_planes_420": (i, [ptr, ptr, ptr, ptr, u, u, ptr]),
+        "fiasco_amd_planes_render_device_420": (i, [ptr, ptr, ptr, u, u, ptr, surfaces, ptr]),
+        "fiasco_amd_batch_decode_device_rendered_420": (i, [ptr, ptr, i, i, surfaces, ptr]),
+    }
+
+
 def _yuv420_abi():
     """the same for include/libfiasco_amd_420.h: decoded frames in 4:2:0 as NV12 / NV21 / I420 buffers (the border list and the
     host planes' entry in host code, which every build of the library has; the kernel and the batch entry in the HIP library)"""
@@ -279,6 +292,9 @@ _DISPLAY_SIGNATURES = _display_abi()
 _RENDER_SIGNATURES = _render_abi()
 _YUV420_SIGNATURES = _yuv420_abi()
 _YCBCR_SIGNATURES = _ycbcr_abi()
+_RENDER420_SIGNATURES = _render420_abi()
+# every symbol include/libfiasco_amd_render_420.h declares
+RENDER420_SYMBOLS = list(_RENDER420_SIGNATURES)
 # every symbol include/libfiasco_amd_ycbcr.h declares
 YCBCR_SYMBOLS = list(_YCBCR_SIGNATURES)
 # every symbol include/libfiasco_amd_420.h declares
@@ -316,7 +332,7 @@ class Library:
             raise FiascoError("%s is missing: run fiasco_amd.build() (there is no fallback)" % path)
         self.path = path
         self.L = ctypes.CDLL(path)
-        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VIDEO_SIGNATURES.items()) + list(_SMOOTH_SIGNATURES.items()) + list(_DISPLAY_SIGNATURES.items()) + list(_RENDER_SIGNATURES.items()) + list(_YUV420_SIGNATURES.items()) + list(_YCBCR_SIGNATURES.items()):      # the one place that declares the ABI to ctypes
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VIDEO_SIGNATURES.items()) + list(_SMOOTH_SIGNATURES.items()) + list(_DISPLAY_SIGNATURES.items()) + list(_RENDER_SIGNATURES.items()) + list(_YUV420_SIGNATURES.items()) + list(_YCBCR_SIGNATURES.items()) + list(_RENDER420_SIGNATURES.items()):      # the one place that declares the ABI to ctypes
             if hasattr(self.L, name):
                 fn = getattr(self.L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -722,6 +738,23 @@ class Batch:
             raise FiascoError(self.lib.error_message())
         return good
 
+    def decode_rendered_420(self, renderer, surfaces, magnify=0, smoothing=-1, stream=None):
+        """fiasco_amd_batch_decode_device_rendered_420: the frames of the last finished pass as the reference's viewer shows
+        them on a screen -- decoded in 4:2:0 as decode_420 decodes them, at `-m magnify -s smoothing`, and rendered through
+        `renderer` with every chroma sample standing for its 2 x 2 pixels -- into `surfaces`, one per frame as
+        decode_rendered takes them, of the size renderer.surface_size_420() gives for the frame at magnified_size(); None
+        skips the frame.  A gray frame and a frame whose chroma the reference leaves zero fail alone.  Returns the number
+        of frames written."""
+        surfaces = list(surfaces)
+        if len(surfaces) != self.n:
+            raise FiascoError("decode_rendered_420: %d surfaces for a batch of %d" % (len(surfaces), self.n))
+        arr = _device_surfaces(surfaces, renderer.bpp)
+        good = self.lib.L.fiasco_amd_batch_decode_device_rendered_420(self.handle, renderer.handle, magnify, smoothing, arr,
+                                                                      _stream_of([t for t in surfaces if t is not None], stream))
+        if not good:
+            raise FiascoError(self.lib.error_message())
+        return good
+
     def decode_thumbnails(self, targets, reduce, thumbs, stream=None, smoothing=0):
         """fiasco_amd_batch_decode_device_thumbnails: ONE decode of the frames of the last finished pass that writes
         every frame into `targets` as decode_device does (None, or a list in which None skips the full-size frame) and
@@ -1037,10 +1070,50 @@ class Renderer:
             raise FiascoError(self.lib.error_message())
         return buf.raw
 
+    def surface_size_420(self, width, height):
+        """fiasco_amd_renderer_surface_size_420: (surface width, surface height, bytes of a packed row) for a 4:2:0 frame of
+        width x height; FiascoError for an odd side, and at 24 bpp not doubled for a width that is no multiple of 4."""
+        w, h, row = ctypes.c_uint(), ctypes.c_uint(), ctypes.c_size_t()
+        if not self.lib.L.fiasco_amd_renderer_surface_size_420(self.handle, width, height, w, h, row):
+            raise FiascoError(self.lib.error_message())
+        return w.value, h.value, row.value
+
+    def render_planes_420(self, y, cb, cr):
+        """fiasco_amd_renderer_render_planes_420, the host loop: int16 numpy planes (12.4 fixed point) Y of H x W, Cb and Cr
+        of H/2 x W/2 -> the bytes of the packed surface."""
+        import numpy
+        y, cb, cr = (numpy.ascontiguousarray(p, dtype=numpy.int16) for p in (y, cb, cr))
+        if y.ndim != 2 or cb.shape != (y.shape[0] // 2, y.shape[1] // 2) or cr.shape != cb.shape:
+            raise FiascoError("render_planes_420: int16 planes of H x W, H/2 x W/2 and H/2 x W/2 expected, not %s, %s, %s" % (y.shape, cb.shape, cr.shape))
+        h, w = y.shape
+        _, sh, row = self.surface_size_420(w, h)
+        buf = ctypes.create_string_buffer(sh * row)
+        if not self.lib.L.fiasco_amd_renderer_render_planes_420(self.handle, y.ctypes.data, cb.ctypes.data, cr.ctypes.data, w, h, buf):
+            raise FiascoError(self.lib.error_message())
+        return buf.raw
+
     def delete(self):
         if self.handle:
             self.lib.L.fiasco_amd_renderer_delete(self.handle)
             self.handle = None
+
+
+def render_planes_device_420(lib, renderer, y, cb, cr, surface, stream=None):
+    """fiasco_amd_planes_render_device_420: the 4:2:0 rendering kernel alone.  `y`, `cb`, `cr`: packed int16 arrays on the GPU
+    (12.4 fixed point) of H x W, H/2 x W/2 and H/2 x W/2; `surface`: as Batch.decode_rendered_420.  Runs on `stream`
+    (default as decode_device) and waits for it."""
+    planes = [_packed_planes(n, p) for n, p in (("y", y), ("cb", cb), ("cr", cr))]
+    if any(len(shape) != 2 for _, shape in planes):
+        raise FiascoError("render_planes_device_420: three int16 arrays of two dimensions expected")
+    (h, w), sb, sr = planes[0][1], planes[1][1], planes[2][1]
+    if sb != (h // 2, w // 2) or sr != sb:
+        raise FiascoError("render_planes_device_420: chroma planes of %s and %s for a Y plane of %d x %d" % (sb[::-1], sr[::-1], w, h))
+    arr = _device_surfaces([surface], renderer.bpp)
+    if surface is None:
+        raise FiascoError("render_planes_device_420: no surface")
+    if not lib.L.fiasco_amd_planes_render_device_420(planes[0][0], planes[1][0], planes[2][0], w, h, renderer.handle, arr,
+                                                     _stream_of([surface], stream)):
+        raise FiascoError(lib.error_message())
 
 
 def render_planes_device(lib, renderer, planes, surface, stream=None):

@@ -41,6 +41,7 @@
 #include "libfiasco_amd_smooth.h"
 #include "libfiasco_amd_display.h"
 #include "libfiasco_amd_render.h"
+#include "libfiasco_amd_render_420.h"
 #include "libfiasco_amd_420.h"
 #include "libfiasco_amd_ycbcr.h"
 
@@ -176,4 +177,5 @@ static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const D
 #include "smooth.inc"
 #include "render.inc"             /* beside output_convert.inc: display surfaces instead of 8-bit pixels; its batch entry is smooth.inc's with surfaces */
 #include "output_convert_420.inc" /* beside output_convert.inc: NV12 / NV21 / I420 buffers of frames decoded in 4:2:0 */
+#include "render_420.inc"         /* behind both: display surfaces of frames decoded in 4:2:0 */
 #include "frame_decoder.inc"

@@ -487,6 +487,7 @@ struct DecFlight {
     std::vector<DecDesc>  descs;                /* one per frame alive after the uploads: blockIdx.y of the level launches */
     std::vector<OcFrame>  octab; std::vector<DsPlane> dstab;    /* the frames written; the planes measured */
     std::vector<Y4Frame>  y4tab;                /* ... written as 4:2:0 buffers (OcOut::t420), in place of octab */
+    std::vector<Rd4Frame> rd4tab;               /* ... or as display surfaces (OcOut::t420 and OcOut::render), in place of y4tab */
     std::vector<DecThumb> thtab; std::vector<OcFrame> thoctab;  /* the thumbnails gathered; written */
     std::vector<SmDesc>   smtab, tsmtab;        /* one per frame (thumbnail) alive and smoothed: first those of the per-pass
                                                  * launches (their blockIdx.y), then those of the fused launch (its blockIdx.x) */
@@ -804,7 +805,8 @@ static void dec_flight_measure(DecShare &S, DecFlight &F)
 }
 
 /* the frames of the flight that have a target into the caller's buffers, once the caller's stream has let go of them:
- * ONE launch of oc_convert_kernel -- or of rd_render_kernel, where the targets are display surfaces (OcOut::render) --;
+ * ONE launch of oc_convert_kernel -- or of rd_render_kernel, where the targets are display surfaces (OcOut::render); of
+ * oc420_convert_kernel for a 4:2:0 flight, or of rd420_render_kernel where that flight's targets are display surfaces --;
  * one more for the thumbnails, if there are any */
 static void dec_flight_write(DecShare &S, DecFlight &F)
 {
@@ -815,6 +817,11 @@ static void dec_flight_write(DecShare &S, DecFlight &F)
             oc_describe(F.thoctab.back(), F.fr[k].thumb, S.out->thumb[F.job[k]], thtotal);
         }
         if (!S.out->target[F.job[k]].data) continue;            /* measured only, the thumbnail only, or not this frame */
+        if (S.out->t420 && S.out->render) {
+            F.rd4tab.emplace_back();
+            rd4_describe_packed(F.rd4tab.back(), F.fr[k].planes, S.out->t420[F.job[k]], total);
+            continue;
+        }
         if (S.out->t420) {
             F.y4tab.emplace_back();
             y4_describe_packed(F.y4tab.back(), F.fr[k].planes, S.out->t420[F.job[k]], total);
@@ -823,8 +830,12 @@ static void dec_flight_write(DecShare &S, DecFlight &F)
         F.octab.emplace_back();
         oc_describe(F.octab.back(), F.fr[k].planes, S.out->target[F.job[k]], total);
     }
-    if (F.octab.empty() && F.thoctab.empty() && F.y4tab.empty()) return;
+    if (F.octab.empty() && F.thoctab.empty() && F.y4tab.empty() && F.rd4tab.empty()) return;
     bool ok = hipStreamWaitEvent(S.stream, S.out->ready, 0) == hipSuccess;
+    static_assert(sizeof(Rd4Frame) <= sizeof(Y4Frame), "the table of a 4:2:0 flight is carved for Y4Frame entries");
+    if (ok && !F.rd4tab.empty())
+        ok = hipMemcpyAsync(S.arena + F.oc_off, F.rd4tab.data(), F.rd4tab.size() * sizeof(Rd4Frame), hipMemcpyHostToDevice, S.stream) == hipSuccess
+             && rd4_launch((const Rd4Frame *) (S.arena + F.oc_off), (unsigned) F.rd4tab.size(), total, S.out->render, S.ncu, S.stream);
     if (ok && !F.y4tab.empty())
         ok = hipMemcpyAsync(S.arena + F.oc_off, F.y4tab.data(), F.y4tab.size() * sizeof(Y4Frame), hipMemcpyHostToDevice, S.stream) == hipSuccess
              && y4_launch((const Y4Frame *) (S.arena + F.oc_off), (unsigned) F.y4tab.size(), total, S.ncu, S.stream);

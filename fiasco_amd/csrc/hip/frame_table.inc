@@ -2,13 +2,14 @@
  *  frame_table.inc -- how the pixel kernels walk the frames of a launch (included by core_hip.cpp ahead of them).
  *
  *  Shape: a launch serves all frames of a share's upload or of a decoder flight.  The host fills a table with one
- *  descriptor per frame (IcFrame, IcyFrame, OcFrame, Y4Frame); the work items of all frames form ONE sequence, and a
+ *  descriptor per frame (IcFrame, IcyFrame, OcFrame, Y4Frame, Rd4Frame); the work items of all frames form ONE sequence, and a
  *  descriptor's member `first' says how many items the frames before it have -- the only member this file reads.  The grid
  *  is sized from the CU count (ft_grid), not from the work: every workgroup of FT_TILE threads takes one contiguous stretch
  *  of the sequence, tile after tile, neighbouring lanes neighbouring items.  So the frame of an item costs one binary
  *  search per workgroup, for the first item of its stretch, and a step forward now and then (ft_stretch, ft_find,
  *  ft_step).  ft_walk is that loop around a per-item function (ic_item, icy_item, oc_item, y4_item); a kernel whose threads
- *  must all stay in the loop (rd_render_kernel: the barriers of its doubled build) keeps its own loop around the same three.
+ *  must all stay in the loop (rd_render_kernel, rd420_render_kernel: the barriers of their doubled builds) keeps its own loop
+ *  around the same three.
  */
 
 enum { FT_TILE = 256 };         /* threads of a workgroup = items of a tile */

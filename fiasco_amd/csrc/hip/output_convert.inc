@@ -114,7 +114,9 @@ struct OcOut {
      * the surfaces (width, height: the frame's) and the flight launches rd_render_kernel; NULL: oc_convert_kernel */
     const fiasco_amd_renderer *render = nullptr;
     /* 4:2:0 buffers instead (fiasco_amd_batch_decode_device_420, output_convert_420.inc): t420[] are the checked targets
-     * by job index, target[] only says which frames are wanted, and the flight launches oc420_convert_kernel */
+     * by job index, target[] only says which frames are wanted, and the flight launches oc420_convert_kernel.  With
+     * `render' set as well (fiasco_amd_batch_decode_device_rendered_420, render_420.inc) t420[i].y, y_pitch, width and
+     * height describe the checked surface of frame i, and the flight launches rd420_render_kernel */
     const fiasco_amd_device_target_420 *t420 = nullptr;
 };
 

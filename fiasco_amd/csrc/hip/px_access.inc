@@ -1,6 +1,6 @@
 /*
  *  px_access.inc -- what the pixel kernels (ic_convert_kernel, icy_convert_kernel, oc_convert_kernel, oc420_convert_kernel,
- *  rd_render_kernel; the smoothing and measuring kernels beside them) read and write at the ragged ends of their rows:
+ *  rd_render_kernel, rd420_render_kernel; the smoothing and measuring kernels beside them) read and write at the ragged ends of their rows:
  *  the partial 16-byte accesses of a work item, and the one switch that turns them and the per-item functions built on
  *  them into plain C++ (included by core_hip.cpp ahead of those files, and by each of them under its replay switch).
  *
@@ -16,7 +16,7 @@
  *  question of speed to be measured on its own, not a clean-up.
  *
  *  PX_HOST_REPLAY: everything here as plain C++ -- no address space, structs in place of the vector types.  A step check
- *  defines the switch of the file it replays (Y420_HOST_REPLAY, RENDER_HOST_REPLAY, YCBCR_IN_HOST_REPLAY,
+ *  defines the switch of the file it replays (Y420_HOST_REPLAY, RENDER_HOST_REPLAY, RENDER420_HOST_REPLAY, YCBCR_IN_HOST_REPLAY,
  *  SMOOTH_HOST_REPLAY); that switch turns this one on and selects which part of its file is compiled.
  */
 #ifndef PX_ACCESS_INC

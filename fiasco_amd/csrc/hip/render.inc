@@ -31,8 +31,9 @@
 struct RdParams { unsigned bpp, doubled, rgb, r_drop, g_drop, b_drop, r_up, g_up; };
 
 /* the 16 pixels of an item as they lie in memory: the pixel word at 16 and 32 bpp, three bytes at 24 bpp.  y, cbv, crv:
- * 16 packed values each (cbv, crv unused for gray) */
-PX_DEV void rd_pixels(const RdParams &P, bool color, const unsigned y[8], const unsigned cbv[8], const unsigned crv[8], unsigned pw[16])
+ * 16 packed values each (cbv, crv unused for gray).  CSH 1: pixel k takes chroma value k >> 1 -- the 8 samples a row of
+ * 16 pixels has in 4:2:0 (render_420.inc); 0 leaves this function as it was */
+template <unsigned CSH = 0> PX_DEV void rd_pixels(const RdParams &P, bool color, const unsigned y[8], const unsigned cbv[8], const unsigned crv[8], unsigned pw[16])
 {
 #ifndef RENDER_HOST_REPLAY
 #pragma clang fp contract(off)
@@ -42,7 +43,7 @@ PX_DEV void rd_pixels(const RdParams &P, bool color, const unsigned y[8], const 
         const int yval = px_int(y, k) + 128;
         unsigned r, g, bl;
         if (color) {
-            int cb = px_int(cbv, k), cr = px_int(crv, k);
+            int cb = px_int(cbv, k >> CSH), cr = px_int(crv, k >> CSH);
             cb = cb < -128 ? -128 : cb > 127 ? 127 : cb;
             cr = cr < -128 ? -128 : cr > 127 ? 127 : cr;
             /* lib/dither.c:155-158, character for character: double arithmetic, C truncation */
@@ -93,16 +94,22 @@ PX_DEV unsigned char *rd_first(const RdParams &P, unsigned char *dst, unsigned l
     return dst + (size_t) row * dup * pitch + (size_t) x0 * dup * (P.bpp / 8);
 }
 
+/* the `n' pixels pw of an item that begins at column x0 of source row `row', into the surface at dst */
+PX_DEV void rd_store(const RdParams &P, const unsigned pw[16], unsigned n, unsigned char *dst, unsigned long long pitch, unsigned row, unsigned x0)
+{
+    unsigned char *q0 = rd_first(P, dst, pitch, row, x0), *q1 = P.doubled ? q0 + pitch : q0;
+    if (P.bpp == 16) { if (P.doubled) rd_emit<2, 2>(pw, n, q0, q1); else rd_emit<2, 1>(pw, n, q0, q1); }
+    else if (P.bpp == 24) { if (P.doubled) rd_emit<3, 2>(pw, n, q0, q1); else rd_emit<3, 1>(pw, n, q0, q1); }
+    else { if (P.doubled) rd_emit<4, 2>(pw, n, q0, q1); else rd_emit<4, 1>(pw, n, q0, q1); }
+}
+
 /* one work item: `n' (1 .. 16) pixels that begin at column x0 of source row `row', into the surface at dst */
 PX_DEV void rd_item(const RdParams &P, bool color, const unsigned y[8], const unsigned cbv[8], const unsigned crv[8], unsigned n,
                     unsigned char *dst, unsigned long long pitch, unsigned row, unsigned x0)
 {
     unsigned pw[16];
     rd_pixels(P, color, y, cbv, crv, pw);
-    unsigned char *q0 = rd_first(P, dst, pitch, row, x0), *q1 = P.doubled ? q0 + pitch : q0;
-    if (P.bpp == 16) { if (P.doubled) rd_emit<2, 2>(pw, n, q0, q1); else rd_emit<2, 1>(pw, n, q0, q1); }
-    else if (P.bpp == 24) { if (P.doubled) rd_emit<3, 2>(pw, n, q0, q1); else rd_emit<3, 1>(pw, n, q0, q1); }
-    else { if (P.doubled) rd_emit<4, 2>(pw, n, q0, q1); else rd_emit<4, 1>(pw, n, q0, q1); }
+    rd_store(P, pw, n, dst, pitch, row, x0);
 }
 
 /* ------------------------------------------------------------------ doubled surfaces: the exchange inside a wave
@@ -218,11 +225,13 @@ static bool rd_launch(const OcFrame *d_tab, unsigned n, unsigned long long total
  * device memory, rows inside the allocation -- and the alignment of the pixels.  *out: the surface as a target of the
  * FRAME's size (what oc_describe takes), pitch filled in; *device: where it lives */
 static bool rd_check_surface(unsigned i, const fiasco_amd_device_surface *in, const fiasco_amd_renderer *r, unsigned width, unsigned height, int color,
-                             fiasco_amd_device_frame *out, int *device)
+                             fiasco_amd_device_frame *out, int *device, bool c420 = false)
 {
     unsigned sw = 0, sh = 0;
     size_t row = 0;
-    if (!fiasco_amd_renderer_surface_size(r, width, height, color, &sw, &sh, &row)) return false;
+    /* c420: the frame is decoded in 4:2:0 and the size rule is that format's (libfiasco_amd_render_420.h) */
+    if (!(c420 ? fiasco_amd_renderer_surface_size_420(r, width, height, &sw, &sh, &row) : fiasco_amd_renderer_surface_size(r, width, height, color, &sw, &sh, &row)))
+        return false;
     if (in->width != sw || in->height != sh) {
         fa_set_error("<device surface %u>: %u x %u pixels for a frame of %u x %u%s: %u x %u.", i, in->width, in->height, width, height,
                      r->doubled ? " doubled" : "", sw, sh);

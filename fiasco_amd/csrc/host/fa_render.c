@@ -11,6 +11,7 @@
 #include <string.h>
 #include "fa_host.h"
 #include "libfiasco_amd_render.h"
+#include "libfiasco_amd_render_420.h"
 
 /* bits set / zero bits below, and whether the mask is one run of at most 8 bits inside `bpp' bits */
 static int mask_shape(unsigned long mask, unsigned bpp, unsigned *bits, unsigned *below)
@@ -78,6 +79,26 @@ int fiasco_amd_renderer_surface_size(const fiasco_amd_renderer_t *r, unsigned wi
 static unsigned clip255(int v) { return (unsigned) (v < 0 ? 0 : v > 255 ? 255 : v); }
 static int clamp_chroma(int v) { return v < -128 ? -128 : v > 127 ? 127 : v; }
 
+/* the pixel of yval and two clamped chroma values as its `bytes' bytes in memory */
+static void pixel_bytes(const fiasco_amd_renderer_t *r, int color, int yval, int cb, int cr, unsigned char px[4])
+{
+    int R = yval, G = yval, B = yval;
+    if (color) {
+        /* lib/dither.c:155-158: double arithmetic, C truncation (this file is built with -ffp-contract=off) */
+        R = yval + (int) ( 1.4022 * cr + 0.5);
+        G = yval + (int) (-0.7145 * cr + 0.5) + (int) (-0.3456 * cb + 0.5);
+        B = yval + (int) ( 1.7710 * cb + 0.5);
+    }
+    px[0] = px[1] = px[2] = px[3] = 0;
+    if (r->bpp == 24) {
+        px[0] = (unsigned char) clip255(r->rgb ? R : B); px[1] = (unsigned char) clip255(G); px[2] = (unsigned char) clip255(r->rgb ? B : R);
+    } else {
+        /* blue is not shifted (lib/dither.c:205-208) */
+        const unsigned v = ((clip255(R) >> r->r_drop) << r->r_up) | ((clip255(G) >> r->g_drop) << r->g_up) | (clip255(B) >> r->b_drop);
+        px[0] = (unsigned char) v; px[1] = (unsigned char) (v >> 8); px[2] = (unsigned char) (v >> 16); px[3] = (unsigned char) (v >> 24);
+    }
+}
+
 int fiasco_amd_renderer_render_planes(const fiasco_amd_renderer_t *r, const int16_t *planes, int color, unsigned width, unsigned height,
                                       unsigned char *out)
 {
@@ -91,22 +112,54 @@ int fiasco_amd_renderer_render_planes(const fiasco_amd_renderer_t *r, const int1
         for (unsigned x = 0; x < width; x++) {
             const size_t at = (size_t) y * width + x;
             const int yval = (planes[at] >> 4) + 128;
-            int R = yval, G = yval, B = yval;
-            if (color) {
-                const int cb = clamp_chroma(planes[npix + at] >> 4), cr = clamp_chroma(planes[2 * npix + at] >> 4);
-                /* lib/dither.c:155-158: double arithmetic, C truncation (this file is built with -ffp-contract=off) */
-                R = yval + (int) ( 1.4022 * cr + 0.5);
-                G = yval + (int) (-0.7145 * cr + 0.5) + (int) (-0.3456 * cb + 0.5);
-                B = yval + (int) ( 1.7710 * cb + 0.5);
-            }
-            unsigned char px[4] = { 0, 0, 0, 0 };
-            if (r->bpp == 24) {
-                px[0] = (unsigned char) clip255(r->rgb ? R : B); px[1] = (unsigned char) clip255(G); px[2] = (unsigned char) clip255(r->rgb ? B : R);
-            } else {
-                /* blue is not shifted (lib/dither.c:205-208) */
-                const unsigned v = ((clip255(R) >> r->r_drop) << r->r_up) | ((clip255(G) >> r->g_drop) << r->g_up) | (clip255(B) >> r->b_drop);
-                px[0] = (unsigned char) v; px[1] = (unsigned char) (v >> 8); px[2] = (unsigned char) (v >> 16); px[3] = (unsigned char) (v >> 24);
-            }
+            unsigned char px[4];
+            pixel_bytes(r, color, yval, color ? clamp_chroma(planes[npix + at] >> 4) : 0, color ? clamp_chroma(planes[2 * npix + at] >> 4) : 0, px);
+            for (unsigned k = 0; k < dup; k++) memcpy(q + ((size_t) x * dup + k) * bytes, px, bytes);
+        }
+        if (dup == 2) memcpy(q + row, q, row);
+    }
+    return 1;
+}
+
+/* ------------------------------------------------------------------ 4:2:0 (include/libfiasco_amd_render_420.h) */
+
+int fiasco_amd_renderer_surface_size_420(const fiasco_amd_renderer_t *r, unsigned width, unsigned height, unsigned *out_width,
+                                         unsigned *out_height, size_t *row_bytes)
+{
+    if (!r) { fa_set_error("Parameter `%s' not defined (NULL).", "renderer"); return 0; }
+    if (!width || !height || width > FA_RENDER_MAX_SIDE || height > FA_RENDER_MAX_SIDE) {
+        fa_set_error("fiasco_amd_renderer: a frame of %u x %u pixels (1 .. %u each way).", width, height, (unsigned) FA_RENDER_MAX_SIDE);
+        return 0;
+    }
+    /* the reference's 4:2:0 loops count pixel pairs and row pairs */
+    if ((width | height) & 1) {
+        fa_set_error("fiasco_amd_renderer: 4:2:0: %u x %u pixels: the width or the height is odd (the reference renders pixel pairs of row pairs).", width, height);
+        return 0;
+    }
+    /* ... and at 24 bpp quadruples of a row, by which they walk the chroma pointers as well */
+    if (r->bpp == 24 && !r->doubled && (width & 3)) {
+        fa_set_error("fiasco_amd_renderer: 4:2:0 at 24 bpp: the width %u is not a multiple of 4 (the reference's rows fall out of step with its chroma planes).", width);
+        return 0;
+    }
+    if (out_width) *out_width = width << r->doubled;
+    if (out_height) *out_height = height << r->doubled;
+    if (row_bytes) *row_bytes = (size_t) (width << r->doubled) * (r->bpp / 8);
+    return 1;
+}
+
+int fiasco_amd_renderer_render_planes_420(const fiasco_amd_renderer_t *r, const int16_t *y, const int16_t *cb, const int16_t *cr,
+                                          unsigned width, unsigned height, unsigned char *out)
+{
+    size_t row = 0;
+    if (!y || !cb || !cr || !out) { fa_set_error("fiasco_amd_renderer_render_planes_420: no planes or no surface"); return 0; }
+    if (!fiasco_amd_renderer_surface_size_420(r, width, height, NULL, NULL, &row)) return 0;
+    const unsigned bytes = r->bpp / 8, dup = r->doubled + 1, cw = width >> 1;
+    for (unsigned yy = 0; yy < height; yy++) {
+        unsigned char *q = out + (size_t) yy * dup * row;
+        for (unsigned x = 0; x < width; x++) {
+            const size_t c = (size_t) (yy >> 1) * cw + (x >> 1);
+            unsigned char px[4];
+            pixel_bytes(r, 1, (y[(size_t) yy * width + x] >> 4) + 128, clamp_chroma(cb[c] >> 4), clamp_chroma(cr[c] >> 4), px);
             for (unsigned k = 0; k < dup; k++) memcpy(q + ((size_t) x * dup + k) * bytes, px, bytes);
         }
         if (dup == 2) memcpy(q + row, q, row);

@@ -28,8 +28,9 @@
  *    a band whose shown level would be clamped at 0 (level of the linear combinations below twice the reduction, the
  *    reduction of the chroma bands being one more);
  *    a smoothed state that falls below level 1 (libfiasco_amd_display.h), with the chroma shift for the Cb states.
- *  Intra frames of staged batches.  Not built: 4:2:0 into display surfaces, RGB from 4:2:0 planes, distortion in 4:2:0,
- *  P/B frames and the outputs of a video.  (The way back in, NV12 / NV21 / I420 input: libfiasco_amd_ycbcr.h.)
+ *  Intra frames of staged batches.  4:2:0 into display surfaces: libfiasco_amd_render_420.h.  Not built: RGB8 targets from
+ *  4:2:0 planes, distortion in 4:2:0, P/B frames and the outputs of a video.  (The way back in, NV12 / NV21 / I420 input:
+ *  libfiasco_amd_ycbcr.h.)
  */
 #ifndef LIBFIASCO_AMD_420_H
 #define LIBFIASCO_AMD_420_H 1

@@ -31,7 +31,7 @@
  *    sizes (every entry)           shapes where the reference's loops do not fill the surface: 24 bpp not doubled with
  *                                  width * height not a multiple of 4; 24 bpp doubled with an odd width; 16 bpp gray not
  *                                  doubled with an odd width * height; an empty frame or one beyond the library's size limit
- *  4:2:0 images are not rendered: the device decoder has no such frame.
+ *  4:2:0 images, what the reference's viewer renders on a screen: libfiasco_amd_render_420.h.
  */
 #ifndef LIBFIASCO_AMD_RENDER_H
 #define LIBFIASCO_AMD_RENDER_H 1
