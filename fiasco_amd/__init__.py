@@ -69,6 +69,15 @@ class SeqOutputs(ctypes.Structure):
                 ("stream", ctypes.c_void_p)]
 
 
+class StreamInfo(ctypes.Structure):
+    """struct fiasco_amd_stream_info (include/libfiasco_amd_stream.h): what the header of a stream says."""
+    _fields_ = [("width", ctypes.c_uint), ("height", ctypes.c_uint), ("color", ctypes.c_int), ("frames", ctypes.c_uint),
+                ("fps", ctypes.c_uint), ("smoothing", ctypes.c_uint), ("title", ctypes.c_char_p), ("comment", ctypes.c_char_p),
+                ("basis_name", ctypes.c_char_p), ("rpf_mantissa", ctypes.c_uint), ("dc_rpf_mantissa", ctypes.c_uint),
+                ("d_rpf_mantissa", ctypes.c_uint), ("d_dc_rpf_mantissa", ctypes.c_uint), ("B_as_past_ref", ctypes.c_int),
+                ("half_pixel", ctypes.c_int)]
+
+
 class Stats(ctypes.Structure):
     """struct fiasco_amd_stats (include/libfiasco_amd_hip.h)."""
     _fields_ = [("kernel_ms", ctypes.c_double), ("launches", ctypes.c_ulonglong),
@@ -285,7 +294,31 @@ def _ycbcr_abi():
     }
 
 
+def _stream_abi():
+    """the same for include/libfiasco_amd_stream.h: .fco streams read back (the reader, the frame order, the rewrite and the
+    border list in host code, which every build of the product has; the decode entries in the HIP library)"""
+    c = ctypes
+    P, ptr, i, u, size = c.POINTER, c.c_void_p, c.c_int, c.c_uint, c.c_size_t
+    return {
+        "fiasco_amd_stream_open": (ptr, [c.c_char_p, size]),
+        "fiasco_amd_stream_open_file": (ptr, [c.c_char_p]),
+        "fiasco_amd_stream_free": (None, [ptr]),
+        "fiasco_amd_stream_get_info": (i, [ptr, P(StreamInfo)]),
+        "fiasco_amd_stream_frame_type": (i, [ptr, u]),
+        "fiasco_amd_stream_coding_order": (i, [ptr, P(u), u]),
+        "fiasco_amd_stream_rewrite": (i, [ptr, P(ptr), P(size)]),
+        "fiasco_amd_stream_smoothing_borders": (i, [ptr, u, i, i, P(Border), u]),
+        "fiasco_amd_stream_decode_device": (i, [ptr, u, u, i, i, P(DeviceTarget), ptr]),
+        "fiasco_amd_stream_decode_device_420": (i, [ptr, u, u, i, i, P(DeviceTarget420), ptr]),
+        "fiasco_amd_stream_decode_planes": (i, [ptr, u, i, ptr]),
+        "fiasco_amd_stream_decode_planes_420": (i, [ptr, u, i, ptr]),
+    }
+
+
 _SIGNATURES = _abi()
+_STREAM_SIGNATURES = _stream_abi()
+# every symbol include/libfiasco_amd_stream.h declares
+STREAM_SYMBOLS = list(_STREAM_SIGNATURES)
 _VIDEO_SIGNATURES = _video_abi()
 _SMOOTH_SIGNATURES = _smooth_abi()
 _DISPLAY_SIGNATURES = _display_abi()
@@ -332,7 +365,7 @@ class Library:
             raise FiascoError("%s is missing: run fiasco_amd.build() (there is no fallback)" % path)
         self.path = path
         self.L = ctypes.CDLL(path)
-        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VIDEO_SIGNATURES.items()) + list(_SMOOTH_SIGNATURES.items()) + list(_DISPLAY_SIGNATURES.items()) + list(_RENDER_SIGNATURES.items()) + list(_YUV420_SIGNATURES.items()) + list(_YCBCR_SIGNATURES.items()) + list(_RENDER420_SIGNATURES.items()):      # the one place that declares the ABI to ctypes
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_VIDEO_SIGNATURES.items()) + list(_SMOOTH_SIGNATURES.items()) + list(_DISPLAY_SIGNATURES.items()) + list(_RENDER_SIGNATURES.items()) + list(_YUV420_SIGNATURES.items()) + list(_YCBCR_SIGNATURES.items()) + list(_RENDER420_SIGNATURES.items()) + list(_STREAM_SIGNATURES.items()):      # the one place that declares the ABI to ctypes
             if hasattr(self.L, name):
                 fn = getattr(self.L, name)
                 fn.restype, fn.argtypes = restype, argtypes
@@ -1435,6 +1468,117 @@ class Sequence:
         if self.handle:
             self.L.fiasco_amd_seq_free(self.handle)
             self.handle = None
+
+
+class Stream:
+    """A .fco stream that was read (include/libfiasco_amd_stream.h): `data` is the stream as bytes, or -- with
+    filename=True -- the name of its file.  Opening parses and validates every frame; a stream that fails raises
+    FiascoError with the reader's message."""
+
+    def __init__(self, lib, data, filename=False):
+        self.lib = lib
+        if not hasattr(lib.L, "fiasco_amd_stream_open"):
+            raise FiascoError("%s has no stream reader" % lib.path)
+        if filename:
+            self.handle = lib.L.fiasco_amd_stream_open_file(os.fsencode(data))
+        else:
+            data = bytes(data)
+            self.handle = lib.L.fiasco_amd_stream_open(data, len(data))
+        if not self.handle:
+            raise FiascoError(lib.error_message())
+        raw = StreamInfo()
+        if not lib.L.fiasco_amd_stream_get_info(self.handle, ctypes.byref(raw)):
+            raise FiascoError(lib.error_message())
+        self.info = {name: getattr(raw, name) for name, _ in StreamInfo._fields_}
+        for name in ("title", "comment", "basis_name"):
+            self.info[name] = (self.info[name] or b"").decode("latin-1")
+        self.n = raw.frames
+        self.frame_types = [lib.L.fiasco_amd_stream_frame_type(self.handle, d) for d in range(self.n)]
+        order = (ctypes.c_uint * max(self.n, 1))()
+        if lib.L.fiasco_amd_stream_coding_order(self.handle, order, self.n) != self.n:
+            raise FiascoError(lib.error_message())
+        self.coding_order = list(order[:self.n])
+
+    def _size(self, magnify):
+        w, h = self.info["width"], self.info["height"]
+        return magnified_size(self.lib, w, h, magnify) if magnify else (w, h)
+
+    def rewrite(self):
+        """fiasco_amd_stream_rewrite: every frame through the writer again; for a stream a coder wrote, its bytes."""
+        out, n = ctypes.c_void_p(), ctypes.c_size_t()
+        if not self.lib.L.fiasco_amd_stream_rewrite(self.handle, ctypes.byref(out), ctypes.byref(n)):
+            raise FiascoError(self.lib.error_message())
+        try:
+            return ctypes.string_at(out.value, n.value)
+        finally:
+            self.lib.L.fiasco_amd_free(out)
+
+    def smoothing_borders(self, display, magnify=0, format_420=False):
+        """fiasco_amd_stream_smoothing_borders: the borders `dfiasco -m magnify` smooths display frame `display` along,
+        (x, y, len, level, pass) as Batch.smoothing_borders() lists them; format_420: as Batch.smoothing_borders_420()."""
+        L = self.lib.L
+        n = L.fiasco_amd_stream_smoothing_borders(self.handle, display, magnify, int(bool(format_420)), None, 0)
+        if not n:
+            raise FiascoError(self.lib.error_message())
+        arr = (Border * n)()
+        if L.fiasco_amd_stream_smoothing_borders(self.handle, display, magnify, int(bool(format_420)), arr, n) != n:
+            raise FiascoError(self.lib.error_message())
+        return [(b.x, b.y, b.len, b.level, b.pass_) for b in arr]
+
+    def decode_device(self, targets, first=0, magnify=0, smoothing=-1, stream=None):
+        """fiasco_amd_stream_decode_device: display frames first .. first + len(targets) - 1 as `dfiasco -m magnify -s
+        smoothing -o` writes them, P and B frames included, into `targets` (as Batch.decode_shown takes them; None: not
+        this frame).  Returns the number of frames written; a frame that fails takes the frames predicted from it along
+        and lib.error_message() names the first and the cause."""
+        targets = list(targets)
+        arr = _device_targets(targets)
+        good = self.lib.L.fiasco_amd_stream_decode_device(self.handle, first, len(targets), magnify, smoothing, arr,
+                                                          _stream_of([t for t in targets if t is not None], stream))
+        if not good:
+            raise FiascoError(self.lib.error_message())
+        return good
+
+    def decode_420(self, targets, first=0, magnify=0, smoothing=-1, stream=None, order="nv12"):
+        """fiasco_amd_stream_decode_device_420: the same in 4:2:0, into targets as Batch.decode_420 takes them."""
+        targets = list(targets)
+        arr = _device_targets_420(targets, order)
+        flat = [a for t in targets if t is not None for a in t]
+        good = self.lib.L.fiasco_amd_stream_decode_device_420(self.handle, first, len(targets), magnify, smoothing, arr,
+                                                              _stream_of(flat, stream))
+        if not good:
+            raise FiascoError(self.lib.error_message())
+        return good
+
+    def decode_planes(self, display, magnify=0):
+        """fiasco_amd_stream_decode_planes: the unsmoothed planes of display frame `display` at `magnify`, int16
+        [bands, h, w] (12.4 fixed point); the frames it is predicted from are decoded on the way."""
+        import numpy
+        w, h = self._size(magnify)
+        out = numpy.empty((3 if self.info["color"] else 1, h, w), dtype=numpy.int16)
+        if not self.lib.L.fiasco_amd_stream_decode_planes(self.handle, display, magnify, out.ctypes.data):
+            raise FiascoError(self.lib.error_message())
+        return out
+
+    def decode_planes_420(self, display, magnify=0):
+        """fiasco_amd_stream_decode_planes_420: the same decoded in 4:2:0: Y [h, w], Cb and Cr [h / 2, w / 2]."""
+        import numpy
+        w, h = self._size(magnify)
+        c = (w // 2) * (h // 2)
+        out = numpy.empty(w * h + 2 * c, dtype=numpy.int16)
+        if not self.lib.L.fiasco_amd_stream_decode_planes_420(self.handle, display, magnify, out.ctypes.data):
+            raise FiascoError(self.lib.error_message())
+        return (out[:w * h].reshape(h, w), out[w * h:w * h + c].reshape(h // 2, w // 2), out[w * h + c:].reshape(h // 2, w // 2))
+
+    def free(self):
+        if self.handle:
+            self.lib.L.fiasco_amd_stream_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class COptions:

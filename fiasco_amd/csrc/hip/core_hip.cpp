@@ -44,6 +44,7 @@
 #include "libfiasco_amd_render_420.h"
 #include "libfiasco_amd_420.h"
 #include "libfiasco_amd_ycbcr.h"
+#include "libfiasco_amd_stream.h"
 
 /* Developer and test switches (FIASCO_AMD_SPEC, _NO_WIDE, _FORCE_TRI, _CAP_GUESS, _QUEUE_SLABS, _TRACE, ...)
  * are honoured only when FIASCO_AMD_DEBUG is set to something other than 0: a drop-in library must not
@@ -179,3 +180,4 @@ static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const D
 #include "output_convert_420.inc" /* beside output_convert.inc: NV12 / NV21 / I420 buffers of frames decoded in 4:2:0 */
 #include "render_420.inc"         /* behind both: display surfaces of frames decoded in 4:2:0 */
 #include "frame_decoder.inc"
+#include "stream_decode.inc"        /* behind the decoder: the frames of a .fco stream that was read, video frames included, into device buffers */

@@ -46,6 +46,13 @@
  *  tops in planes Y [H][W], Cb, Cr [H >> 1][W >> 1]; the smoothing list is fa_smoothing_borders_420()'s.  Intra frames, to
  *  4:2:0 targets (output_convert_420.inc) or to the host; the frames of a call are of one format.
  *
+ *  Frames of a stream that is walked (fa_dec_job.from_stream; csrc/host/fa_stream.c, stream_decode.inc): their reference
+ *  frames live at the magnification and in the format shown, as get_next_frame keeps them, which lifts three refusals for
+ *  P/B frames: magnification (the blocks as enlarge_image leaves them: dec_mc_scaled, dec_mc.h), 4:2:0 (dec_mc420_kernel,
+ *  dec_clip_chroma420_kernel; a 4:2:0 frame may be kept) and smoothing (a frame that is smoothed and kept is smoothed in a
+ *  copy, DecFrame::shown; the kept planes stay unsmoothed).  A residual frame may lack every linear combination, or those of
+ *  a band: it gets no tops there and the prediction is added to the zeroed planes.
+ *
  *  The decoded planes stay on the device (fa_image.dev): the next P/B frame of the sequence takes its
  *  reference frames with a device-to-device copy (upload_reference); the host copy serves every other caller.
  */
@@ -54,7 +61,8 @@ struct DecNode { int32_t tree, n; DecEdge e[6]; };                    /* 32 byte
 /* n > 6 (basis states of medium.fco / large.fco, whose edge lists run on into the next rows -- fa_wfa_append_edge):
  * the list lies behind the 2 S nodes, from DecEdge number *(int32_t *) e on */
 struct DecTop  { int32_t state, x0, y0, band; };
-struct DecMc   { int32_t x0, y0, level, type, fx, fy, bx, by; };
+#define DEC_MC_FN __host__ __device__ static inline
+#include "dec_mc.h"                /* DecMc, the blocks of a magnified frame, the items of dec_mc420_kernel */
 
 /* the frames of a flight side by side: blockIdx.y = frame */
 struct DecDesc {
@@ -219,6 +227,45 @@ __global__ void __launch_bounds__(256) dec_clip_chroma_kernel(int16_t *__restric
     planes[npix + i] = (int16_t) (v * 16);
 }
 
+/* dec_mc_kernel for a 4:2:0 frame (fa_dec_job.from_stream; restore_mc with FORMAT_4_2_0, codec/motion.c:51): one work item
+ * per pixel of (motion block, band).  Band 0 has dec_mc_kernel's geometry; in bands 1 and 2 the block's place, its sides,
+ * the four vector components and the plane width are each halved toward zero (dec_mc420_item, dec_mc.h), the planes lie
+ * where dec_assemble420_kernel puts them and the reference frames have the same layout.  Linear addressing, each band
+ * checked against its own plane.  Plain 16-bit global accesses */
+__global__ void __launch_bounds__(256) dec_mc420_kernel(const DecMc *__restrict__ mcs, unsigned nmc, unsigned maxl, int16_t *__restrict__ planes,
+                                                        const int16_t *__restrict__ past, const int16_t *__restrict__ future,
+                                                        unsigned W, unsigned H)
+{
+    const size_t idx = (size_t) blockIdx.x * 256 + threadIdx.x;
+    if (idx >= ((size_t) nmc * 3 << maxl)) return;
+    const unsigned p = (unsigned) (idx & ((1u << maxl) - 1));
+    const unsigned m = (unsigned) ((idx >> maxl) % nmc), b = (unsigned) ((idx >> maxl) / nmc);
+    const DecMc mc = mcs[m];
+    unsigned long long base;
+    long long npix, di, fi, bi;
+    if (!dec_mc420_item(&mc, b, p, W, H, &base, &npix, &di, &fi, &bi)) return;
+    if (di < 0 || di >= npix) return;
+    int add;
+    if (mc.type == FA_MV_FORWARD) { if (fi < 0 || fi >= npix) return; add = past[base + fi]; }
+    else if (mc.type == FA_MV_BACKWARD) { if (bi < 0 || bi >= npix) return; add = future[base + bi]; }
+    else {
+        if (fi < 0 || fi >= npix || bi < 0 || bi >= npix) return;
+        add = ((int) past[base + fi] + (int) future[base + bi]) >> 1;
+    }
+    dec_add16(planes + base, (size_t) di, (unsigned) add & 0xffffu);
+}
+
+/* dec_clip_chroma_kernel for a 4:2:0 frame: the two planes of cpix = (W >> 1) * (H >> 1) values behind the npix of Y
+ * (restore_mc shifts its count by 2, codec/motion.c:195-224) */
+__global__ void __launch_bounds__(256) dec_clip_chroma420_kernel(int16_t *__restrict__ planes, size_t npix, size_t cpix)
+{
+    const size_t i = (size_t) blockIdx.x * 256 + threadIdx.x;
+    if (i >= 2 * cpix) return;
+    int v = planes[npix + i] >> 4;
+    v = v < -128 ? -128 : v > 127 ? 127 : v;
+    planes[npix + i] = (int16_t) (v * 16);
+}
+
 static int16_t dec_fixed_of(float v) { return (int16_t) ((int) ((double) (v * 8) + .5) * 2); }
 
 /* one plane that is smoothed: the checked border list against it (packed into the flight's block, never uploaded itself),
@@ -248,6 +295,11 @@ struct DecFrame {                     /* one frame in flight */
     size_t thumb_off = 0, thumb_bytes = 0;
     unsigned tw = 0, th = 0;
     bool own_planes = false;          /* planes is an allocation of its own (kept on the device) */
+    int16_t *shown = nullptr;         /* a frame that is smoothed AND kept (fa_dec_job.from_stream): the copy in the arena that is smoothed
+                                       * and consumed, while `planes' stays as the next frame is predicted from it (get_next_frame
+                                       * smooths a clone, codec/decoder.c:372-378); nullptr: the planes themselves */
+    size_t shown_off = 0;             /* ... from the frame's scratch */
+    bool shown_copy = false;
     unsigned long long bytes = 0;     /* algorithmic: 2 bytes per pixel written and per (pixel, term) read */
     size_t scratch_off = 0;           /* dec_flight_prepare: its scratch_b bytes of the flight's arena */
     unsigned slot = 0;                /* dec_flight_measure: its place in the result array of the measuring launch */
@@ -256,6 +308,9 @@ struct DecFrame {                     /* one frame in flight */
     SmPlan sm, tsm;                   /* the frame's Y plane at the size shown; the Y plane of its thumbnail */
     int sm_is = 0, sm_inegs = 0;      /* the factors */
 };
+
+/* the planes the smoothing step and the consumers take */
+static int16_t *dec_shown(const DecFrame &D) { return D.shown ? D.shown : D.planes; }
 
 static void dec_fail(fa_dec_job *j, const char *msg) { snprintf(j->errmsg, sizeof j->errmsg, "%s", msg); j->out = nullptr; }
 
@@ -285,8 +340,9 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
     const unsigned S = w->states, bands = j->color ? 3 : 1;
     unsigned root[3] = { 0, 0, 0 }, maxl = 0, W = j->width, H = j->height;
     const int mag = j->magnify;
-    if (mag && j->frame_type != FA_I_FRAME) { dec_fail(j, "device decoder: magnification of intra frames only (the vectors of a P/B frame are not scaled)"); return false; }
-    if (j->format_420 && (j->frame_type != FA_I_FRAME || j->keep_dev)) { dec_fail(j, "device decoder: 4:2:0 for intra frames only (restore_mc scales the vectors per band)"); return false; }
+    const bool walked = j->from_stream != 0;        /* a frame of a stream that is walked: its references live at the size and in the format shown */
+    if (mag && j->frame_type != FA_I_FRAME && !walked) { dec_fail(j, "device decoder: magnification of intra frames only (the vectors of a P/B frame are not scaled)"); return false; }
+    if (j->format_420 && (j->frame_type != FA_I_FRAME || j->keep_dev) && !walked) { dec_fail(j, "device decoder: 4:2:0 for intra frames only (restore_mc scales the vectors per band)"); return false; }
     if (mag && !fiasco_amd_magnified_size(j->width, j->height, mag, &W, &H)) {
         snprintf(j->errmsg, sizeof j->errmsg, "device decoder: magnification %d is out of range for a frame of %u x %u pixels", mag, j->width, j->height);
         j->out = nullptr; return false;
@@ -295,24 +351,54 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
         const unsigned r0 = (unsigned) FA_TREE(w, w->root_state, 0), r1 = (unsigned) FA_TREE(w, w->root_state, 1);
         root[FA_Y] = (unsigned) FA_TREE(w, r0, 0); root[FA_CB] = (unsigned) FA_TREE(w, r0, 1); root[FA_CR] = (unsigned) FA_TREE(w, r1, 0);
     } else root[0] = w->root_state;
+    bool any_edge = false;
     for (unsigned s = w->basis_states; s < S; s++)
-        if (FA_INTO(w, s, 0, 0) != FA_NO_EDGE || FA_INTO(w, s, 1, 0) != FA_NO_EDGE)
+        if (FA_INTO(w, s, 0, 0) != FA_NO_EDGE || FA_INTO(w, s, 1, 0) != FA_NO_EDGE) {
+            any_edge = true;
             if (w->level_of_state[s] > maxl) maxl = w->level_of_state[s];
+        }
+    /* A P/B frame of a walked stream is a residual: it may hold no linear combination at all, or none in a band.
+     * decode_image leaves zeros there (no state at the level shown), and zeros are what the prediction is added to: such a
+     * frame gets no tops for the band, where an intra frame of the batch entries is refused as degenerate */
+    const bool residual = walked && j->frame_type != FA_I_FRAME;
+    const unsigned NO_TOPS = 255;                   /* no state has that level */
+    unsigned top_level[2] = { maxl, maxl };          /* the coded level of the states shown: Y (gray), chroma */
+    if (residual && !any_edge) top_level[0] = top_level[1] = NO_TOPS;
     if (maxl > 24) { dec_fail(j, "device decoder: level of the linear combinations out of range"); return false; }
     /* the level shown (the header): the states of level `maxl' at level maxl + 2 mag.  Blocks smaller than the reduction
      * -- the reference clamps their level at 0 and several land on one pixel -- are refused, not reproduced */
-    if (mag < 0 && maxl < 2u * (unsigned) -mag) { dec_fail(j, "device decoder: the blocks of the frame are smaller than the reduction (level of the linear combinations below twice the reduction)"); return false; }
-    unsigned shown = (unsigned) ((int) maxl + 2 * mag);
+    if (mag < 0 && maxl < 2u * (unsigned) -mag && !(residual && !any_edge)) { dec_fail(j, "device decoder: the blocks of the frame are smaller than the reduction (level of the linear combinations below twice the reduction)"); return false; }
+    unsigned shown = residual && !any_edge ? 0u : (unsigned) ((int) maxl + 2 * mag);
     /* 4:2:0: the level shown and the coded levels of the states the planes are made of come from fa_420_plan_of, which
      * also refuses what is not reproduced (fa_batch_decode.c) */
     fa_420_plan plan = { 0, 0, 0 };
-    if (j->format_420) {
+    if (j->format_420 && residual) {
+        /* fa_420_plan_of without its refusals of what comes out zero: per band group the largest level with a linear
+         * combination, shown at + 2 mag (Y) and + 2 mag - 2 (chroma); the largest of those is the level of every top */
+        if (!j->color) { dec_fail(j, "device decoder: 4:2:0: a gray frame has no chroma bands"); return false; }
+        int lc[2] = { -1, -1 }, top = -1;
+        const int shift[2] = { 2 * mag, 2 * mag - 2 };
+        for (unsigned s = w->basis_states; s < S; s++) {
+            if (s == w->root_state || s == (unsigned) FA_TREE(w, w->root_state, 0) || s == (unsigned) FA_TREE(w, w->root_state, 1)) continue;
+            if (FA_INTO(w, s, 0, 0) == FA_NO_EDGE && FA_INTO(w, s, 1, 0) == FA_NO_EDGE) continue;
+            const int g = s > root[FA_Y];
+            if ((int) w->level_of_state[s] > lc[g]) lc[g] = w->level_of_state[s];
+        }
+        for (int g = 0; g < 2; g++) {
+            if (lc[g] < 0) continue;
+            if (lc[g] + shift[g] < 0) { dec_fail(j, "device decoder: 4:2:0: the blocks of the frame are smaller than the reduction"); return false; }
+            if (lc[g] + shift[g] > top) top = lc[g] + shift[g];
+        }
+        shown = top < 0 ? 0u : (unsigned) top;
+        for (int g = 0; g < 2; g++) top_level[g] = top < 0 || top - shift[g] < 0 ? NO_TOPS : (unsigned) (top - shift[g]);
+    } else if (j->format_420) {
         char why[160];
         if (!fa_420_plan_of(w, j->color, mag, &plan, why, sizeof why)) {
             snprintf(j->errmsg, sizeof j->errmsg, "device decoder: %.140s", why);
             j->out = nullptr; return false;
         }
         shown = plan.max_level;
+        top_level[0] = plan.y_level; top_level[1] = plan.c_level;
     }
     if (shown > 24) { dec_fail(j, "device decoder: level of the magnified linear combinations out of range (above 24)"); return false; }
     /* host side of the arithmetic: nodes with integer weights, the lists of blocks */
@@ -322,7 +408,7 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
         if (j->color && (s == w->root_state || s == (unsigned) FA_TREE(w, w->root_state, 0) || s == (unsigned) FA_TREE(w, w->root_state, 1)))
             continue;
         const int band = !j->color || s <= root[FA_Y] ? 0 : s > root[FA_CB] ? FA_CR : FA_CB;
-        if (w->level_of_state[s] == (!j->format_420 ? maxl : band ? plan.c_level : plan.y_level)) {
+        if (w->level_of_state[s] == top_level[j->format_420 && band ? 1 : 0]) {
             const int shift = j->format_420 && band ? mag - 1 : mag;       /* enlarge_image: one step more behind the Y root */
             DecTop t;
             t.state = (int) s; t.x0 = w->x[s * 2]; t.y0 = w->y[s * 2];
@@ -343,10 +429,12 @@ static bool dec_prepare(fa_dec_job *j, DecFrame &D)
                     dec_fail(j, "device decoder: motion vector without its reference frame"); return false;
                 }
                 DecMc m;
-                m.x0 = w->x[s * 2 + l]; m.y0 = w->y[s * 2 + l]; m.level = (int) level; m.type = mv->type;
-                m.fx = mv->fx; m.fy = mv->fy; m.bx = mv->bx; m.by = mv->by;
+                if (!dec_mc_scaled(&m, w->x[s * 2 + l], w->y[s * 2 + l], (int) level, mv->type, mv->fx, mv->fy, mv->bx, mv->by, mag)) {
+                    dec_fail(j, "device decoder: the motion blocks of the frame are smaller than the reduction (level of a block below twice the reduction)");
+                    return false;
+                }
                 mcs.push_back(m);
-                if (level > mc_maxl) mc_maxl = level;
+                if ((unsigned) m.level > mc_maxl) mc_maxl = (unsigned) m.level;
             }
     }
     /* edge lists of more than six entries (long bases): behind the nodes */
@@ -418,7 +506,8 @@ static bool dec_run(fa_dec_job *j, DecFrame &D, char *scratch, hipStream_t strea
  * every P/B frame: the clipping of the chroma planes too when no block moved */
 static bool dec_run_mc(fa_dec_job *j, DecFrame &D, hipStream_t stream, int cur_dev)
 {
-    const unsigned bands = j->color ? 3 : 1, W = j->width, H = j->height;
+    /* the size shown: the coded one but for a frame of a stream that is walked at a magnification */
+    const unsigned bands = j->color ? 3 : 1, W = D.W, H = D.H;
     const size_t npix = (size_t) W * H;
     const int16_t *refs[2] = { nullptr, nullptr };
     const fa_image *src[2] = { j->past, j->future };
@@ -429,18 +518,24 @@ static bool dec_run_mc(fa_dec_job *j, DecFrame &D, hipStream_t stream, int cur_d
             dec_fail(j, "device decoder: reference frame of another size"); ok = false; break;
         }
         if (src[r]->dev && src[r]->dev_id == cur_dev) { refs[r] = (const int16_t *) src[r]->dev; continue; }
+        /* the frames of a walked stream stay on one share; their host planes, where they have any, may be 4:2:0 */
+        if (D.c420 || !src[r]->pixels[0]) { dec_fail(j, "device decoder: the reference frame does not lie on the device the frame is decoded on"); ok = false; break; }
         int16_t *&up = r ? D.future : D.past;
         if (hipMalloc((void **) &up, D.plane_bytes) != hipSuccess) { (void) hipGetLastError(); dec_fail(j, "device decoder: out of device memory"); ok = false; break; }
         for (unsigned b = 0; b < bands && ok; b++)
             ok = hipMemcpyAsync(up + b * npix, src[r]->pixels[b], npix * 2, hipMemcpyHostToDevice, stream) == hipSuccess;
         refs[r] = up;
     }
+    const size_t cpix = (size_t) (W >> 1) * (H >> 1);
     if (ok && D.nmcs) {
         const size_t n = ((size_t) D.nmcs * bands) << D.mc_maxl;
-        dec_mc_kernel<<<dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream>>>((const DecMc *) (D.base + D.nodes_b + D.tops_b), D.nmcs,
-                                                                                   D.mc_maxl, D.planes, refs[0], refs[1], W, H, bands);
+        const DecMc *mcs = (const DecMc *) (D.base + D.nodes_b + D.tops_b);
+        if (D.c420) dec_mc420_kernel<<<dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream>>>(mcs, D.nmcs, D.mc_maxl, D.planes, refs[0], refs[1], W, H);
+        else dec_mc_kernel<<<dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, stream>>>(mcs, D.nmcs, D.mc_maxl, D.planes, refs[0], refs[1], W, H, bands);
     }
-    if (ok && j->color)
+    if (ok && j->color && D.c420) {
+        if (cpix) dec_clip_chroma420_kernel<<<dim3((unsigned) ((2 * cpix + 255) / 256)), dim3(256), 0, stream>>>(D.planes, npix, cpix);
+    } else if (ok && j->color)
         dec_clip_chroma_kernel<<<dim3((unsigned) ((2 * npix + 255) / 256)), dim3(256), 0, stream>>>(D.planes, npix);
     if (ok && hipGetLastError() != hipSuccess) ok = false;
     if (!ok && !j->errmsg[0]) dec_fail(j, "device decoder: HIP error");
@@ -542,6 +637,7 @@ static bool dec_smooth_plan(fa_dec_job *j, int magnify, unsigned W, unsigned H, 
 {
     /* a 4:2:0 frame: the list of the automaton enlarge_image has shifted for that format (fa_smoothing_borders_420) */
     auto list = [&](fiasco_amd_border *out, unsigned cap) {
+        if (c420 && j->from_stream && j->frame_type != FA_I_FRAME) return fa_smoothing_borders_420_residual(j->wfa, j->width, j->height, j->color, magnify, out, cap);
         return c420 ? fa_smoothing_borders_420(j->wfa, j->width, j->height, j->color, magnify, out, cap)
                     : fa_smoothing_borders_magnified(j->wfa, j->width, j->height, j->color, magnify, out, cap);
     };
@@ -572,10 +668,13 @@ static bool dec_smooth_prepare(DecShare &S, unsigned job, DecFrame &D)
     fa_dec_job *j = &S.jobs[job];
     if (!j->smoothing) return true;
     if (j->smoothing < 0 || j->smoothing > 100) { dec_fail(j, "device decoder: smoothing out of range (1 .. 100 per cent; the header's value is the batch entries' to look up)"); return false; }
-    if (j->frame_type != FA_I_FRAME) { dec_fail(j, "device decoder: smoothing of intra frames only"); return false; }
+    /* a P/B frame of a walked stream is smoothed along the borders of its own automaton, as get_next_frame does it */
+    if (j->frame_type != FA_I_FRAME && !j->from_stream) { dec_fail(j, "device decoder: smoothing of intra frames only"); return false; }
     if (!sm_factors(j->smoothing, &D.sm_is, &D.sm_inegs)) return true;       /* the reference smooths nothing */
     const bool consumed = !S.out || S.ds || S.images || S.out->target[job].data;
     if (consumed && !dec_smooth_plan(j, j->magnify, D.W, D.H, D.sm, D.c420)) return false;
+    /* smoothed and kept: the copy that is smoothed and consumed, behind the frame's scratch */
+    if (D.sm.np && D.own_planes && j->from_stream) { D.shown_copy = true; D.shown_off = D.scratch_b; D.scratch_b += D.plane_bytes; }
     if (D.thumb_bytes && !dec_smooth_plan(j, -(int) S.out->reduce, D.tw, D.th, D.tsm)) return false;
     return true;
 }
@@ -718,6 +817,13 @@ static void dec_flight_smooth(DecShare &S, DecFlight &F, bool thumbs)
     const size_t tab_off = thumbs ? F.tsmd_off : F.smd_off;
     bool ok = thumbs || F.smhost.empty() || F.alive.empty()
               || hipMemcpyAsync(S.arena + F.sm_first, F.smhost.data(), F.smhost.size(), hipMemcpyHostToDevice, S.stream) == hipSuccess;
+    /* a frame that is smoothed and kept: from here on its copy, the kept planes stay as the kernels above left them */
+    for (size_t k : F.alive) {
+        DecFrame &D = F.fr[k];
+        if (thumbs || !D.shown_copy || D.shown) continue;
+        D.shown = (int16_t *) (S.arena + D.scratch_off + D.shown_off);
+        ok = ok && hipMemcpyAsync(D.shown, D.planes, D.vals * 2, hipMemcpyDeviceToDevice, S.stream) == hipSuccess;
+    }
     unsigned passes = 0;
     unsigned long long fused_most = 0;
     std::vector<const SmPlan *> per;                    /* the planes of the per-pass launches: the first per.size() descriptors */
@@ -727,7 +833,7 @@ static void dec_flight_smooth(DecShare &S, DecFlight &F, bool thumbs)
             const SmPlan &P = thumbs ? D.tsm : D.sm;
             if (!P.np || P.fused != (fused != 0)) continue;
             tab.emplace_back();
-            sm_describe(tab.back(), thumbs ? D.thumb : D.planes, thumbs ? D.tw : D.W, thumbs ? D.th : D.H, S.arena + P.off, (unsigned) P.borders.size(), P.np,
+            sm_describe(tab.back(), thumbs ? D.thumb : dec_shown(D), thumbs ? D.tw : D.W, thumbs ? D.th : D.H, S.arena + P.off, (unsigned) P.borders.size(), P.np,
                         D.sm_is, D.sm_inegs);
             if (!fused) { per.push_back(&P); if (P.np > passes) passes = P.np; }
             else for (unsigned p = 0; p < P.np; p++)
@@ -819,16 +925,16 @@ static void dec_flight_write(DecShare &S, DecFlight &F)
         if (!S.out->target[F.job[k]].data) continue;            /* measured only, the thumbnail only, or not this frame */
         if (S.out->t420 && S.out->render) {
             F.rd4tab.emplace_back();
-            rd4_describe_packed(F.rd4tab.back(), F.fr[k].planes, S.out->t420[F.job[k]], total);
+            rd4_describe_packed(F.rd4tab.back(), dec_shown(F.fr[k]), S.out->t420[F.job[k]], total);
             continue;
         }
         if (S.out->t420) {
             F.y4tab.emplace_back();
-            y4_describe_packed(F.y4tab.back(), F.fr[k].planes, S.out->t420[F.job[k]], total);
+            y4_describe_packed(F.y4tab.back(), dec_shown(F.fr[k]), S.out->t420[F.job[k]], total);
             continue;
         }
         F.octab.emplace_back();
-        oc_describe(F.octab.back(), F.fr[k].planes, S.out->target[F.job[k]], total);
+        oc_describe(F.octab.back(), dec_shown(F.fr[k]), S.out->target[F.job[k]], total);
     }
     if (F.octab.empty() && F.thoctab.empty() && F.y4tab.empty() && F.rd4tab.empty()) return;
     bool ok = hipStreamWaitEvent(S.stream, S.out->ready, 0) == hipSuccess;
@@ -901,6 +1007,15 @@ static void dec_flight_results(DecShare &S, DecFlight &F)
             S.ds->done[i] = 1;
         }
         if ((S.images || (!S.out && !S.ds)) && !dec_download(S, j, D)) continue;
+        if (j->from_stream && !j->out) {
+            /* a frame of a walked stream whose consumers are on the device: an image without host planes says that it is
+             * decoded, and holds the planes the next frame is predicted from */
+            fa_image *im = (fa_image *) calloc(1, sizeof *im);
+            if (!im) { dec_fail(j, "Out of memory!"); continue; }
+            im->width = D.W; im->height = D.H; im->color = j->color;
+            if (D.own_planes) { im->dev = D.planes; im->dev_id = S.device; D.planes = nullptr; }
+            j->out = im; j->out_420 = D.c420;
+        }
         frames++;
         bytes += D.bytes + (S.ds ? 4 * vals : 0) + (written ? 3 * vals : 0) + 7 * tvals + (D.sm.np ? 8 * D.sm.pairs : 0) + (D.thumb && D.tsm.np ? 8 * D.tsm.pairs : 0);
     }

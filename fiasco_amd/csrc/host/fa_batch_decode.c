@@ -440,14 +440,17 @@ int fa_420_plan_of(const fa_wfa *w, int color, int magnify, fa_420_plan *plan, c
 
 /* the list smooth_image walks on the automaton enlarge_image has shifted for FORMAT_4_2_0 */
 static unsigned borders_420(const fa_wfa *w, unsigned width, unsigned height, int color, int magnify, fiasco_amd_border *out, unsigned cap,
-                            const char *who)
+                            const char *who, int intra)
 {
     unsigned mw = width, mh = height, low = 0, n;
     int low_mag = 0;
     fa_420_plan plan;
     char msg[200];
     if (magnify && !fiasco_amd_magnified_size(width, height, magnify, &mw, &mh)) return 0;
-    if (!fa_420_plan_of(w, color, magnify, &plan, msg, sizeof msg)) { fa_set_error("%s: %s", who, msg); return 0; }
+    /* the plan refuses what decode_image leaves zero; a P/B frame whose residual lacks a band is such a frame by right
+     * (fa_smoothing_borders_420_residual): its borders are those of its partition all the same */
+    if (!color) { fa_set_error("%s: 4:2:0: a gray frame has no chroma bands", who); return 0; }
+    if (intra && !fa_420_plan_of(w, color, magnify, &plan, msg, sizeof msg)) { fa_set_error("%s: %s", who, msg); return 0; }
     if (magnify > 8) { fa_set_error("%s: magnification %d: the borders of the frame do not fit 16-bit coordinates", who, magnify); return 0; }
     n = borders_at(w, mw, mh, color, magnify, magnify - 1, out, cap, &low, &low_mag);
     if (low) {
@@ -460,7 +463,12 @@ static unsigned borders_420(const fa_wfa *w, unsigned width, unsigned height, in
 
 unsigned fa_smoothing_borders_420(const fa_wfa *w, unsigned width, unsigned height, int color, int magnify, fiasco_amd_border *out, unsigned cap)
 {
-    return borders_420(w, width, height, color, magnify, out, cap, "smoothing borders");
+    return borders_420(w, width, height, color, magnify, out, cap, "smoothing borders", 1);
+}
+
+unsigned fa_smoothing_borders_420_residual(const fa_wfa *w, unsigned width, unsigned height, int color, int magnify, fiasco_amd_border *out, unsigned cap)
+{
+    return borders_420(w, width, height, color, magnify, out, cap, "smoothing borders", 0);
 }
 
 int fiasco_amd_batch_smoothing_borders_420(const fiasco_amd_batch_t *b, unsigned i, int magnify, fiasco_amd_border *out, unsigned cap)
@@ -469,7 +477,7 @@ int fiasco_amd_batch_smoothing_borders_420(const fiasco_amd_batch_t *b, unsigned
     char who[80];
     if (!job) return 0;
     snprintf(who, sizeof who, "fiasco_amd_batch_smoothing_borders_420: frame %u", i);
-    return (int) borders_420(job->wfa, job->image->width, job->image->height, job->image->color, magnify, out, cap, who);
+    return (int) borders_420(job->wfa, job->image->width, job->image->height, job->image->color, magnify, out, cap, who, 1);
 }
 
 int fiasco_amd_batch_decode_planes_420(const fiasco_amd_batch_t *b, unsigned i, int magnify, int16_t *out)

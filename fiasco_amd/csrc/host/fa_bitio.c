@@ -1,5 +1,5 @@
 /*
- *  fa_bitio.c -- MSB-first bit writer, memory backed.
+ *  fa_bitio.c -- MSB-first bit writer and bit reader, memory backed.
  *
  *  Bit-exact with reference lib/bit-io.c:148-329 (write side): the write cursor starts
  *  with bitpos = 8 (so an align before the first bit emits a whole zero byte), align pads
@@ -87,4 +87,51 @@ void fa_bw_bincode(fa_bitw *b, unsigned value, unsigned maxval)
     unsigned r = (maxval + 1) % (1u << k);
     if (value < maxval + 1 - 2 * r) fa_bw_put_bits(b, value, k);
     else fa_bw_put_bits(b, value + maxval + 1 - 2 * r, k + 1);
+}
+
+/* ------------------------------------------------------------------ the read side (lib/bit-io.c:192-262)
+ *
+ * The read cursor starts on a byte boundary, an align skips to the next one.  Every read is checked against the
+ * buffer: a bit behind its end reads as 0 and sets `over', which the caller turns into its refusal. */
+
+void fa_br_init(fa_bitr *b, const unsigned char *buf, size_t len)
+{
+    b->buf = buf; b->len = len; b->pos = 0; b->over = 0;
+}
+
+unsigned fa_br_get_bit(fa_bitr *b)
+{
+    unsigned v;
+    if ((b->pos >> 3) >= b->len) { b->over = 1; return 0; }
+    v = (b->buf[b->pos >> 3] >> (7 - (b->pos & 7))) & 1u;
+    b->pos++;
+    return v;
+}
+
+unsigned fa_br_get_bits(fa_bitr *b, unsigned n)
+{
+    unsigned v = 0;
+    while (n--) v = (v << 1) | fa_br_get_bit(b);
+    return v;
+}
+
+void fa_br_align(fa_bitr *b) { b->pos = (b->pos + 7) & ~(size_t) 7; }
+
+/* the unary part is bounded: no field of a stream reaches 2^24 */
+unsigned fa_br_rice(fa_bitr *b, unsigned k)
+{
+    unsigned u = 0;
+    while (fa_br_get_bit(b))
+        if (++u > (1u << 24 >> k)) { b->over = 1; return 0; }
+    return (u << k) | fa_br_get_bits(b, k);
+}
+
+unsigned fa_br_bincode(fa_bitr *b, unsigned maxval)
+{
+    unsigned k = ilog2(maxval + 1);
+    unsigned r = (maxval + 1) % (1u << k);
+    unsigned value = fa_br_get_bits(b, k);
+    if (value < maxval + 1 - 2 * r) return value;
+    value = (value << 1) | fa_br_get_bit(b);
+    return value - maxval - 1 + 2 * r;
 }

@@ -68,6 +68,7 @@ typedef struct fa_rpf {
 } fa_rpf;
 void fa_rpf_init(fa_rpf *r, unsigned mantissa, int range_e);
 int  fa_rtob(float f, const fa_rpf *r);   /* used by the stream writer (weights) */
+float fa_btor(int binary, const fa_rpf *r); /* used by the stream reader: 0 <= binary < 2^(mantissa_bits + 1) */
 
 /* ---------------- options (reference codec/options.h:20-65) ---------------- */
 typedef struct fa_options {
@@ -216,6 +217,14 @@ typedef struct fa_dec_job {
                                            * out then has Y at full size and, at the BEGINNING of pixels[1] and pixels[2], the packed
                                            * chroma planes of (width >> 1) x (height >> 1) values.  The test oracle does not know the field */
     int             out_420;              /* out: 1 where `out' is such a frame: callers check it as they check the size */
+    int             from_stream;          /* in: a frame of a stream that is walked (fa_stream.c), whose reference frames live at the
+                                           * magnification and in the format shown, as get_next_frame keeps them
+                                           * (codec/decoder.c:160-410).  Lifts three refusals for P/B frames: magnify (the blocks and
+                                           * vectors as enlarge_image leaves them), format_420 with keep_dev (dec_mc420_kernel; past and
+                                           * future are 4:2:0 frames of the size shown) and smoothing (a frame that is smoothed AND kept
+                                           * is smoothed in a copy: the next frame is predicted from the unsmoothed one).  The test
+                                           * oracle does not know the field.  (Everything that fills a job is compiled against this
+                                           * header and fills it by name; `smoothing' stays the last field) */
     int             smoothing;            /* in: blend the Y plane along the borders of the partition before any consumer sees the
                                            * frame (smooth_image, codec/decoder.c:674-768; csrc/hip/smooth.inc): 0 nothing, 1 .. 100
                                            * that percentage (dfiasco -s N); -1 stands for the value of the frame's stream header
@@ -243,6 +252,10 @@ int fa_420_plan_of(const fa_wfa *w, int color, int magnify, fa_420_plan *plan, c
  * size shown (width x height: the coded size).  0 + message as fa_smoothing_borders_magnified */
 unsigned fa_smoothing_borders_420(const fa_wfa *w, unsigned width, unsigned height, int color, int magnify, fiasco_amd_border *out,
                                   unsigned cap);
+/* ... of a P/B frame of a stream that is walked: the same list without the plan's refusals -- a residual may lack a band,
+ * or every linear combination, and decode_image's zeros are then the frame's */
+unsigned fa_smoothing_borders_420_residual(const fa_wfa *w, unsigned width, unsigned height, int color, int magnify, fiasco_amd_border *out,
+                                           unsigned cap);
 void fa_core_release_dev(void *dev, int dev_id);
 
 /* ---------------- stream info (reference codec/wfa.h:65-110 wfa_info_t) ----------- */
@@ -382,11 +395,55 @@ size_t fa_bw_finish(fa_bitw *b);   /* number of bytes the reference would write 
 void fa_bw_rice(fa_bitw *b, unsigned value, unsigned k);
 void fa_bw_bincode(fa_bitw *b, unsigned value, unsigned maxval);
 
+/* ---------------- bit reader (reference lib/bit-io.c, memory backed, bounds-checked) -------------- */
+typedef struct fa_bitr {
+    const unsigned char *buf;
+    size_t   len;
+    size_t   pos;        /* bits consumed */
+    int      over;       /* a read went behind the end of the buffer (it gave 0) */
+} fa_bitr;
+void fa_br_init(fa_bitr *b, const unsigned char *buf, size_t len);
+unsigned fa_br_get_bit(fa_bitr *b);
+unsigned fa_br_get_bits(fa_bitr *b, unsigned n);
+void fa_br_align(fa_bitr *b);
+unsigned fa_br_rice(fa_bitr *b, unsigned k);
+unsigned fa_br_bincode(fa_bitr *b, unsigned maxval);
+
 /* ---------------- .fco writer (reference output/ directory) ---------------- */
 void fa_write_header(const fa_info *wi, fa_bitw *out);
 /* returns 1 ok, 0 on the reference's "total != ..." sanity error */
 int  fa_write_frame(const fa_wfa *wfa, const fa_info *wi, int frame_type, unsigned number,
                     int prediction, int normal_domains, int delta_domains, fa_bitw *out);
+/* ---------------- .fco reader (reference input/ directory; fa_reader.c) ---------------- */
+/* The header of the stream in `in' (input/read.c:57-217): *wi filled, the cursor on the first frame.  0 + message */
+int  fa_read_header(fa_bitr *in, const char *name, fa_info *wi);
+/* The next frame (read_next_wfa, input/read.c:344-451) into an automaton of its own; basis: the automaton
+ * fa_load_basis made of the header's basis, copied in front; *number: the display number; flags[3]: prediction,
+ * use_normal, use_delta as fa_write_frame takes them.  Everything a decoder follows is validated: NULL + message
+ * for a stream that fails */
+fa_wfa *fa_read_frame(fa_bitr *in, const fa_info *wi, const fa_wfa *basis, unsigned *number, int flags[3]);
+
+/* ---------------- a stream that was read (include/libfiasco_amd_stream.h; fa_stream.c) ---------------- */
+struct fiasco_amd_stream;
+const fa_info *fa_stream_info(const struct fiasco_amd_stream *s);
+/* The walk of get_next_frame (codec/decoder.c:160-410) over display frames first .. first + count - 1 and every frame
+ * they are predicted from, in coding order: frames whose references are decoded go to run() together, as jobs of the
+ * decoder with from_stream set (a run of B frames between two P frames: one call where B_as_past_ref is 0, else one
+ * frame per call, as each B frame is then the past of the next; a chain of P frames: one frame per
+ * call).  display[i]: the display number of jobs[i]; wanted[i]: inside the range asked for -- such a job is smoothed
+ * (smoothing resolved: 0 .. 100) and run() attaches its consumer; the others are decoded for reference only.  run()
+ * returns after the frames are decoded: a job that succeeded has `out' (an image that holds the device planes where
+ * keep_dev is set), a job that failed has its errmsg.  After the walk: result[d - first] holds the image of wanted
+ * frame d where keep_images is set (the caller frees it), and errs[d - first] the message of a frame that failed or
+ * whose reference did.  mask: NULL, or [count]: 0 = this frame of the range is not wanted.  Returns the number of wanted
+ * frames decoded */
+typedef void (*fa_stream_run)(void *ctx, unsigned n, fa_dec_job *jobs, const unsigned *display, const uint8_t *wanted);
+int fa_stream_walk(const struct fiasco_amd_stream *s, const char *who, unsigned first, unsigned count, const uint8_t *mask, int magnify, int smoothing,
+                   int format_420, fa_stream_run run, void *ctx, int keep_images, fa_image **result, char (*errs)[160]);
+
+/* MPEG's code of a vector component, {code, length}, index = component + search range (fa_writer.c) */
+extern const unsigned short fa_mv_code[33][2];
+
 /* stable (count desc, state asc) top-n hits, reference codec/wfalib.c:182-231 */
 int16_t *fa_compute_hits(unsigned from, unsigned to, unsigned n, const fa_wfa *wfa);
 

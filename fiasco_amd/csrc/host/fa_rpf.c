@@ -54,3 +54,12 @@ int fa_rtob(float f, const fa_rpf *r)
     if (mant >= (1u << r->mantissa_bits)) return sign;      /* overflow: +-1.0 */
     return (int) (((mant & ((1u << r->mantissa_bits) - 1)) << 1) | (unsigned) sign);
 }
+
+/* btor, lib/rpf.c:113-169: mantissa / 2^mantissa_bits with the sign in bit 0; a mantissa of 0 stands for +-1.0 */
+float fa_btor(int binary, const fa_rpf *r)
+{
+    const unsigned mant = ((unsigned) binary >> 1) & ((1u << r->mantissa_bits) - 1);
+    float v = mant ? (float) mant / (float) (1u << r->mantissa_bits) : 1.0f;
+    if (binary & 1) v = -v;
+    return v * r->range;
+}

@@ -572,7 +572,7 @@ static int write_nd(const fa_wfa *wfa, const fa_info *wi, fa_bitw *out)
 
 /* MPEG's Huffman code of a vector component: {code, length}, index = component + search range
  * (codec/mwfa.c:40-50) */
-static const unsigned short mv_code[33][2] = {
+const unsigned short fa_mv_code[33][2] = {
     {0x19, 11}, {0x1b, 11}, {0x1d, 11}, {0x1f, 11}, {0x21, 11}, {0x23, 11}, {0x13, 10}, {0x15, 10},
     {0x17, 10}, {0x7, 8}, {0x9, 8}, {0xb, 8}, {0x7, 7}, {0x3, 5}, {0x3, 4}, {0x3, 3}, {0x1, 1},
     {0x2, 3}, {0x2, 4}, {0x2, 5}, {0x6, 7}, {0xa, 8}, {0x8, 8}, {0x6, 8}, {0x16, 10}, {0x14, 10},
@@ -580,7 +580,7 @@ static const unsigned short mv_code[33][2] = {
 
 static void put_mv(fa_bitw *out, int v, unsigned sr)
 {
-    fa_bw_put_bits(out, mv_code[v + (int) sr][0], mv_code[v + (int) sr][1]);
+    fa_bw_put_bits(out, fa_mv_code[v + (int) sr][0], fa_mv_code[v + (int) sr][1]);
 }
 
 static int write_mc(int frame_type, const fa_wfa *wfa, const fa_info *wi, fa_bitw *out)
