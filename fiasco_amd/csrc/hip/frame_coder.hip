@@ -18,7 +18,9 @@
  *                                  codec/prediction.c, codec/mwfa.c
  *    fc_models.inc     snapshot slots, generic models (FC_GM)
  *                                  codec/domain-pool.c:621-852, codec/coeff.c:215-267
- *    mp_device.inc     matching pursuit (and mp_reg.inc and mp_roles.h, which it includes)
+ *    mp_device.inc     matching pursuit: rate terms, table pass, the scans with scratch in HBM, op_approx as a
+ *                      sequence of steps (and what it includes: mp_roles.h, the roles of the table pass; mp_step.inc,
+ *                      the pieces of a step every scan shares; mp_reg.inc, the register scan and the short list scan)
  *                                  codec/approx.c:74-271,317-699 (domain-parallel, see below)
  *    fc_serial.inc     partition search: serial state machine, lane 0, explicit LDS stack; bands
  *                                  codec/subdivide.c:60-502, codec/coder.c:738-833, codec/bintree.c:35-73

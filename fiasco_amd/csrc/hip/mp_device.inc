@@ -773,6 +773,7 @@ __device__ __forceinline__ void lds_barrier()
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+#include "mp_step.inc"                /* what every scan does with a candidate: accept rule, record, commit, update */
 #include "mp_reg.inc"                 /* register-resident scan and the chroma list scan */
 
 /* general scan: per-candidate scratch in HBM (any number of states, up to MAXEDGES vectors).
@@ -783,7 +784,6 @@ __device__ __noinline__ void mp_steps_global(DevFrame &F, Sh &sh, int q, float s
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, P = F.P;
     MPState &mp = sh.mp;
     const int S = sh.states;
-    /* general path: scratch in HBM (any number of states, up to MAXEDGES vectors) */
     const int nblk = (S + 63) >> 6;
     constexpr int U = 4;                 /* candidates per lane per pass: loads of all U in flight */
     unsigned long long tA = 0, tB = 0, tmark = wall_clock64();
@@ -846,13 +846,8 @@ __device__ __noinline__ void mp_steps_global(DevFrame &F, Sh &sh, int q, float s
 #pragma unroll
                     for (int u = 0; u < U; u++) {
                         if (us[u]) continue;
-                        float t = g[u];
-#pragma unroll
-                        for (int k = 0; k < MAXED - 1; k++)
-                            if (k < nv) t -= ip[u][k] / novk[k] * selk[k];
+                        const float t = mp_orthogonalize<MAXED - 1>(g[u], ip[u], novk, selk, nv, nov_nv, ipio_nv, num[u], den[u]);
                         F.ipdo[(size_t) nv * P + dd[u]] = t;
-                        den[u] -= t * t / nov_nv;
-                        num[u] -= ipio_nv / nov_nv * t;
                         if (den[u] / size < MIN_NORM) { us[u] = true; F.used[dd[u]] = 1; }
                         F.num[dd[u]] = num[u]; F.den[dd[u]] = den[u];
                     }
@@ -871,80 +866,7 @@ __device__ __noinline__ void mp_steps_global(DevFrame &F, Sh &sh, int q, float s
         __syncthreads();
         if (tid == 0) { unsigned long long t = wall_clock64(); tA += t - tmark; tmark = t; }
         /* ------- phase B: ordered replay + commit of the step, all inside wave 0 ------- */
-        if (wave == 0) {
-            float m = mp.min_costs;
-            unsigned evals = 0;
-            /* the best candidate of the step lives in registers (wave-uniform copies) */
-            int b_state = -1;
-            float b_cost = 0, b_mbits = 0, b_wbits = 0, b_err = 0, b_f[MAXED];
-#pragma unroll
-            for (int k = 0; k < MAXED; k++) b_f[k] = 0;
-            for (int bb = 0; bb < nblk; bb += 64) {
-                float bm = (bb + lane < nblk) ? sh.blockmin[bb + lane] : BIGF;
-                int lastb = -1;
-                for (;;) {
-                    unsigned long long mask = __ballot(bm < m && lane > lastb);
-                    if (!mask) break;
-                    int jb = __ffsll((long long) mask) - 1;
-                    lastb = jb;
-                    int d = ((bb + jb) << 6) + lane;
-                    float e = (d < S) ? F.est[d] : BIGF;
-                    bool pass = e < m;
-                    Eval ev;
-                    ev.costs = BIGF; ev.m_bits = ev.w_bits = ev.m_err = 0;
-#pragma unroll
-                    for (int k = 0; k < MAXED; k++) ev.f[k] = 0;
-                    if (pass) {
-                        float i0 = n > 0 ? F.ipdo[d] : 0.0f, i1 = n > 1 ? F.ipdo[(size_t) P + d] : 0.0f;
-                        float i2 = n > 2 ? F.ipdo[(size_t) 2 * P + d] : 0.0f, i3 = n > 3 ? F.ipdo[(size_t) 3 * P + d] : 0.0f;
-                        full_eval<MAXED - 1>(F, sh, mp, sh.lglv, n, F.pos[d], d, F.num[d], F.den[d], i0, i1, i2, i3, ev);
-                    }
-                    evals += (unsigned) __popcll(__ballot(pass));
-                    blockevals++;
-                    int last = -1, win = -1;
-                    for (;;) {
-                        unsigned long long ok = __ballot(pass && lane > last && e < m && ev.costs < m);
-                        if (!ok) break;
-                        int j = __ffsll((long long) ok) - 1;
-                        last = j; win = j;
-                        m = __shfl(ev.costs, j);
-                    }
-                    if (win >= 0) {                 /* wave-uniform */
-                        b_state = ((bb + jb) << 6) + win;
-                        b_cost = __shfl(ev.costs, win); b_mbits = __shfl(ev.m_bits, win);
-                        b_wbits = __shfl(ev.w_bits, win); b_err = __shfl(ev.m_err, win);
-#pragma unroll
-                        for (int k = 0; k < MAXED; k++) b_f[k] = __shfl(ev.f[k], win);
-                    }
-                }
-            }
-            if (lane == 0) {
-                sh.cnt.n_fulleval += evals;
-                int index = b_state >= 0 ? (int) F.pos[b_state] : -1;     /* its pool position */
-                if (index >= 0) {
-                    if (b_cost < mp.costs) {
-                        mp.costs = b_cost; mp.err = b_err;
-                        mp.matrix_bits = b_mbits; mp.weights_bits = b_wbits;
-#pragma unroll
-                        for (int k = 0; k < MAXED; k++) if (k <= n) mp.weight[k] = b_f[k];
-                        mp.symp = SYMP_NONE;            /* (this scan does not carry the symbols) */
-                        mp.best_n = n + 1;
-                    }
-                    mp.indices[n] = (short) index;
-                    mp.into[n] = (short) b_state;
-                    F.used[b_state] = 1;
-                    mp.norm_ov[n] = F.den[b_state];
-                    mp.ipio[n] = F.num[b_state];
-#pragma unroll
-                    for (int k = 0; k < MAXED - 1; k++)
-                        if (k < n) mp.sel_ipdo[n][k] = F.ipdo[(size_t) k * P + b_state];
-                    mp.row_state = b_state;
-                    mp.n = n + 1;
-                    if (mp.n < F.max_elements) mp_step_prepare(F, sh, mp, sh.lglv, sh.lglv_m1);
-                }
-                mp.index = index;
-            }
-        }
+        if (wave == 0) mp_replay_hbm<false>(F, sh, n, S, blockevals);
         __syncthreads();
         if (tid == 0) { unsigned long long t = wall_clock64(); tB += t - tmark; tmark = t; }
         if (!(mp.n < F.max_elements && mp.index >= 0)) break;
@@ -989,12 +911,12 @@ __device__ __noinline__ void mp_steps_list_global(DevFrame &F, Sh &sh, int q, fl
                     F.num[c] = num; F.den[c] = den; F.used[c] = uu;
                 } else if (!us) {                                     /* codec/approx.c:676-698 */
                     num = F.num[c]; den = F.den[c];
-                    float t = gram_load(Gq, P, mp.row_state, st, flim);
-                    for (int k = 0; k < MAXED - 1; k++)
-                        if (k < nv) t -= F.ipdo[(size_t) k * P + c] / mp.norm_ov[k] * mp.sel_ipdo[nv][k];
+                    float ip[MAXED - 1];
+#pragma unroll
+                    for (int k = 0; k < MAXED - 1; k++) ip[k] = k < nv ? F.ipdo[(size_t) k * P + c] : 0.0f;
+                    const float t = mp_orthogonalize<MAXED - 1>(gram_load(Gq, P, mp.row_state, st, flim), ip, mp.norm_ov,
+                                                                mp.sel_ipdo[nv], nv, mp.norm_ov[nv], mp.ipio[nv], num, den);
                     F.ipdo[(size_t) nv * P + c] = t;
-                    den -= t * t / mp.norm_ov[nv];
-                    num -= mp.ipio[nv] / mp.norm_ov[nv] * t;
                     if (den / size < MIN_NORM) { us = true; F.used[c] = 1; }
                     F.num[c] = num; F.den[c] = den;
                 }
@@ -1021,86 +943,7 @@ __device__ __noinline__ void mp_steps_list_global(DevFrame &F, Sh &sh, int q, fl
             }
         }
         __syncthreads();
-        if (wave == 0) {                     /* ordered replay + commit of the step, as in mp_steps_global */
-            float m = mp.min_costs;
-            unsigned evals = 0;
-            int b_idx = -1;
-            float b_cost = 0, b_mbits = 0, b_wbits = 0, b_err = 0, b_f[MAXED];
-#pragma unroll
-            for (int k = 0; k < MAXED; k++) b_f[k] = 0;
-            for (int bb = 0; bb < nblk; bb += 64) {
-                float bm = (bb + lane < nblk) ? sh.blockmin[bb + lane] : BIGF;
-                int lastb = -1;
-                for (;;) {
-                    unsigned long long mask = __ballot(bm < m && lane > lastb);
-                    if (!mask) break;
-                    int jb = __ffsll((long long) mask) - 1;
-                    lastb = jb;
-                    const int c = ((bb + jb) << 6) + lane;
-                    float e = (c < D) ? F.est[c] : BIGF;
-                    bool pass = e < m;
-                    Eval ev;
-                    ev.costs = BIGF; ev.m_bits = ev.w_bits = ev.m_err = 0;
-#pragma unroll
-                    for (int k = 0; k < MAXED; k++) ev.f[k] = 0;
-                    if (pass) {
-                        float i0 = n > 0 ? F.ipdo[c] : 0.0f, i1 = n > 1 ? F.ipdo[(size_t) P + c] : 0.0f;
-                        float i2 = n > 2 ? F.ipdo[(size_t) 2 * P + c] : 0.0f, i3 = n > 3 ? F.ipdo[(size_t) 3 * P + c] : 0.0f;
-#if FC_GM
-                        ev.qc = GM_QAC(sh.gm.pk[0]) && c < (int) sh.pool.n ? (int) GQ_CUR(sh, 0)[c] : 0;
-#endif
-                        full_eval<MAXED - 1>(F, sh, mp, sh.lglv, n, c, list[c], F.num[c], F.den[c], i0, i1, i2, i3, ev);
-                    }
-                    evals += (unsigned) __popcll(__ballot(pass));
-                    blockevals++;
-                    int last = -1, win = -1;
-                    for (;;) {
-                        unsigned long long ok = __ballot(pass && lane > last && e < m && ev.costs < m);
-                        if (!ok) break;
-                        int j = __ffsll((long long) ok) - 1;
-                        last = j; win = j;
-                        m = __shfl(ev.costs, j);
-                    }
-                    if (win >= 0) {
-                        b_idx = ((bb + jb) << 6) + win;
-                        b_cost = __shfl(ev.costs, win); b_mbits = __shfl(ev.m_bits, win);
-                        b_wbits = __shfl(ev.w_bits, win); b_err = __shfl(ev.m_err, win);
-#pragma unroll
-                        for (int k = 0; k < MAXED; k++) b_f[k] = __shfl(ev.f[k], win);
-                    }
-                }
-            }
-            if (lane == 0) {
-                sh.cnt.n_fulleval += evals;
-                const int index = b_idx;
-                if (index >= 0) {
-                    const int b_state = list[index];
-                    if (b_cost < mp.costs) {
-                        mp.costs = b_cost; mp.err = b_err;
-                        mp.matrix_bits = b_mbits; mp.weights_bits = b_wbits;
-#pragma unroll
-                        for (int k = 0; k < MAXED; k++) if (k <= n) mp.weight[k] = b_f[k];
-                        mp.symp = SYMP_NONE;            /* (this scan does not carry the symbols) */
-                        mp.best_n = n + 1;
-                    }
-                    mp.indices[n] = (short) index;
-                    mp.into[n] = (short) b_state;
-#if FC_GM
-                    mp.kq[n] = GM_QAC(sh.gm.pk[0]) && index < (int) sh.pool.n ? GQ_CUR(sh, 0)[index] : (short) 0;
-#endif
-                    F.used[index] = 1;
-                    mp.norm_ov[n] = F.den[index];
-                    mp.ipio[n] = F.num[index];
-#pragma unroll
-                    for (int k = 0; k < MAXED - 1; k++)
-                        if (k < n) mp.sel_ipdo[n][k] = F.ipdo[(size_t) k * P + index];
-                    mp.row_state = b_state;
-                    mp.n = n + 1;
-                    if (mp.n < F.max_elements) mp_step_prepare(F, sh, mp, sh.lglv, sh.lglv_m1);
-                }
-                mp.index = index;
-            }
-        }
+        if (wave == 0) mp_replay_hbm<true>(F, sh, n, D, blockevals);
         __syncthreads();
         if (!(mp.n < F.max_elements && mp.index >= 0)) break;
     }
@@ -1116,188 +959,106 @@ __device__ __noinline__ void mp_steps_chroma(DevFrame &F, Sh &sh, int q, float s
     mp_steps_list<MAXED - 1>(F, sh, q, size, D);
 }
 
-/* approximate_range (codec/approx.c:74-271): one matching pursuit, plus in the big variant a
- * second one without the first vector of the first (second_domain_block, :103-118) */
-__device__ __forceinline__ void op_approx(DevFrame &F, Sh &sh)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, P = sh.par.P;
-    SFrame &fr = sh.st[sh.sp];
-    MPState &mp = sh.mp;
-    const int level = fr.lrange.level;
-    const float size = (float) (1u << level);
-    const int q = level - sh.par.gl0;                    /* Gram table index of this level */
-    const int D = sh.pool.n;
-    int y = fr.y_state;                             /* rle_generate, domain-pool.c:716-719 */
-    if (y >= 0 && !(F.domain_type[y] & 2)) y = -1;
-
+/* approximate_range (codec/approx.c:74-271): one matching pursuit, plus in the big variant further ones without vectors
+ * of the first (:103-206).  op_approx() at the end is the sequence of the steps below.  What a build does differently is
+ * said once, in the step it belongs to, as two whole definitions: FC_GM first, then FC_VARIANT_BIG against the default. */
 #ifdef FC_SERIAL_PROFILE
-    unsigned long long tp = wall_clock64();
+#define APX_CLOCK() unsigned long long tp = wall_clock64()
 #define APX_MARK(i) do { if (tid == 0) { unsigned long long t_ = wall_clock64(); sh.tk_apx[i] += t_ - tp; tp = t_; } } while (0)
 #else
+#define APX_CLOCK() do { } while (0)
 #define APX_MARK(i) do { } while (0)
 #endif
-    /* candidates are walked by STATE id (scratch, diag, Gram row, numerators are all state
-     * indexed, so every load of phase A is direct and coalesced); pos[] gives the position in
-     * the pool list that the rate model needs, -1 for states outside the pool.  State order ==
-     * position order, so the 64-state blocks keep the reference's scan order. */
-#define APX_REGSCAN() (!sh.band && sh.states <= KREG * B && sh.par.max_elements <= FC_NIP + 1)        /* uniform */
-    if (fr.coop) snap_coop_before(sh, fr, sh.sp, sh.par.ML);
-#if !FC_VARIANT_BIG
-    /* The scan's first reads depend on nothing the call computes: they are requested in front of the table pass and
-     * cross it and lane 0's set-up in flight (MP_TABLES_INLINE; a call of the out-of-line mp_tables waits for them) */
-    const bool regscan = APX_REGSCAN();
-    Step0 pre;
-#if MP_TABLES_INLINE
-    /* vmcnt(0), as the call of the out-of-line mp_tables had it at this point: nothing an earlier operation requested
-     * is in flight here, but the compiler cannot tell (the barrier at the head of the operation loop does not wait for
-     * memory reads) and would otherwise wait for "them" -- in fact for the reads requested below -- in the middle of
-     * the table pass and of the set-up, wherever it reuses a register such a read once went to */
-    __builtin_amdgcn_s_waitcnt(0x0f70);
-#endif
-    if (regscan) mp_step0_issue(sh, q, sh.par.ipis + (size_t) fr.lrange.image * P, pre);
-#endif
-    mp_tables(F, sh, level, y);
-#if MP_TABLES_INLINE && !FC_VARIANT_BIG
-    lds_barrier();                       /* the tables live in LDS */
-#else
-    __syncthreads();
-#endif
-#if FC_VARIANT_BIG
-    const bool regscan = APX_REGSCAN();  /* the row of the first reads is chosen by the set-up: requested behind it */
-    Step0 pre;
-#endif
-    APX_MARK(0);
-#if FC_VARIANT_BIG
-    /* retries of approximate_range (codec/approx.c:103-206): second domain block, then removal
-     * of vectors whose weight rounded to zero (underflow) or to the extreme value (overflow);
-     * `mp` is the reference's working copy t, sh.mp_keep its best result so far */
-    const bool retries = F.second_domain_block || F.check_underflow || F.check_overflow;
-    if (tid == 0) {
-        sh.apx_stage = 0; sh.apx_it = -1;
-        mp.excl[0] = NOEDGE;
-        for (int k = 0; k < MAXED; k++) mp.weight[k] = 0;     /* mp_t starts zeroed */
-    }
-#else
-    const bool retries = false;
-#endif
-    for (;;) {
-    if (tid == 0) {
-        mp.n = 0; mp.best_n = 0; mp.symp = SYMP_NONE;
-        mp.D = D; mp.N = D;
-        mp.y_state = y; mp.ypos = -1;
-        if (sh.band) {
-            /* the list is the chroma pool (constant, kept in sh.dl) plus y unless present */
-            int ypos = -1;
-#if FC_VARIANT_BIG
-#if FC_GM
-            if (sh.gm.pk[0] == FC_PK_UNIFORM || sh.gm.pk[0] == FC_PK_CONSTANT) {
-                /* uniform_generate / const_generate (codec/domain-pool.c:578-590,518-528) know no luminance state */
-            } else
-#endif
-            if (FC_GM || F.chroma_max > 63) {         /* long list in F.pool_states; F.pos is its inverse (op_chroma_pool) */
-                if (y >= 0) {
-                    ypos = F.pos[y];
-                    if (ypos < 0 || ypos >= D) { F.pool_states[D] = (short) y; ypos = D; mp.D = D + 1; }
-                }
-            } else
-#endif
-            if (y >= 0) {
-                for (int i = 0; i < D; i++) if (sh.dl[i] == y) ypos = i;
-                if (ypos < 0) { sh.dl[D] = (short) y; ypos = D; mp.D = D + 1; }
-            }
-            mp.ypos = ypos;
-        }
-        mp.level = level; mp.image = fr.lrange.image; mp.address = fr.lrange.address;
-#if FC_VARIANT_BIG
-        if (level > sh.par.images_level) {
-            mp.norm = sh.norms[mp.image];
-            mp.numrow = sh.par.ipis + (size_t) mp.image * P;
-        } else {
-            /* block not larger than a state image: direct dots (codec/ip.c:46-70,268-295),
-             * tables d5 / d4 of the current pixel block; norm as codec/approx.c:388-389 */
-            const int npx = 1 << level;
-            const float *px = sh.pixels + mp.address * npx;
-            float nrm = 0;
-            for (int k = 0; k < npx; k++) nrm += px[k] * px[k];
-            mp.norm = nrm;
-            mp.numrow = (level == sh.par.images_level ? ACT_D5(F, sh) : ACT_D4(F, sh)) + (size_t) mp.address * P;
-        }
-#else
-        mp.norm = sh.norms[mp.image];
-#endif
-#if FC_VARIANT_BIG
-        /* additional_bits, codec/approx.c:391-393 */
-        mp.ab = fr.lrange.tree_bits + fr.lrange.mv_tree_bits + fr.lrange.mv_coord_bits + fr.lrange.nd_tree_bits
-                + fr.lrange.nd_weights_bits;
-#else
-        fr.lrange.tree_bits = sh.tb[0];
-        mp.ab = sh.tb[0];
-#endif
-        mp.price = fr.price;
-        mp.err = mp.norm;
-        mp.weights_bits = 0;
-        mp.matrix_bits = sh.Ltab[0] + sh.Q0;         /* rle_bits of the empty list */
-#if FC_GM
-        if (!GM_RLE(sh.gm.pk[0])) mp.matrix_bits = sh.gm.pk[0] == FC_PK_CONSTANT ? 0.0f : sh.gm.base;
-#endif
-        mp.costs = (mp.matrix_bits + mp.weights_bits + mp.ab) * mp.price + mp.err;
-        mp.index = -1;
-#if FC_VARIANT_BIG
-        mp_step_prepare(F, sh, mp, sh.lglv, sh.lglv_m1);
-#else
-        if (sh.band) mp_step_prepare(F, sh, mp, sh.lglv, sh.lglv_m1);
-        else {
-            /* the rest of the first step's set-up: mp_tables (integers), and the three list prices here */
-            const float L0 = sh.Ltab[0], L1 = sh.Ltab[1], q0 = sh.Q0, q1 = sh.Q1;
-            float b = L1; b += q0; mp.s1_pre[0] = b;
-            b = L1; b += q1; mp.s1_z0 = b;
-            b = L0; b += q0; mp.s1_zy = b;                 /* also rle_bits of the empty list */
-            mp.min_costs = mp.costs;
-        }
-#endif
-    }
-    lds_barrier();                       /* the set-up lives in LDS; the scan's first reads stay in flight */
 
-    APX_MARK(1);
+/* Candidates are walked by STATE id (scratch, diag, Gram row, numerators are all state indexed, so every load of
+ * phase A is direct and coalesced); pos[] gives the position in the pool list that the rate model needs, -1 for states
+ * outside the pool.  State order == position order, so the 64-state blocks keep the reference's scan order.
+ * The register scan takes a luminance search whose states and vectors fit its slots (uniform). */
+#define APX_REGSCAN(sh) (!(sh).band && (sh).states <= KREG * B && (sh).par.max_elements <= FC_NIP + 1)
+
 #if FC_GM
-    if (true) {
-        /* every search of this build: the list scan with scratch in HBM and the ->bits of the active pool */
-        mp_steps_list_global(F, sh, q, size, mp.D);
-    } else
+/* uniform_generate / const_generate (codec/domain-pool.c:578-590,518-528) know no luminance state */
+__device__ __forceinline__ bool gm_no_luma(const Sh &sh)
+{
+    return sh.gm.pk[0] == FC_PK_UNIFORM || sh.gm.pk[0] == FC_PK_CONSTANT;
+}
+/* set-up: the ->bits of the active pool for the empty list */
+__device__ __forceinline__ float apx_empty_list_bits(const Sh &sh)
+{
+    if (!GM_RLE(sh.gm.pk[0])) return sh.gm.pk[0] == FC_PK_CONSTANT ? 0.0f : sh.gm.base;
+    return sh.Ltab[0] + sh.Q0;
+}
+#else
+__device__ __forceinline__ bool gm_no_luma(const Sh &sh) { return false; }
+/* set-up: rle_bits of the empty list */
+__device__ __forceinline__ float apx_empty_list_bits(const Sh &sh) { return sh.Ltab[0] + sh.Q0; }
 #endif
-    if (sh.band) {
-        /* chroma bands: short explicit candidate list (mp_reg.inc) */
-        mp_steps_chroma(F, sh, q, size, mp.D);
-    } else if (regscan) {
-        /* fast path: per-candidate scratch lives in registers (mp_reg.inc) */
+
 #if FC_VARIANT_BIG
-        mp_step0_issue(sh, q, MP_NUMROW(F, mp), pre);        /* the row is chosen by the set-up */
-#endif
-#if FC_VARIANT_BIG
-        /* uniform: a half / a quarter of the register slots hold every state (a frame starts with a handful).  (The
-         * default builds keep ONE instance: a second one inlined beside it costs them more in spilled registers --
-         * 128 VGPRs, four frames per CU -- than the shorter slot loops save: 545 against 556 frames/s.) */
-        const int kslots = (sh.states + B - 1) / B;
-        /* at most three vectors per block (the CLI's default, BASELINE config 5): the scan of the default builds --
-         * one kept projection per register slot instead of three, shorter fixed-trip loops in the estimate */
-        if (sh.par.max_elements <= 3) {
-            if (kslots <= KREG / 4) mp_steps_reg<2, KREG / 4>(F, sh, q, size, pre);
-            else if (kslots <= KREG / 2) mp_steps_reg<2, KREG / 2>(F, sh, q, size, pre);
-            else mp_steps_reg<2>(F, sh, q, size, pre);
-        } else if (kslots <= KREG / 4) mp_steps_reg<FC_NIP, KREG / 4>(F, sh, q, size, pre);
-        else if (kslots <= KREG / 2) mp_steps_reg<FC_NIP, KREG / 2>(F, sh, q, size, pre);
-        else
-#endif
-        mp_steps_reg<FC_NIP>(F, sh, q, size, pre);
+/* ---------------- the big builds ---------------- */
+
+/* set-up: the range's inputs -- its norm, its row of <range, state> numerators, the bits it costs besides the
+ * combination */
+__device__ __forceinline__ void apx_range_inputs(const DevFrame &F, Sh &sh, SFrame &fr, int level)
+{
+    MPState &mp = sh.mp;
+    const int P = sh.par.P;
+    if (level > sh.par.images_level) {
+        mp.norm = sh.norms[mp.image];
+        mp.numrow = sh.par.ipis + (size_t) mp.image * P;
     } else {
-        mp_steps_global(F, sh, q, size);
+        /* block not larger than a state image: direct dots (codec/ip.c:46-70,268-295),
+         * tables d5 / d4 of the current pixel block; norm as codec/approx.c:388-389 */
+        const int npx = 1 << level;
+        const float *px = sh.pixels + mp.address * npx;
+        float nrm = 0;
+        for (int k = 0; k < npx; k++) nrm += px[k] * px[k];
+        mp.norm = nrm;
+        mp.numrow = (level == sh.par.images_level ? ACT_D5(F, sh) : ACT_D4(F, sh)) + (size_t) mp.address * P;
     }
-    APX_MARK(2);
-    if (!retries) break;
-#if FC_VARIANT_BIG
+    /* additional_bits, codec/approx.c:391-393 */
+    mp.ab = fr.lrange.tree_bits + fr.lrange.mv_tree_bits + fr.lrange.mv_coord_bits + fr.lrange.nd_tree_bits
+            + fr.lrange.nd_weights_bits;
+}
+
+/* The register scan: its first reads take the row of numerators that the set-up has chosen, so they are requested
+ * here.  Then by (uniform) instance: a half / a quarter of the register slots hold every state (a frame starts
+ * with a handful).  (The default builds keep ONE instance: a second one inlined beside it costs them more in spilled
+ * registers -- 128 VGPRs, four frames per CU -- than the shorter slot loops save: 545 against 556 frames/s.) */
+__device__ __forceinline__ void apx_steps_reg(DevFrame &F, Sh &sh, int q, float size, Step0 &pre)
+{
+    mp_step0_issue(sh, q, MP_NUMROW(F, sh.mp), pre);
+    const int kslots = (sh.states + B - 1) / B;
+    /* at most three vectors per block (the CLI's default, BASELINE config 5): the scan of the default builds --
+     * one kept projection per register slot instead of three, shorter fixed-trip loops in the estimate */
+    if (sh.par.max_elements <= 3) {
+        if (kslots <= KREG / 4) mp_steps_reg<2, KREG / 4>(F, sh, q, size, pre);
+        else if (kslots <= KREG / 2) mp_steps_reg<2, KREG / 2>(F, sh, q, size, pre);
+        else mp_steps_reg<2>(F, sh, q, size, pre);
+    } else if (kslots <= KREG / 4) mp_steps_reg<FC_NIP, KREG / 4>(F, sh, q, size, pre);
+    else if (kslots <= KREG / 2) mp_steps_reg<FC_NIP, KREG / 2>(F, sh, q, size, pre);
+    else mp_steps_reg<FC_NIP>(F, sh, q, size, pre);
+}
+
+/* Retries of approximate_range (codec/approx.c:103-206): second domain block, then removal of vectors whose weight
+ * rounded to zero (underflow) or to the extreme value (overflow); sh.mp is the reference's working copy t, sh.mp_keep
+ * its best result so far.  apx_retry_begin: does the frame ask for any; apx_retry_next, behind a search: keep the
+ * better result and say whether another search follows (its exclude list is then in sh.mp). */
+__device__ __forceinline__ bool apx_retry_begin(const DevFrame &F, Sh &sh)
+{
+    if (threadIdx.x == 0) {
+        sh.apx_stage = 0; sh.apx_it = -1;
+        sh.mp.excl[0] = NOEDGE;
+        for (int k = 0; k < MAXED; k++) sh.mp.weight[k] = 0;     /* mp_t starts zeroed */
+    }
+    return F.second_domain_block || F.check_underflow || F.check_overflow;
+}
+__device__ __forceinline__ bool apx_retry_next(const DevFrame &F, Sh &sh, bool retries)
+{
+    if (!retries) return false;
     __syncthreads();
-    if (tid == 0) {
-        MPState &best = sh.mp_keep;
+    if (threadIdx.x == 0) {
+        MPState &mp = sh.mp, &best = sh.mp_keep;
         mp.indices[mp.best_n] = NOEDGE;                       /* codec/approx.c:636-640 */
         mp.costs = (mp.matrix_bits + mp.weights_bits + mp.ab) * mp.price + mp.err;
         if (sh.apx_stage == 0) best = mp;
@@ -1340,75 +1101,221 @@ __device__ __forceinline__ void op_approx(DevFrame &F, Sh &sh)
         sh.apx_more = more;
     }
     __syncthreads();
-    if (!sh.apx_more) break;
-#endif
-    }
+    return sh.apx_more;
+}
 
-    if (tid == 0) {
-        Range &lr = fr.lrange;
-        mp.indices[mp.best_n] = NOEDGE;
-        float costs = (mp.matrix_bits + mp.weights_bits + mp.ab) * mp.price + mp.err;
-        if (costs < fr.max_costs) {
-            int ni = 0;
-            unsigned sp = 0;                 /* the symbols move with their weights */
-            for (int oi = 0; mp.indices[oi] != NOEDGE; oi++)
-                if (mp.weight[oi] != 0) {
-                    mp.indices[ni] = mp.indices[oi]; mp.into[ni] = mp.into[oi];
-                    mp.weight[ni] = mp.weight[oi];
-                    if (oi < 3) sp |= ((mp.symp >> (10 * oi)) & 1023u) << (10 * ni);      /* (ni <= oi) */
-                    ni++;
-                }
-            mp.indices[ni] = NOEDGE; mp.into[ni] = NOEDGE;
-            models_update(F, sh, mp.indices, mp.into, mp.weight, level, mp.y_state, sp);
-            int e = 0;
-            for (; mp.indices[e] != NOEDGE; e++) { lr.into[e] = mp.into[e]; lr.weight[e] = mp.weight[e]; }
-            lr.into[e] = NOEDGE;
-            lr.matrix_bits = mp.matrix_bits; lr.weights_bits = mp.weights_bits; lr.err = mp.err;
-        } else {
-            lr.into[0] = NOEDGE;
-            costs = MAXCOSTS;
-        }
-        fr.lincomb = costs;
+#else
+/* ---------------- the builds of the default geometry ---------------- */
+
+/* set-up: the range's inputs -- its norm (its numerators are the image's row of the table, MP_NUMROW) and the bits
+ * it costs besides the combination: the tree bits of this level, which mp_tables left in sh.tb */
+__device__ __forceinline__ void apx_range_inputs(const DevFrame &F, Sh &sh, SFrame &fr, int level)
+{
+    sh.mp.norm = sh.norms[sh.mp.image];
+    fr.lrange.tree_bits = sh.tb[0];
+    sh.mp.ab = sh.tb[0];
+}
+
+__device__ __forceinline__ void apx_steps_reg(DevFrame &F, Sh &sh, int q, float size, Step0 &pre)
+{
+    mp_steps_reg<FC_NIP>(F, sh, q, size, pre);
+}
+
+/* no retries: full_search, second_domain_block and the weight checks need a big build */
+__device__ __forceinline__ bool apx_retry_begin(const DevFrame &F, Sh &sh) { return false; }
+__device__ __forceinline__ bool apx_retry_next(const DevFrame &F, Sh &sh, bool retries) { return false; }
+#endif
+
+/* Default builds: the first reads of the register scan depend on nothing the call computes.  They are requested in
+ * front of the table pass and cross it and lane 0's set-up in flight (MP_TABLES_INLINE; a call of the out-of-line
+ * mp_tables waits for them) */
+__device__ __forceinline__ void apx_issue_early(const Sh &sh, const SFrame &fr, int q, bool regscan, Step0 &pre)
+{
+    /* vmcnt(0), as the call of the out-of-line mp_tables had it at this point: nothing an earlier operation requested
+     * is in flight here, but the compiler cannot tell (the barrier at the head of the operation loop does not wait for
+     * memory reads) and would otherwise wait for "them" -- in fact for the reads requested below -- in the middle of
+     * the table pass and of the set-up, wherever it reuses a register such a read once went to */
+    if (MP_TABLES_INLINE) __builtin_amdgcn_s_waitcnt(0x0f70);
+    if (regscan) mp_step0_issue(sh, q, sh.par.ipis + (size_t) fr.lrange.image * sh.par.P, pre);
+}
+
+/* set-up, chroma: the list is the chroma pool (constant) plus the luminance state y unless present: y's position in
+ * it, where it is appended if need be (mp.D grows); -1 without y */
+__device__ __forceinline__ int apx_ypos(DevFrame &F, Sh &sh, int y, int D)
+{
+    int ypos = -1;
+    if (y < 0 || gm_no_luma(sh)) return ypos;
+    if (FC_VARIANT_BIG && (FC_GM || F.chroma_max > 63)) {    /* long list in F.pool_states; F.pos is its inverse */
+        ypos = F.pos[y];                                     /* (op_chroma_pool) */
+        if (ypos < 0 || ypos >= D) { F.pool_states[D] = (short) y; ypos = D; sh.mp.D = D + 1; }
+    } else {                                                 /* at most 64, kept in sh.dl */
+        for (int i = 0; i < D; i++) if (sh.dl[i] == y) ypos = i;
+        if (ypos < 0) { sh.dl[D] = (short) y; ypos = D; sh.mp.D = D + 1; }
+    }
+    return ypos;
+}
+
+/* per-search set-up, lane 0: the call's state in sh.mp before the first step */
+__device__ __forceinline__ void apx_setup(DevFrame &F, Sh &sh, SFrame &fr, int level, int y, int D)
+{
+    MPState &mp = sh.mp;
+    mp.n = 0; mp.best_n = 0; mp.symp = SYMP_NONE;
+    mp.D = D; mp.N = D;
+    mp.y_state = y;
+    mp.ypos = sh.band ? apx_ypos(F, sh, y, D) : -1;
+    mp.level = level; mp.image = fr.lrange.image; mp.address = fr.lrange.address;
+    apx_range_inputs(F, sh, fr, level);
+    mp.price = fr.price;
+    mp.err = mp.norm;
+    mp.weights_bits = 0;
+    mp.matrix_bits = apx_empty_list_bits(sh);
+    mp.costs = (mp.matrix_bits + mp.weights_bits + mp.ab) * mp.price + mp.err;
+    mp.index = -1;
+    /* the prices of the first step.  A luminance search of a default build has no kept vector: mp_tables left the
+     * integers, the three list prices are added up here.  (Big builds: weights of an earlier run may enter them.) */
+    if (FC_VARIANT_BIG || sh.band) mp_step_prepare(F, sh, mp, sh.lglv, sh.lglv_m1);
+    else {
+        const float L0 = sh.Ltab[0], L1 = sh.Ltab[1], q0 = sh.Q0, q1 = sh.Q1;
+        float b = L1; b += q0; mp.s1_pre[0] = b;
+        b = L1; b += q1; mp.s1_z0 = b;
+        b = L0; b += q0; mp.s1_zy = b;                 /* also rle_bits of the empty list */
+        mp.min_costs = mp.costs;
+    }
+}
+
+/* the choice of scan (uniform) */
+#if FC_GM
+/* every search of this build: the list scan with scratch in HBM and the ->bits of the active pool */
+__device__ __forceinline__ void apx_scan(DevFrame &F, Sh &sh, int q, float size, bool regscan, Step0 &pre)
+{
+    mp_steps_list_global(F, sh, q, size, sh.mp.D);
+}
+#else
+__device__ __forceinline__ void apx_scan(DevFrame &F, Sh &sh, int q, float size, bool regscan, Step0 &pre)
+{
+    if (sh.band) mp_steps_chroma(F, sh, q, size, sh.mp.D);   /* chroma bands: explicit candidate list */
+    else if (regscan) apx_steps_reg(F, sh, q, size, pre);    /* per-candidate scratch in registers (mp_reg.inc) */
+    else mp_steps_global(F, sh, q, size);
+}
+#endif
+
+/* acceptance, lane 0: the combination found becomes the range's approximation if it costs less than max_costs --
+ * without the vectors whose weight is zero, and the models learn it.  Returns its costs, MAXCOSTS if it is not taken. */
+__device__ __forceinline__ float apx_take(const DevFrame &F, Sh &sh, SFrame &fr, int level)
+{
+    MPState &mp = sh.mp;
+    Range &lr = fr.lrange;
+    mp.indices[mp.best_n] = NOEDGE;
+    float costs = (mp.matrix_bits + mp.weights_bits + mp.ab) * mp.price + mp.err;
+    if (costs < fr.max_costs) {
+        int ni = 0;
+        unsigned sp = 0;                 /* the symbols move with their weights */
+        for (int oi = 0; mp.indices[oi] != NOEDGE; oi++)
+            if (mp.weight[oi] != 0) {
+                mp.indices[ni] = mp.indices[oi]; mp.into[ni] = mp.into[oi];
+                mp.weight[ni] = mp.weight[oi];
+                if (oi < 3) sp |= ((mp.symp >> (10 * oi)) & 1023u) << (10 * ni);      /* (ni <= oi) */
+                ni++;
+            }
+        mp.indices[ni] = NOEDGE; mp.into[ni] = NOEDGE;
+        models_update(F, sh, mp.indices, mp.into, mp.weight, level, mp.y_state, sp);
+        int e = 0;
+        for (; mp.indices[e] != NOEDGE; e++) { lr.into[e] = mp.into[e]; lr.weight[e] = mp.weight[e]; }
+        lr.into[e] = NOEDGE;
+        lr.matrix_bits = mp.matrix_bits; lr.weights_bits = mp.weights_bits; lr.err = mp.err;
+    } else {
+        lr.into[0] = NOEDGE;
+        costs = MAXCOSTS;
+    }
+    fr.lincomb = costs;
+    return costs;
+}
+
+/* acceptance, lane 0, FC_SPEC: a block with a checkpoint (chain): guess that its combination wins -- its verifier
+ * searches the block, the chain goes on (fr.ckpt = 3) -- or search the block here: after a wrong guess about it, or
+ * when the costs of the combination say that it will hardly win (SpecLocal.mlc) */
 #if FC_SPEC
-        if (fr.ckpt == 2 && sh.sl.role == 0) {
-            /* a block with a checkpoint (chain): guess that its combination wins -- its verifier searches
-             * the block, the chain goes on (fr.ckpt = 3) -- or search the block here: after a wrong guess
-             * about it, or when the costs of the combination say that it will hardly win (SpecLocal.mlc) */
-            Sh::SpecLocal &sl = sh.sl;
-            const unsigned slot = (sl.head - 1) % FC_SPEC_W;      /* this block's checkpoint */
-            if (sl.nospec) { sl.nospec = 0; sl.n_inline++; }
-            else if (costs < (sl.nlc >= 8 ? SPEC_THR * sl.mlc : MAXCOSTS) && !sh.failed) {
-                sl.spec_mask |= 1u << slot;
-                sl.lin[slot] = costs;
-                fr.ckpt = 3;
-            } else sl.n_inline++;
-        }
-#endif
-        if (sh.par.trace_on && F.trace_n < F.trace_cap) {
-            FcTrace &t = F.trace[F.trace_n];
-            t.seq = F.trace_n; t.level = level; t.image = mp.image; t.D = D; t.states = sh.states;
-            t.cost = costs; t.err = mp.err; t.mbits = mp.matrix_bits; t.wbits = mp.weights_bits;
-            int e = 0;
-            for (; e < 6; e++) { t.into[e] = -1; if (e < 5) t.w[e] = 0; }
-            for (e = 0; costs < MAXCOSTS && lr.into[e] != NOEDGE; e++) { t.into[e] = lr.into[e]; t.w[e] = lr.weight[e]; }
-            t.nedges = e;
-            F.trace_n++;
-        }
-#if FC_VARIANT_BIG
-        sh.cnt.bytes_mp += 4ull * D * (2 + mp.n) + 4ull * (1u << level);
-        sh.cnt.n_mp++; sh.cnt.n_steps += mp.n;
-#endif
+__device__ __forceinline__ void apx_spec_checkpoint(Sh &sh, SFrame &fr, float costs)
+{
+    if (fr.ckpt == 2 && sh.sl.role == 0) {
+        Sh::SpecLocal &sl = sh.sl;
+        const unsigned slot = (sl.head - 1) % FC_SPEC_W;      /* this block's checkpoint */
+        if (sl.nospec) { sl.nospec = 0; sl.n_inline++; }
+        else if (costs < (sl.nlc >= 8 ? SPEC_THR * sl.mlc : MAXCOSTS) && !sh.failed) {
+            sl.spec_mask |= 1u << slot;
+            sl.lin[slot] = costs;
+            fr.ckpt = 3;
+        } else sl.n_inline++;
     }
-#if !FC_VARIANT_BIG
-    else if (tid == 64) {                /* the roofline counters, off the serial lane (mp.n is final) */
-        sh.cnt.bytes_mp += 4ull * D * (2 + mp.n) + 4ull * (1u << level);
-        sh.cnt.n_mp++; sh.cnt.n_steps += mp.n;
-    }
+}
+#else
+__device__ __forceinline__ void apx_spec_checkpoint(Sh &sh, SFrame &fr, float costs) { }
 #endif
-    if (fr.coop) {                       /* uniform */
+
+/* acceptance, lane 0: the call's record for the trace (tests: every call's result against the oracle's) */
+__device__ __forceinline__ void apx_trace(DevFrame &F, const Sh &sh, const SFrame &fr, int level, int D, float costs)
+{
+    if (sh.par.trace_on && F.trace_n < F.trace_cap) {
+        const MPState &mp = sh.mp;
+        const Range &lr = fr.lrange;
+        FcTrace &t = F.trace[F.trace_n];
+        t.seq = F.trace_n; t.level = level; t.image = mp.image; t.D = D; t.states = sh.states;
+        t.cost = costs; t.err = mp.err; t.mbits = mp.matrix_bits; t.wbits = mp.weights_bits;
+        int e = 0;
+        for (; e < 6; e++) { t.into[e] = -1; if (e < 5) t.w[e] = 0; }
+        for (e = 0; costs < MAXCOSTS && lr.into[e] != NOEDGE; e++) { t.into[e] = lr.into[e]; t.w[e] = lr.weight[e]; }
+        t.nedges = e;
+        F.trace_n++;
+    }
+}
+
+/* the roofline counters of a call (mp.n is final) */
+__device__ __forceinline__ void apx_count(Sh &sh, int level, int D)
+{
+    sh.cnt.bytes_mp += 4ull * D * (2 + sh.mp.n) + 4ull * (1u << level);
+    sh.cnt.n_mp++; sh.cnt.n_steps += sh.mp.n;
+}
+
+__device__ __forceinline__ void op_approx(DevFrame &F, Sh &sh)
+{
+    const int tid = threadIdx.x;
+    SFrame &fr = sh.st[sh.sp];
+    const int level = fr.lrange.level;
+    const float size = (float) (1u << level);
+    const int q = level - sh.par.gl0;                    /* Gram table index of this level */
+    const int D = sh.pool.n;
+    int y = fr.y_state;                                  /* rle_generate, domain-pool.c:716-719 */
+    if (y >= 0 && !(F.domain_type[y] & 2)) y = -1;
+    APX_CLOCK();
+    if (fr.coop) snap_coop_before(sh, fr, sh.sp, sh.par.ML);
+    const bool regscan = APX_REGSCAN(sh);
+    Step0 pre;
+    if (!FC_VARIANT_BIG) apx_issue_early(sh, fr, q, regscan, pre);
+    mp_tables(F, sh, level, y);
+    if (MP_TABLES_INLINE && !FC_VARIANT_BIG) lds_barrier();      /* the tables live in LDS */
+    else __syncthreads();
+    APX_MARK(0);
+    const bool retries = apx_retry_begin(F, sh);
+    do {
+        if (tid == 0) apx_setup(F, sh, fr, level, y, D);
+        lds_barrier();                   /* the set-up lives in LDS; the scan's first reads stay in flight */
+        APX_MARK(1);
+        apx_scan(F, sh, q, size, regscan, pre);
+        APX_MARK(2);
+    } while (apx_retry_next(F, sh, retries));
+    /* looked up again: kept across the scan, its address is spilled and reloaded on the serial lane (0.5 % slower) */
+    SFrame &fr_behind_scan = sh.st[sh.sp];
+    if (tid == 0) {
+        const float costs = apx_take(F, sh, fr_behind_scan, level);
+        apx_spec_checkpoint(sh, fr_behind_scan, costs);
+        apx_trace(F, sh, fr_behind_scan, level, D, costs);
+        if (FC_VARIANT_BIG) apx_count(sh, level, D);
+    } else if (!FC_VARIANT_BIG && tid == 64) apx_count(sh, level, D);    /* default builds: off the serial lane */
+    if (fr_behind_scan.coop) {           /* uniform */
         __syncthreads();                 /* the models as the accepted combination left them */
-        snap_coop_after(sh, fr, sh.sp);
+        snap_coop_after(sh, fr_behind_scan, sh.sp);
     }
     APX_MARK(3);
-#undef APX_MARK
 }
+#undef APX_CLOCK
+#undef APX_MARK

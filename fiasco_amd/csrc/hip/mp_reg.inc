@@ -13,7 +13,8 @@
  *  the wave that owns that block evaluates its survivors' true costs from its registers,
  *  replays the accept rule in index order (ballot/ffs) and publishes the new minimum and the
  *  winner's record in LDS; one barrier per round.  Block j is owned by wave j % NWAVES,
- *  register slot j / NWAVES.
+ *  register slot j / NWAVES.  The accept rule, the record and the commit are mp_step.inc's, shared with
+ *  the other scans (mp_steps_list below, the HBM scans); the slot loop of the update is this scan's own.
  */
 
 #define KREG FC_KREG                 /* register slots per lane: S <= KREG * B states */
@@ -191,6 +192,8 @@ __device__ __forceinline__ void mp_steps_reg(DevFrame &F, Sh &sh, int q, float s
             }
             const float nov_nv = mp.norm_ov[nv], ipio_nv = mp.ipio[nv];
 #pragma unroll
+            /* mp_orthogonalize() written out: through the helper the (uniform) branch round the division of a slot
+             * becomes a select and the division runs in every step (wide builds: 1 % of the 4K frame rate) */
             for (int k = 0; k < KR; k++) {                  /* codec/approx.c:676-698 */
                 if ((usmask >> k) & 1u) continue;
                 float t = g[k];
@@ -272,48 +275,21 @@ __device__ __forceinline__ void mp_steps_reg(DevFrame &F, Sh &sh, int q, float s
                         for (int j = 0; j < NIP - 1; j++) ipk[j] = ip[k][j];
                     }
                 const int state = kk * B + tid;
-                if (n == NIP) {
-                    /* the last step: <state, o_(NIP-1)> again, as phase A computed it (same inputs,
-                     * same operations: codec/approx.c:676-698) */
-                    const int nv = NIP - 1;
-                    float t = 0.0f;
-                    if (!((usmask >> kk) & 1u)) {
-                        t = gram_load(PGRAM(sh, q), P, mp.row_state, state, sh.flim);
-#pragma unroll
-                        for (int j = 0; j < NIP - 1; j++)
-                            if (j < nv) t -= ipk[j] / mp.norm_ov[j] * mp.sel_ipdo[nv][j];
-                    }
-                    ipk[NIP - 1] = t;
-                }
+                /* the last step: <state, o_(NIP-1)> again, as phase A computed it (same inputs, same operations) */
+                if (n == NIP && !((usmask >> kk) & 1u))
+                    ipk[NIP - 1] = mp_project<NIP - 1>(gram_load(PGRAM(sh, q), P, mp.row_state, state, sh.flim), ipk,
+                                                       mp.norm_ov, mp.sel_ipdo[NIP - 1], NIP - 1);
                 /* the estimate of phase A again (same inputs, same value) */
                 const float ek = ((usmask >> kk) & 1u) ? BIGF : stage1<NIP>(ctx, psk, state, numk, denk);
                 bool pass = ek < m;
                 Eval ev;
-                ev.costs = BIGF; ev.m_bits = ev.w_bits = ev.m_err = 0; ev.symp = SYMP_NONE;
-#pragma unroll
-                for (int k = 0; k < MAXED; k++) ev.f[k] = 0;
+                eval_clear(ev);
                 const float i0 = ipk[0], i1 = NIP > 1 ? ipk[1 % NIP] : 0.0f;
                 const float i2 = NIP > 2 ? ipk[2 % NIP] : 0.0f, i3 = NIP > 3 ? ipk[3 % NIP] : 0.0f;
                 if (pass) full_eval<NIP>(F, sh, mp, sh.lglv, n, psk, state, numk, denk, i0, i1, i2, i3, ev);
                 unsigned npass = (unsigned) __popcll(__ballot(pass));
-                int last = -1, win = -1;
-                for (;;) {
-                    unsigned long long ok = __ballot(pass && lane > last && ek < m && ev.costs < m);
-                    if (!ok) break;
-                    int j = __ffsll((long long) ok) - 1;
-                    last = j; win = j;
-                    m = __shfl(ev.costs, j);
-                }
-                if (lane == win) {                            /* at most one lane */
-                    rb.state = state; rb.idx = psk;       /* pool position: no pos[] read at commit */
-                    rb.cost = ev.costs; rb.mbits = ev.m_bits; rb.wbits = ev.w_bits;
-                    rb.err = ev.m_err; rb.symp = ev.symp;
-#pragma unroll
-                    for (int k = 0; k < MAXED; k++) rb.f[k] = ev.f[k];
-                    rb.num = numk; rb.den = denk;
-#pragma unroll
-                    for (int j = 0; j < MAXED - 1; j++) rb.ip[j] = j < NIP ? ipk[j % NIP] : 0.0f;
-                }
+                const int win = mp_accept(pass, ek, ev.costs, lane, m);
+                if (lane == win) mp_record(rb, state, psk, ev, numk, denk, ipk);      /* at most one lane */
                 if (lane == 0) { rb.m2[round & 1] = m; rb.evals += npass; rb.blockevals++; }
             }
             __syncthreads();
@@ -321,30 +297,7 @@ __device__ __forceinline__ void mp_steps_reg(DevFrame &F, Sh &sh, int q, float s
             round++;
         }
         /* ---------------- commit (lane 0) ---------------- */
-        if (tid == 0) {
-            const int bstate = rb.state;
-            int index = bstate >= 0 ? rb.idx : -1;
-            if (index >= 0) {
-                if (rb.cost < mp.costs) {
-                    mp.costs = rb.cost; mp.err = rb.err;
-                    mp.matrix_bits = rb.mbits; mp.weights_bits = rb.wbits;
-#pragma unroll
-                    for (int k = 0; k < MAXED; k++) if (k <= n) mp.weight[k] = rb.f[k];
-                    mp.symp = rb.symp;
-                    mp.best_n = n + 1;
-                }
-                mp.indices[n] = (short) index;
-                mp.into[n] = (short) bstate;
-                mp.norm_ov[n] = rb.den;
-                mp.ipio[n] = rb.num;
-#pragma unroll
-                for (int k = 0; k < MAXED - 1; k++) if (k < n) mp.sel_ipdo[n][k] = rb.ip[k];
-                mp.row_state = bstate;
-                mp.n = n + 1;
-                if (mp.n < sh.par.max_elements) mp_step_prepare(F, sh, mp, sh.lglv, sh.lglv_m1);
-            }
-            mp.index = index;
-        }
+        if (tid == 0) mp_commit(F, sh, n, rb);
         __syncthreads();
         if (tid == 0) { unsigned long long t = wall_clock64(); tB += t - tmark; tmark = t; }
         if (!(mp.n < sh.par.max_elements && mp.index >= 0)) break;
@@ -393,15 +346,11 @@ __device__ __forceinline__ void mp_steps_list(DevFrame &F, Sh &sh, int q, float 
             const int nv = n - 1;
             if (tid == (int) mp.indices[nv]) used = true;     /* the vector chosen last step */
             if (!used) {                                      /* codec/approx.c:676-698 */
-                float t = gram_load(PGRAM(sh, q), P, mp.row_state, st, sh.flim);
-#pragma unroll
-                for (int j = 0; j < NIP; j++)
-                    if (j < nv) t -= ip[j] / mp.norm_ov[j] * mp.sel_ipdo[nv][j];
+                const float t = mp_orthogonalize<NIP>(gram_load(PGRAM(sh, q), P, mp.row_state, st, sh.flim), ip, mp.norm_ov,
+                                                      mp.sel_ipdo[nv], nv, mp.norm_ov[nv], mp.ipio[nv], num, den);
 #pragma unroll
                 for (int j = 0; j < NIP; j++)
                     if (j == nv) ip[j] = t;
-                den -= t * t / mp.norm_ov[nv];
-                num -= mp.ipio[nv] / mp.norm_ov[nv] * t;
                 if (den / size < MIN_NORM) used = true;
             }
         }
@@ -411,57 +360,17 @@ __device__ __forceinline__ void mp_steps_list(DevFrame &F, Sh &sh, int q, float 
             float m = mp.min_costs;
             bool pass = e < m;
             Eval ev;
-            ev.costs = BIGF; ev.m_bits = ev.w_bits = ev.m_err = 0; ev.symp = SYMP_NONE;
-#pragma unroll
-            for (int k = 0; k < MAXED; k++) ev.f[k] = 0;
+            eval_clear(ev);
             if (pass)
                 full_eval<NIP>(F, sh, mp, sh.lglv, n, tid, st, num, den, ip[0], NIP > 1 ? ip[1 % NIP] : 0.0f,
                           NIP > 2 ? ip[2 % NIP] : 0.0f, NIP > 3 ? ip[3 % NIP] : 0.0f, ev);
             evals += (unsigned) __popcll(__ballot(pass));
-            int last = -1, win = -1;
-            for (;;) {
-                unsigned long long okm = __ballot(pass && lane > last && e < m && ev.costs < m);
-                if (!okm) break;
-                int j = __ffsll((long long) okm) - 1;
-                last = j; win = j;
-                m = __shfl(ev.costs, j);
-            }
+            const int win = mp_accept(pass, e, ev.costs, lane, m);
             if (lane == 0) rb.state = -1;
-            if (lane == win) {                                /* at most one lane */
-                rb.state = st; rb.idx = tid;
-                rb.cost = ev.costs; rb.mbits = ev.m_bits; rb.wbits = ev.w_bits; rb.err = ev.m_err; rb.symp = ev.symp;
-#pragma unroll
-                for (int k = 0; k < MAXED; k++) rb.f[k] = ev.f[k];
-                rb.num = num; rb.den = den;
-#pragma unroll
-                for (int j = 0; j < MAXED - 1; j++) rb.ip[j] = j < NIP ? ip[j % NIP] : 0.0f;
-            }
+            if (lane == win) mp_record(rb, st, tid, ev, num, den, ip);        /* at most one lane */
         }
         __syncthreads();
-        if (tid == 0) {                                       /* commit, as in mp_steps_reg */
-            const int bstate = rb.state;
-            const int index = bstate >= 0 ? rb.idx : -1;
-            if (index >= 0) {
-                if (rb.cost < mp.costs) {
-                    mp.costs = rb.cost; mp.err = rb.err;
-                    mp.matrix_bits = rb.mbits; mp.weights_bits = rb.wbits;
-#pragma unroll
-                    for (int k = 0; k < MAXED; k++) if (k <= n) mp.weight[k] = rb.f[k];
-                    mp.symp = rb.symp;
-                    mp.best_n = n + 1;
-                }
-                mp.indices[n] = (short) index;
-                mp.into[n] = (short) bstate;
-                mp.norm_ov[n] = rb.den;
-                mp.ipio[n] = rb.num;
-#pragma unroll
-                for (int k = 0; k < MAXED - 1; k++) if (k < n) mp.sel_ipdo[n][k] = rb.ip[k];
-                mp.row_state = bstate;
-                mp.n = n + 1;
-                if (mp.n < sh.par.max_elements) mp_step_prepare(F, sh, mp, sh.lglv, sh.lglv_m1);
-            }
-            mp.index = index;
-        }
+        if (tid == 0) mp_commit(F, sh, n, rb);
         steps++;
         __syncthreads();
         if (!(mp.n < sh.par.max_elements && mp.index >= 0)) break;
