@@ -424,11 +424,14 @@ def test_signatures_cover_the_headers():
 
 
 def test_binding_declares_the_abi_in_one_place():
-    """fiasco_amd/__init__.py assigns argtypes / restype only where Library.__init__ applies _SIGNATURES: no method
-    declares a signature of its own."""
+    """The package assigns argtypes / restype only where Library.__init__ applies the ABI table: no method, and no other
+    module of the package, declares a signature of its own."""
+    import glob
     import re
-    src = open(os.path.join(os.path.dirname(os.path.abspath(fiasco_amd.__file__)), "__init__.py")).read()
-    lines = [l.strip() for l in src.splitlines() if re.search(r"\.(argtypes|restype)\b", l)]
+    package = os.path.dirname(os.path.abspath(fiasco_amd.__file__))
+    modules = sorted(glob.glob(os.path.join(package, "*.py")))
+    assert os.path.join(package, "__init__.py") in modules and len(modules) >= 2
+    lines = [l.strip() for m in modules for l in open(m).read().splitlines() if re.search(r"\.(argtypes|restype)\b", l)]
     assert lines == ["fn.restype, fn.argtypes = restype, argtypes"], lines
 
 
