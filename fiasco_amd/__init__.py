@@ -15,9 +15,9 @@ import ctypes
 import os
 import subprocess
 
-from ._abi import *  # noqa: F401,F403  (FiascoError, the enum values, the structures, ABI and the nine *_SYMBOLS lists)
+from ._abi import *  # noqa: F401,F403  (FiascoError, the enum values, the structures, ABI and the ten *_SYMBOLS lists)
 from ._abi import (_SIGNATURES, _VIDEO_SIGNATURES, _SMOOTH_SIGNATURES, _DISPLAY_SIGNATURES, _RENDER_SIGNATURES,  # noqa: F401
-                   _YUV420_SIGNATURES, _YCBCR_SIGNATURES, _RENDER420_SIGNATURES, _STREAM_SIGNATURES)
+                   _YUV420_SIGNATURES, _YCBCR_SIGNATURES, _RENDER420_SIGNATURES, _STREAM_SIGNATURES, _DECODER_SIGNATURES)
 from ._arrays import (_describe, _device_frames, _device_surfaces, _device_targets, _device_targets_420,  # noqa: F401
                       _empty_planes_420, _packed_planes, _packed_strides, _planes_420, _stream_of, _stream_over, _ycbcr_frames)
 
@@ -516,8 +516,18 @@ class Renderer:
 
     def __init__(self, lib, red_mask, green_mask, blue_mask, bpp, double_resolution=False):
         self.lib, self.bpp, self.double_resolution = lib, bpp, bool(double_resolution)
+        self.masks = (red_mask, green_mask, blue_mask)
+        self._fiasco = None
         self.handle = lib.L.fiasco_amd_renderer_new(red_mask, green_mask, blue_mask, bpp, 1 if double_resolution else 0)
         _check(lib, self.handle)
+
+    def fiasco_renderer(self):
+        """The fiasco_renderer_t of the same parameters (fiasco_renderer_new, include/libfiasco_amd_decoder.h), which renders
+        Images; made on first use, freed by delete().  It keeps a staging surface: one thread at a time."""
+        if not self._fiasco:
+            _need(self.lib, "fiasco_renderer_new", "the decoder half of fiasco.h")
+            self._fiasco = _check(self.lib, self.lib.L.fiasco_renderer_new(*self.masks, self.bpp, 1 if self.double_resolution else 0))
+        return self._fiasco
 
     def surface_size(self, width, height, color):
         """fiasco_amd_renderer_surface_size: (surface width, surface height, bytes of a packed row) for a frame of
@@ -564,6 +574,9 @@ class Renderer:
         return buf.raw
 
     def delete(self):
+        if self._fiasco:
+            self.lib.L.fiasco_renderer_delete(self._fiasco)
+            self._fiasco = None
         if self.handle:
             self.lib.L.fiasco_amd_renderer_delete(self.handle)
             self.handle = None
@@ -892,6 +905,133 @@ class Stream:
     def __del__(self):
         try:
             self.free()
+        except Exception:
+            pass
+
+
+class Image:
+    """fiasco_image_t (include/libfiasco_amd_decoder.h): a frame Decoder.get_frame() handed out, whose 12.4 planes live in
+    device memory, or a PNM file (Image.open), whose planes live on the host until device_planes() uploads them.  delete()
+    releases it; an image may outlive its decoder."""
+
+    def __init__(self, lib, handle):
+        self.lib, self.handle = lib, handle
+        # fiasco_image_get_height returns the width, as the reference's does
+        self.width, self.height = lib.L.fiasco_image_get_width(handle), lib.L.fiasco_amd_image_get_height(handle)
+        self.color = bool(lib.L.fiasco_image_is_color(handle))
+        self.format_420 = lib.L.fiasco_amd_image_format(handle) == 1
+
+    @classmethod
+    def open(cls, lib, path):
+        """fiasco_image_new: a raw PGM / PPM file (looked up in FIASCO_IMAGES) as an image."""
+        _need(lib, "fiasco_image_new", "the decoder half of fiasco.h")
+        return cls(lib, _check(lib, lib.L.fiasco_image_new(os.fsencode(path))))
+
+    def planes(self):
+        """fiasco_amd_image_planes: the planes on the host, int16 12.4 fixed point: [bands, h, w], or for a 4:2:0 image the
+        tuple Y [h, w], Cb and Cr [h / 2, w / 2] -- what the reference's fiasco_decoder_get_frame() hands out."""
+        import numpy
+        if self.format_420:
+            out, planes = _empty_planes_420(self.width, self.height)
+        else:
+            out = planes = numpy.empty((3 if self.color else 1, self.height, self.width), dtype=numpy.int16)
+        _check(self.lib, self.lib.L.fiasco_amd_image_planes(self.handle, out.ctypes.data))
+        return planes
+
+    def device_planes(self):
+        """fiasco_amd_image_planes_device: ([address of Y, Cb, Cr or None], device) of the planes where they live; the
+        memory belongs to the image."""
+        planes, device = (ctypes.c_void_p * 3)(), ctypes.c_int(-1)
+        _check(self.lib, self.lib.L.fiasco_amd_image_planes_device(self.handle, planes, ctypes.byref(device)))
+        return [planes[b] for b in range(3)], device.value
+
+    def _surface_size(self, renderer):
+        return renderer.surface_size_420(self.width, self.height) if self.format_420 else renderer.surface_size(self.width, self.height, self.color)
+
+    def render(self, renderer):
+        """fiasco_renderer_render with the fiasco_renderer_t of `renderer` (a Renderer): the bytes of the packed XImage."""
+        _, sh, row = self._surface_size(renderer)
+        buf = ctypes.create_string_buffer(sh * row)
+        _check(self.lib, self.lib.L.fiasco_renderer_render(renderer.fiasco_renderer(), buf, self.handle))
+        return buf.raw
+
+    def render_device(self, renderer, surface, stream=None):
+        """fiasco_amd_renderer_render_device: into `surface`, a writable uint8 GPU array as Batch.decode_rendered takes it,
+        on `stream` (default as decode_device)."""
+        if surface is None:
+            raise FiascoError("render_device: no surface")
+        arr = _device_surfaces([surface], renderer.bpp)
+        _check(self.lib, self.lib.L.fiasco_amd_renderer_render_device(renderer.fiasco_renderer(), arr, self.handle, _stream_of([surface], stream)))
+
+    def delete(self):
+        if self.handle:
+            self.lib.L.fiasco_image_delete(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.delete()
+        except Exception:
+            pass
+
+
+class Decoder:
+    """fiasco_decoder_t (include/libfiasco_amd_decoder.h): a .fco stream played display frame by display frame on the
+    device.  `source`: the stream as bytes, or the name of its file (looked up in FIASCO_DATA).  smoothing: -1 the header's
+    value, 0 none, 1 .. 100 per cent, None: the default of fiasco_d_options_new (70); read_ahead: how many display frames
+    one call may decode (fiasco_amd_decoder_set_read_ahead).  Iterating yields the remaining frames as Images."""
+
+    def __init__(self, lib, source, smoothing=None, magnify=0, format_420=False, read_ahead=32):
+        self.lib, self.handle = lib, None
+        _need(lib, "fiasco_decoder_new", "the decoder half of fiasco.h")
+        options = _check(lib, lib.L.fiasco_d_options_new())
+        try:
+            if smoothing is not None:
+                _check(lib, lib.L.fiasco_d_options_set_smoothing(options, smoothing))
+            _check(lib, lib.L.fiasco_d_options_set_magnification(options, magnify))
+            _check(lib, lib.L.fiasco_d_options_set_4_2_0_format(options, 1 if format_420 else 0))
+            if isinstance(source, (bytes, bytearray, memoryview)):
+                source = bytes(source)
+                self.handle = lib.L.fiasco_amd_decoder_new_memory(source, len(source), options)
+            else:
+                self.handle = lib.L.fiasco_decoder_new(os.fsencode(source), options)
+            _check(lib, self.handle)
+        finally:
+            lib.L.fiasco_d_options_delete(options)
+        _check(lib, lib.L.fiasco_amd_decoder_set_read_ahead(self.handle, read_ahead))
+        L, h = lib.L, self.handle
+        self.width, self.height, self.color = L.fiasco_decoder_get_width(h), L.fiasco_decoder_get_height(h), bool(L.fiasco_decoder_is_color(h))
+        self.rate, self.length = L.fiasco_decoder_get_rate(h), L.fiasco_decoder_get_length(h)
+        self.title = (L.fiasco_decoder_get_title(h) or b"").decode("latin-1")
+        self.comment = (L.fiasco_decoder_get_comment(h) or b"").decode("latin-1")
+
+    def get_frame(self):
+        """fiasco_decoder_get_frame: the next display frame as an Image.  FiascoError for a frame that fails -- it is
+        consumed, the next call goes on behind it -- and behind the last frame."""
+        return Image(self.lib, _check(self.lib, self.lib.L.fiasco_decoder_get_frame(self.handle)))
+
+    def write_frame(self, path):
+        """fiasco_decoder_write_frame: the next display frame, decoded in 4:4:4, as a raw PGM / PPM file."""
+        _check(self.lib, self.lib.L.fiasco_decoder_write_frame(self.handle, os.fsencode(path)))
+
+    @property
+    def position(self):
+        """fiasco_amd_decoder_position: the display frames consumed so far -- handed out, written or failed; a call that is
+        refused as a whole consumes nothing."""
+        return self.lib.L.fiasco_amd_decoder_position(self.handle)
+
+    def __iter__(self):
+        while self.position < self.length:
+            yield self.get_frame()
+
+    def delete(self):
+        if self.handle:
+            self.lib.L.fiasco_decoder_delete(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.delete()
         except Exception:
             pass
 

@@ -98,7 +98,7 @@ class Stats(ctypes.Structure):
 
 def _declare():
     """header -> {name: (restype, [argtypes])} of every function the header declares, in the header's order; the headers in
-    the order they were added.  Handles (options, batches, sequences, renderers, streams that were read), hipStream_t and
+    the order they were added.  Handles (options, batches, sequences, renderers, streams that were read, decoders, images), hipStream_t and
     planes travel as void pointers; buffers the callers make with create_string_buffer, and names, as char pointers."""
     c = ctypes
     P, ptr, cstr, i, u, f32, f64 = c.POINTER, c.c_void_p, c.c_char_p, c.c_int, c.c_uint, c.c_float, c.c_double
@@ -269,6 +269,42 @@ def _declare():
             "fiasco_amd_stream_decode_planes": (i, [ptr, u, i, ptr]),
             "fiasco_amd_stream_decode_planes_420": (i, [ptr, u, i, ptr]),
         },
+        # the decoder half of fiasco.h -- options, decoder, image, renderer -- and the extensions around it (the objects, the
+        # stream's header and the host renderer in host code; the frames in the HIP library)
+        "libfiasco_amd_decoder.h": {
+            "fiasco_d_options_new": (ptr, []),
+            "fiasco_d_options_delete": (None, [ptr]),
+            "fiasco_d_options_set_smoothing": (i, [ptr, i]),
+            "fiasco_d_options_set_magnification": (i, [ptr, i]),
+            "fiasco_d_options_set_4_2_0_format": (i, [ptr, i]),
+            "fiasco_decoder_new": (ptr, [cstr, ptr]),
+            "fiasco_decoder_delete": (i, [ptr]),
+            "fiasco_decoder_write_frame": (i, [ptr, cstr]),
+            "fiasco_decoder_get_frame": (ptr, [ptr]),
+            "fiasco_decoder_get_width": (u, [ptr]),
+            "fiasco_decoder_get_height": (u, [ptr]),
+            "fiasco_decoder_is_color": (i, [ptr]),
+            "fiasco_decoder_get_rate": (u, [ptr]),
+            "fiasco_decoder_get_length": (u, [ptr]),
+            "fiasco_decoder_get_title": (cstr, [ptr]),
+            "fiasco_decoder_get_comment": (cstr, [ptr]),
+            "fiasco_image_new": (ptr, [cstr]),
+            "fiasco_image_delete": (None, [ptr]),
+            "fiasco_image_get_width": (u, [ptr]),
+            "fiasco_image_get_height": (u, [ptr]),
+            "fiasco_image_is_color": (i, [ptr]),
+            "fiasco_renderer_new": (ptr, [ul, ul, ul, u, i]),
+            "fiasco_renderer_delete": (None, [ptr]),
+            "fiasco_renderer_render": (i, [ptr, ptr, ptr]),
+            "fiasco_amd_decoder_new_memory": (ptr, [cstr, size, ptr]),
+            "fiasco_amd_decoder_set_read_ahead": (i, [ptr, u]),
+            "fiasco_amd_decoder_position": (i, [ptr]),
+            "fiasco_amd_image_get_height": (u, [ptr]),
+            "fiasco_amd_image_format": (i, [ptr]),
+            "fiasco_amd_image_planes": (i, [ptr, ptr]),
+            "fiasco_amd_image_planes_device": (i, [ptr, P(ptr), P(i)]),
+            "fiasco_amd_renderer_render_device": (i, [ptr, surfaces, ptr, ptr]),
+        },
     }
 
 
@@ -284,6 +320,7 @@ _YUV420_SIGNATURES = ABI["libfiasco_amd_420.h"]
 _YCBCR_SIGNATURES = ABI["libfiasco_amd_ycbcr.h"]
 _RENDER420_SIGNATURES = ABI["libfiasco_amd_render_420.h"]
 _STREAM_SIGNATURES = ABI["libfiasco_amd_stream.h"]
+_DECODER_SIGNATURES = ABI["libfiasco_amd_decoder.h"]
 EXPORTED_SYMBOLS = list(_SIGNATURES)
 VIDEO_SYMBOLS = list(_VIDEO_SIGNATURES)
 SMOOTH_SYMBOLS = list(_SMOOTH_SIGNATURES)
@@ -293,3 +330,4 @@ YUV420_SYMBOLS = list(_YUV420_SIGNATURES)
 YCBCR_SYMBOLS = list(_YCBCR_SIGNATURES)
 RENDER420_SYMBOLS = list(_RENDER420_SIGNATURES)
 STREAM_SYMBOLS = list(_STREAM_SIGNATURES)
+DECODER_SYMBOLS = list(_DECODER_SIGNATURES)

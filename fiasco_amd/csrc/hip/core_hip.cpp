@@ -181,3 +181,4 @@ static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const D
 #include "render_420.inc"         /* behind both: display surfaces of frames decoded in 4:2:0 */
 #include "frame_decoder.inc"
 #include "stream_decode.inc"        /* behind the decoder: the frames of a .fco stream that was read, video frames included, into device buffers */
+#include "decoder_outlet.inc"       /* beside it: the shown planes of such frames into the images of a fiasco_decoder_t (fa_decoder.c) */

@@ -555,7 +555,10 @@ extern "C" void fa_core_release_dev(void *dev, int dev_id)
  * out != NULL (fiasco_amd_batch_decode_device, output_convert.inc): the frames are written as 8-bit pixels into
  * out->target[job]; such a frame gets no host image and no copy to the host (jobs[].out stays NULL, out->done[job] says
  * that it was written).  out->thumb != NULL (fiasco_amd_batch_decode_device_thumbnails): frame `job' is written a second
- * time, at 1 / 2^out->reduce of its side length, into out->thumb[job]; out->thumb_done[job] says so.
+ * time, at 1 / 2^out->reduce of its side length, into out->thumb[job]; out->thumb_done[job] says so.  out->planes != NULL
+ * (the images of a fiasco_decoder_t, decoder_outlet.inc): the shown planes themselves are copied into out->planes[job], a
+ * buffer that was made before the call (the flight allocates nothing), instead of being converted; out->done[job] says
+ * that they were.
  * ds != NULL (fiasco_amd_batch_decode_distortion_device, distortion.inc): the frames are compared with their originals
  * before the pixels are written, if they are (a frame whose target has no data is measured only).  Such a frame gets
  * no host image either; ds->done[job] says that it was measured. */
@@ -692,7 +695,7 @@ static void dec_flight_prepare(DecShare &S, DecFlight &F, const unsigned *idx, s
             /* 4:2:0 planes have consumers of their own -- the 4:2:0 targets of the call, or the host -- and a flight has one
              * assembly launch: the frames of a call are of one format */
             const bool c420 = F.fr[k].c420;
-            if ((c420 && (S.ds || S.images || thumbs || (S.out && !S.out->t420))) || (!c420 && S.out && S.out->t420)
+            if ((c420 && (S.ds || S.images || thumbs || (S.out && !S.out->t420 && !S.out->planes))) || (!c420 && S.out && S.out->t420)
                 || (!F.alive.empty() && F.fr[F.alive[0]].c420 != c420)) {
                 dec_fail(&S.jobs[F.job[k]], "device decoder: 4:2:0 frames and 4:4:4 frames do not share a call, and 4:2:0 frames go to 4:2:0 targets or to the host");
                 continue;
@@ -917,6 +920,27 @@ static void dec_flight_measure(DecShare &S, DecFlight &F)
 static void dec_flight_write(DecShare &S, DecFlight &F)
 {
     unsigned long long total = 0, thtotal = 0;
+    if (S.out->planes) {
+        /* the planes outlet: no layout forces a kernel -- the shown planes are packed as the image keeps them: one copy */
+        std::vector<size_t> run;
+        for (size_t k : F.alive) {
+            const unsigned i = F.job[k];
+            const DecFrame &D = F.fr[k];
+            if (S.out->target[i].data) {
+                int16_t *buf = S.out->planes[i];
+                if (!buf || S.out->planes_dev[i] != S.device || D.vals * 2 != S.out->planes_bytes) {
+                    dec_fail(&S.jobs[i], "device decoder: the buffer for the frame's planes does not fit the frame or its device");
+                    continue;
+                }
+                if (hipMemcpyAsync(buf, dec_shown(D), D.vals * 2, hipMemcpyDeviceToDevice, S.stream) != hipSuccess) {
+                    (void) hipGetLastError(); dec_fail(&S.jobs[i], "device decoder: HIP error"); continue;
+                }
+            }
+            run.push_back(k);
+        }
+        F.alive.swap(run);
+        return;
+    }
     for (size_t k : F.alive) {
         if (F.fr[k].thumb) {
             F.thoctab.emplace_back();
@@ -1055,15 +1079,47 @@ static void dec_share_release_caller(DecShare &S)
     if (written) (void) hipEventDestroy(written);
 }
 
+/* What a share makes per call -- its stream, the two events and the arena -- kept between the calls of a caller that comes
+ * again: a fiasco_decoder_t owns one (OcOut::keep, decoder_outlet.inc) for its lifetime, so a call for one display frame
+ * costs its flight and no stream, event or arena.  The arena only grows.  A stream's jobs carry one share key, so one share
+ * serves the decoder (decode_frames refuses a call with a DecKeep whose jobs are dealt to more); should the share's device change between calls, what is kept is released and made again there.
+ * Between calls nothing of it is in use: every flight ends with a wait for its stream */
+struct DecKeep {
+    int         device = -1;
+    hipStream_t stream = nullptr;
+    hipEvent_t  ev0 = nullptr, ev1 = nullptr;
+    char       *arena = nullptr; size_t arena_b = 0;
+};
+
+static void dec_keep_release(DecKeep &K)
+{
+    int cur = -1;
+    bool moved = false;
+    if (K.device >= 0 && hipGetDevice(&cur) == hipSuccess && cur != K.device) moved = hipSetDevice(K.device) == hipSuccess;
+    if (K.arena) (void) hipFree(K.arena);
+    if (K.ev0) (void) hipEventDestroy(K.ev0);
+    if (K.ev1) (void) hipEventDestroy(K.ev1);
+    if (K.stream) (void) hipStreamDestroy(K.stream);
+    (void) hipGetLastError();
+    if (moved) (void) hipSetDevice(cur);
+    K = DecKeep();
+}
+
 /* the jobs `mine' of a call on this thread's device, in flights.  Returns the number of frames decoded */
 static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine, const OcOut *out, const DsOut *ds, bool images)
 {
     DecShare S;
     S.jobs = jobs; S.out = out; S.ds = ds; S.images = images;
-    bool usable = hipGetDevice(&S.device) == hipSuccess && hipStreamCreate(&S.stream) == hipSuccess;
+    DecKeep *K = out ? out->keep : nullptr;
+    bool usable = hipGetDevice(&S.device) == hipSuccess;
+    if (K && K->stream && (!usable || K->device != S.device)) dec_keep_release(*K);
+    if (usable && K && K->stream) { S.stream = K->stream; S.ev0 = K->ev0; S.ev1 = K->ev1; S.arena = K->arena; S.arena_b = K->arena_b; }
+    else {
+        usable = usable && hipStreamCreate(&S.stream) == hipSuccess;
+        if (usable && (hipEventCreate(&S.ev0) != hipSuccess || hipEventCreate(&S.ev1) != hipSuccess)) (void) hipGetLastError();
+    }
     if (usable) S.ncu = ft_cus();
     if (!usable) (void) hipGetLastError();
-    else if (hipEventCreate(&S.ev0) != hipSuccess || hipEventCreate(&S.ev1) != hipSuccess) (void) hipGetLastError();
     std::vector<unsigned> todo;
     for (unsigned i : mine) {
         fa_dec_job *j = &jobs[i];
@@ -1091,7 +1147,11 @@ static int decode_share(fa_dec_job *jobs, const std::vector<unsigned> &mine, con
         dec_flight_release(F);
         f0 += n;
     }
-    if (out && S.stream) dec_share_release_caller(S);
+    if (out && !out->planes && S.stream) dec_share_release_caller(S);
+    if (K && usable) {
+        K->device = S.device; K->stream = S.stream; K->ev0 = S.ev0; K->ev1 = S.ev1; K->arena = S.arena; K->arena_b = S.arena_b;
+        return S.good;
+    }
     if (S.arena) (void) hipFree(S.arena);
     if (S.ev0) (void) hipEventDestroy(S.ev0);
     if (S.ev1) (void) hipEventDestroy(S.ev1);
@@ -1110,6 +1170,11 @@ static int decode_frames(unsigned n, fa_dec_job *jobs, const OcOut *out, const D
     std::vector<size_t> share;
     for (size_t k = 0; k < ND; k++) if (!deal[k].empty()) share.push_back(k);
     if (share.empty()) return 0;
+    /* what a caller keeps between calls (OcOut::keep) is ONE stream and ONE arena: two shares must never adopt it at once */
+    if (out && out->keep && share.size() > 1) {
+        for (unsigned i = 0; i < n; i++) if (!jobs[i].skip) dec_fail(&jobs[i], "device decoder: jobs with a kept share context were dealt to more than one share (they must carry one share key)");
+        return 0;
+    }
     std::vector<int> goodv(share.size(), 0);
     for_shares(share, [&](size_t part) { goodv[part] = decode_share(jobs, deal[share[part]], out, ds, images); });
     int good = 0;

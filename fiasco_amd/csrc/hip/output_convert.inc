@@ -118,6 +118,16 @@ struct OcOut {
      * `render' set as well (fiasco_amd_batch_decode_device_rendered_420, render_420.inc) t420[i].y, y_pitch, width and
      * height describe the checked surface of frame i, and the flight launches rd420_render_kernel */
     const fiasco_amd_device_target_420 *t420 = nullptr;
+    /* the shown planes themselves instead (the images of a decoder, decoder_outlet.inc): target[] only says which frames are
+     * wanted (ready and caller are not used: nobody else knows the buffers).  planes[i] is a buffer of planes_bytes bytes on
+     * device planes_dev[i], made BEFORE the call; the flight copies the planes the other consumers would read -- smoothed
+     * where smoothing applies, 4:4:4 or 4:2:0 as the jobs say -- into it on its stream, and allocates nothing.  A frame
+     * whose values do not fill the buffer exactly, or that is decoded on another device, fails */
+    int16_t *const *planes = nullptr;                   /* [n] */
+    const int      *planes_dev = nullptr;               /* [n] */
+    size_t          planes_bytes = 0;
+    /* what a share keeps between calls for a caller that comes again (a decoder): see DecKeep, frame_decoder.inc */
+    struct DecKeep *keep = nullptr;
 };
 
 static void oc_describe(OcFrame &d, const int16_t *planes, const fiasco_amd_device_frame &t, unsigned long long &total)

@@ -440,6 +440,48 @@ const fa_info *fa_stream_info(const struct fiasco_amd_stream *s);
 typedef void (*fa_stream_run)(void *ctx, unsigned n, fa_dec_job *jobs, const unsigned *display, const uint8_t *wanted);
 int fa_stream_walk(const struct fiasco_amd_stream *s, const char *who, unsigned first, unsigned count, const uint8_t *mask, int magnify, int smoothing,
                    int format_420, fa_stream_run run, void *ctx, int keep_images, fa_image **result, char (*errs)[160]);
+/* The same walk with its state kept between calls: a cursor.  fa_stream_walk() is one open, one advance over the whole
+ * range and one close; a decoder that hands out one display frame per call (fa_decoder.c) advances as it goes, and every
+ * coded frame is decoded once per cursor.  open: the range, mask, magnification, smoothing and format of the walk; what
+ * each wanted frame is predicted from is worked out here, and the walk's refusals are given here (NULL + message).
+ * advance(display, ahead): decodes, in the walk's flights, every frame not yet decoded up to the last coded frame among
+ * the wanted display frames display .. display + ahead - 1.  A frame that is a future reference and shown later is
+ * decoded then, as a wanted frame: run() gets it once, smoothed for its consumer, and the cursor holds its unsmoothed
+ * image for the frames predicted from it.  An image is released as soon as no frame still to come is predicted from it
+ * (with keep_images a wanted one stays until it is taken or the cursor is closed); close releases everything.
+ * status: 1 decoded, 0 failed (*cause: why, the cursor's string), -1 not decoded yet.  held: images the cursor holds */
+typedef struct fa_cursor fa_cursor;
+fa_cursor *fa_cursor_open(const struct fiasco_amd_stream *s, const char *who, unsigned first, unsigned count, const uint8_t *mask, int magnify,
+                          int smoothing, int format_420, int keep_images);
+void      fa_cursor_advance(fa_cursor *c, unsigned display, unsigned ahead, fa_stream_run run, void *ctx);
+int       fa_cursor_status(const fa_cursor *c, unsigned display, const char **cause);
+fa_image *fa_cursor_take(fa_cursor *c, unsigned display);
+unsigned  fa_cursor_held(const fa_cursor *c);
+void      fa_cursor_close(fa_cursor *c);
+/* the stream in a buffer or a file, as fiasco_amd_stream_open[_file] opens it; name: for the messages */
+struct fiasco_amd_stream *fa_stream_open_named(const unsigned char *data, size_t len, const char *name);
+
+/* ---------------- the device side of the decoder objects (csrc/hip/decoder_outlet.inc; fa_decoder.c calls it) ---------- */
+/* A fa_stream_run for a cursor: the wanted jobs get the planes outlet of their flight (OcOut::planes) -- the shown planes,
+ * smoothed where smoothing applies, Y / Cb / Cr back to back (4:2:0: the chroma planes packed), copied on the flight's
+ * stream into a device buffer of their own.  ctx: a fa_outlet, whose planes[display] / device[display] receive the buffer
+ * (released with fa_dev_free) */
+typedef struct fa_outlet {
+    int16_t **planes; int *device;        /* out, by display number */
+    size_t    bytes;                      /* of the planes of one frame shown */
+    void   *(*take)(void *pool, size_t bytes, int device);     /* a buffer the caller has to spare, or NULL: allocated then */
+    void     *pool;
+    void    **keep;                       /* the caller's slot for what the share keeps between calls -- its stream, events and
+                                           * arena --, made by the first call; released with fa_dev_keep_free */
+} fa_outlet;
+void  fa_dev_outlet_run(void *ctx, unsigned n, fa_dec_job *jobs, const unsigned *display, const uint8_t *wanted);
+void  fa_dev_keep_free(void *keep);
+int   fa_dev_available(void);                                  /* 0 + the library's no-device message */
+void  fa_dev_free(void *p, int device);
+void *fa_dev_upload(const void *host, size_t bytes, int *device);          /* NULL + message */
+int   fa_dev_download(void *host, const void *dev, size_t bytes, int device);       /* waits; 0 + message */
+/* a staging surface in device memory that grows: *buf of *cap bytes on *device */
+int   fa_dev_reserve(void **buf, size_t *cap, size_t bytes, int device);
 
 /* MPEG's code of a vector component, {code, length}, index = component + search range (fa_writer.c) */
 extern const unsigned short fa_mv_code[33][2];

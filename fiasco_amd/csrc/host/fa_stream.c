@@ -5,7 +5,9 @@
  *  Open reads everything (fa_reader.c).  Which frames serve as past and future of which follows get_next_frame
  *  (codec/decoder.c:160-410); fa_sequence.c holds the coder-side twin of that rule.  The walk hands the frames to the
  *  core's decoder (fa_core_decode_frames: the device) as jobs with from_stream set: the reference frames of a stream
- *  that is walked live at the magnification and in the format shown.
+ *  that is walked live at the magnification and in the format shown.  Its state is a cursor (fa_cursor) that may be
+ *  kept between calls: fa_stream_walk() is one open, one advance and one close; the decoder objects (fa_decoder.c)
+ *  advance one display frame per call.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -97,6 +99,8 @@ bad:
     return NULL;
 }
 
+struct fiasco_amd_stream *fa_stream_open_named(const unsigned char *data, size_t len, const char *name) { return stream_open(data, len, name); }
+
 fiasco_amd_stream_t *fiasco_amd_stream_open(const unsigned char *data, size_t len)
 {
     if (!data) { fa_set_error("fiasco_amd_stream_open: no stream"); return NULL; }
@@ -178,109 +182,196 @@ int fiasco_amd_stream_smoothing_borders(const fiasco_amd_stream_t *s, unsigned d
     return (int) fa_smoothing_borders(w, s->wi.width, s->wi.height, s->wi.color, out, cap);
 }
 
-/* ---------------------------------------------------------------- the walk */
+/* ---------------------------------------------------------------- the cursor, and the walk over it */
 
-int fa_stream_walk(const struct fiasco_amd_stream *s, const char *who, unsigned first, unsigned count, const uint8_t *mask, int magnify, int smoothing,
-                   int format_420, fa_stream_run run, void *ctx, int keep_images, fa_image **result, char (*errs)[160])
+/* The state of get_next_frame's walk, kept between calls (fa_host.h).  Everything is indexed by coded frame.  need,
+ * isref, wanted and last_use are fixed at open: what the wanted frames of the range are predicted from.  images[] holds
+ * the decoded frames a frame still to come is predicted from -- unsmoothed, with their device planes (keep_dev) --, and
+ * with keep_images the wanted ones until they are taken; next is the position in coding order */
+struct fa_cursor {
+    const struct fiasco_amd_stream *s;
+    char       who[64];
+    unsigned   first, count;
+    int        magnify, smoothing, format_420, keep_images;
+    unsigned   next;
+    uint8_t   *need, *isref, *failed, *wanted, *done;
+    int       *last_use;
+    fa_image **images;
+    char     (*cause)[160];
+    fa_dec_job *jobs;
+    unsigned  *batch, *disp;
+    uint8_t   *bw;
+};
+
+void fa_cursor_close(fa_cursor *c)
+{
+    unsigned k;
+    if (!c) return;
+    for (k = 0; c->images && k < c->s->n; k++) fa_image_free(c->images[k]);
+    free(c->need); free(c->isref); free(c->failed); free(c->wanted); free(c->done); free(c->last_use); free(c->images); free(c->cause);
+    free(c->jobs); free(c->batch); free(c->disp); free(c->bw);
+    free(c);
+}
+
+fa_cursor *fa_cursor_open(const struct fiasco_amd_stream *s, const char *who, unsigned first, unsigned count, const uint8_t *mask, int magnify,
+                          int smoothing, int format_420, int keep_images)
 {
     const unsigned n = s->n;
-    uint8_t *need, *isref, *failed, *wanted_k;
-    int *last_use;
-    fa_image **images;
-    char (*cause)[160];
-    fa_dec_job *jobs;
-    unsigned *batch, *disp, nb = 0, k, i;
-    uint8_t *bw;
-    int good = 0, video = 0;
+    fa_cursor *c;
+    unsigned k, i;
+    int video = 0;
 
-    if (!count || first >= n || count > n - first) { fa_set_error("%s: frames %u .. %u of a stream of %u frames", who, first, first + count - 1, n); return 0; }
-    if (smoothing < -1 || smoothing > 100) { fa_set_error("%s: smoothing out of range (-1: the header's value, 0: none, 1 .. 100 per cent)", who); return 0; }
+    if (!count || first >= n || count > n - first) { fa_set_error("%s: frames %u .. %u of a stream of %u frames", who, first, first + count - 1, n); return NULL; }
+    if (smoothing < -1 || smoothing > 100) { fa_set_error("%s: smoothing out of range (-1: the header's value, 0: none, 1 .. 100 per cent)", who); return NULL; }
     if (smoothing < 0) smoothing = s->wi.smoothing <= 100 ? (int) s->wi.smoothing : 0;      /* get_next_frame :372-374 */
-    need = (uint8_t *) calloc(n, 1); isref = (uint8_t *) calloc(n, 1); failed = (uint8_t *) calloc(n, 1); wanted_k = (uint8_t *) calloc(n, 1);
-    last_use = (int *) calloc(n, sizeof *last_use);
-    images = (fa_image **) calloc(n, sizeof *images);
-    cause = (char (*)[160]) calloc(n, 160);
-    jobs = (fa_dec_job *) calloc(n, sizeof *jobs);
-    batch = (unsigned *) calloc(n, sizeof *batch); disp = (unsigned *) calloc(n, sizeof *disp); bw = (uint8_t *) calloc(n, 1);
-    if (!need || !isref || !failed || !wanted_k || !last_use || !images || !cause || !jobs || !batch || !disp || !bw) { fa_set_error("Out of memory!"); goto out; }
-    for (i = first; i < first + count; i++) if (!mask || mask[i - first]) { need[s->coded_of[i]] = 1; wanted_k[s->coded_of[i]] = 1; }
+    c = (fa_cursor *) calloc(1, sizeof *c);
+    if (!c) { fa_set_error("Out of memory!"); return NULL; }
+    c->s = s; c->first = first; c->count = count; c->magnify = magnify; c->smoothing = smoothing; c->format_420 = format_420; c->keep_images = keep_images;
+    snprintf(c->who, sizeof c->who, "%s", who);
+    c->need = (uint8_t *) calloc(n, 1); c->isref = (uint8_t *) calloc(n, 1); c->failed = (uint8_t *) calloc(n, 1); c->wanted = (uint8_t *) calloc(n, 1);
+    c->done = (uint8_t *) calloc(n, 1);
+    c->last_use = (int *) calloc(n, sizeof *c->last_use);
+    c->images = (fa_image **) calloc(n, sizeof *c->images);
+    c->cause = (char (*)[160]) calloc(n, 160);
+    c->jobs = (fa_dec_job *) calloc(n, sizeof *c->jobs);
+    c->batch = (unsigned *) calloc(n, sizeof *c->batch); c->disp = (unsigned *) calloc(n, sizeof *c->disp); c->bw = (uint8_t *) calloc(n, 1);
+    if (!c->need || !c->isref || !c->failed || !c->wanted || !c->done || !c->last_use || !c->images || !c->cause || !c->jobs || !c->batch || !c->disp || !c->bw) {
+        fa_set_error("Out of memory!");
+        goto bad;
+    }
+    for (i = first; i < first + count; i++) if (!mask || mask[i - first]) { c->need[s->coded_of[i]] = 1; c->wanted[s->coded_of[i]] = 1; }
     for (k = n; k-- > 0; ) {
-        last_use[k] = -1;
-        if (!need[k]) continue;
+        c->last_use[k] = -1;
+        if (!c->need[k]) continue;
         video = video || s->wfa[k]->frame_type != FA_I_FRAME;
     }
     for (k = n; k-- > 0; ) {
         int r;
-        if (!need[k]) continue;
+        if (!c->need[k]) continue;
         for (r = 0; r < 2; r++) {
             const int ref = r ? s->future[k] : s->past[k];
             if (ref < 0 || s->wfa[k]->frame_type == FA_I_FRAME) continue;
-            need[ref] = 1; isref[ref] = 1;
-            if (last_use[ref] < (int) k) last_use[ref] = (int) k;
+            c->need[ref] = 1; c->isref[ref] = 1;
+            if (c->last_use[ref] < (int) k) c->last_use[ref] = (int) k;
         }
     }
     if (video && s->wi.half_pixel) {
         fa_set_error("Half-pixel motion vectors are not supported (the reference coder's half-pixel "
                      "path reads outside the reference frame).");
-        goto out;
+        goto bad;
     }
-    for (k = 0; k <= n; k++) {
-        int flush = k == n;
-        if (!flush && !need[k]) continue;
-        for (i = 0; !flush && i < nb; i++)
-            flush = s->wfa[k]->frame_type != FA_I_FRAME && ((int) batch[i] == s->past[k] || (int) batch[i] == s->future[k]);
-        if (flush && nb) {
-            unsigned nj = 0, j;
-            unsigned *owner = batch;                       /* jobs[j] is frame owner[j]: compacted in place */
-            for (i = 0; i < nb; i++) {
-                const unsigned f = batch[i];
-                const fa_wfa *w = s->wfa[f];
-                fa_dec_job *d = &jobs[nj];
-                int r, dead = 0;
-                for (r = 0; r < 2 && !dead && w->frame_type != FA_I_FRAME; r++) {
-                    const int ref = r ? s->future[f] : s->past[f];
-                    if (ref >= 0 && failed[ref]) {
-                        snprintf(cause[f], 160, "display frame %u is predicted from frame %u, which failed: %.90s", s->number[f], s->number[ref], cause[ref]);
-                        failed[f] = 1; dead = 1;
-                    }
-                }
-                if (dead) continue;
-                memset(d, 0, sizeof *d);
-                d->wfa = w; d->width = s->wi.width; d->height = s->wi.height; d->color = s->wi.color; d->frame_type = w->frame_type;
-                if (w->frame_type != FA_I_FRAME) {
-                    d->past = s->past[f] >= 0 ? images[s->past[f]] : NULL;
-                    d->future = s->future[f] >= 0 ? images[s->future[f]] : NULL;
-                }
-                d->p_max_level = s->wi.p_max_level;
-                d->keep_dev = isref[f]; d->share_key = 1;           /* one share: the references never change device */
-                d->magnify = magnify; d->format_420 = format_420; d->from_stream = 1;
-                d->smoothing = wanted_k[f] ? smoothing : 0;
-                disp[nj] = s->number[f]; bw[nj] = wanted_k[f]; owner[nj] = f;
-                nj++;
+    return c;
+bad:
+    fa_cursor_close(c);
+    return NULL;
+}
+
+/* the frames gathered go to run() as one call; then what nobody still to come (from coded frame k on) is predicted from goes */
+static void cursor_flush(fa_cursor *c, unsigned nb, unsigned k, fa_stream_run run, void *ctx)
+{
+    const struct fiasco_amd_stream *s = c->s;
+    unsigned nj = 0, i, j;
+    unsigned *owner = c->batch;                    /* jobs[j] is frame owner[j]: compacted in place */
+    for (i = 0; i < nb; i++) {
+        const unsigned f = c->batch[i];
+        const fa_wfa *w = s->wfa[f];
+        fa_dec_job *d = &c->jobs[nj];
+        int r, dead = 0;
+        c->done[f] = 1;
+        for (r = 0; r < 2 && !dead && w->frame_type != FA_I_FRAME; r++) {
+            const int ref = r ? s->future[f] : s->past[f];
+            if (ref >= 0 && c->failed[ref]) {
+                snprintf(c->cause[f], 160, "display frame %u is predicted from frame %u, which failed: %.90s", s->number[f], s->number[ref], c->cause[ref]);
+                c->failed[f] = 1; dead = 1;
             }
-            if (nj) run(ctx, nj, jobs, disp, bw);
-            for (j = 0; j < nj; j++) {
-                const unsigned f = owner[j];
-                if (jobs[j].out) { images[f] = jobs[j].out; good += wanted_k[f]; }
-                else { failed[f] = 1; snprintf(cause[f], 160, "%s", jobs[j].errmsg[0] ? jobs[j].errmsg : "decoder failed"); }
-            }
-            /* what nobody is predicted from any more */
-            for (j = 0; j < n; j++)
-                if (images[j] && last_use[j] < (int) k && !(keep_images && wanted_k[j])) { fa_image_free(images[j]); images[j] = NULL; }
-            nb = 0;
         }
-        if (k < n) batch[nb++] = k;
+        if (dead) continue;
+        memset(d, 0, sizeof *d);
+        d->wfa = w; d->width = s->wi.width; d->height = s->wi.height; d->color = s->wi.color; d->frame_type = w->frame_type;
+        if (w->frame_type != FA_I_FRAME) {
+            d->past = s->past[f] >= 0 ? c->images[s->past[f]] : NULL;
+            d->future = s->future[f] >= 0 ? c->images[s->future[f]] : NULL;
+        }
+        d->p_max_level = s->wi.p_max_level;
+        d->keep_dev = c->isref[f]; d->share_key = 1;        /* one share: the references never change device */
+        d->magnify = c->magnify; d->format_420 = c->format_420; d->from_stream = 1;
+        d->smoothing = c->wanted[f] ? c->smoothing : 0;
+        c->disp[nj] = s->number[f]; c->bw[nj] = c->wanted[f]; owner[nj] = f;
+        nj++;
     }
+    if (nj) run(ctx, nj, c->jobs, c->disp, c->bw);
+    for (j = 0; j < nj; j++) {
+        const unsigned f = owner[j];
+        if (c->jobs[j].out) c->images[f] = c->jobs[j].out;
+        else { c->failed[f] = 1; snprintf(c->cause[f], 160, "%s", c->jobs[j].errmsg[0] ? c->jobs[j].errmsg : "decoder failed"); }
+    }
+    for (j = 0; j < s->n; j++)
+        if (c->images[j] && c->last_use[j] < (int) k && !(c->keep_images && c->wanted[j])) { fa_image_free(c->images[j]); c->images[j] = NULL; }
+}
+
+void fa_cursor_advance(fa_cursor *c, unsigned display, unsigned ahead, fa_stream_run run, void *ctx)
+{
+    const struct fiasco_amd_stream *s = c->s;
+    const unsigned end = c->first + c->count;
+    unsigned nb = 0, k, i, to = 0;
+    /* one behind the last coded frame among the wanted display frames display .. display + ahead - 1 */
+    for (i = display < c->first ? c->first : display; i < end && i - display < ahead; i++)
+        if (c->wanted[s->coded_of[i]] && s->coded_of[i] + 1 > to) to = s->coded_of[i] + 1;
+    if (to <= c->next) return;
+    for (k = c->next; k <= to; k++) {
+        int flush = k == to;
+        if (!flush && !c->need[k]) continue;
+        for (i = 0; !flush && i < nb; i++)
+            flush = s->wfa[k]->frame_type != FA_I_FRAME && ((int) c->batch[i] == s->past[k] || (int) c->batch[i] == s->future[k]);
+        if (flush && nb) { cursor_flush(c, nb, k, run, ctx); nb = 0; }
+        if (k < to) c->batch[nb++] = k;
+    }
+    c->next = to;
+}
+
+int fa_cursor_status(const fa_cursor *c, unsigned display, const char **cause)
+{
+    const unsigned f = display < c->s->n ? c->s->coded_of[display] : 0;
+    if (cause) *cause = "";
+    if (display >= c->s->n || !c->done[f]) return -1;
+    if (cause && c->failed[f]) *cause = c->cause[f];
+    return !c->failed[f];
+}
+
+fa_image *fa_cursor_take(fa_cursor *c, unsigned display)
+{
+    const unsigned f = display < c->s->n ? c->s->coded_of[display] : 0;
+    fa_image *im;
+    if (display >= c->s->n || !c->keep_images || !c->wanted[f] || c->last_use[f] >= (int) c->next) return NULL;
+    im = c->images[f]; c->images[f] = NULL;
+    return im;
+}
+
+unsigned fa_cursor_held(const fa_cursor *c)
+{
+    unsigned k, held = 0;
+    for (k = 0; k < c->s->n; k++) held += c->images[k] != NULL;
+    return held;
+}
+
+int fa_stream_walk(const struct fiasco_amd_stream *s, const char *who, unsigned first, unsigned count, const uint8_t *mask, int magnify, int smoothing,
+                   int format_420, fa_stream_run run, void *ctx, int keep_images, fa_image **result, char (*errs)[160])
+{
+    fa_cursor *c = fa_cursor_open(s, who, first, count, mask, magnify, smoothing, format_420, keep_images);
+    int good = 0, named = 0;
+    unsigned i;
+    if (!c) return 0;
+    fa_cursor_advance(c, first, count, run, ctx);
     for (i = first; i < first + count; i++) {
-        const unsigned f = s->coded_of[i];
-        if (errs) snprintf(errs[i - first], 160, "%s", failed[f] ? cause[f] : "");
-        if (keep_images && result) { result[i - first] = images[f]; images[f] = NULL; }
+        const char *cause;
+        const int st = fa_cursor_status(c, i, &cause);
+        if (errs) snprintf(errs[i - first], 160, "%s", cause);
+        if (keep_images && result) result[i - first] = fa_cursor_take(c, i);
+        if (!c->wanted[s->coded_of[i]]) continue;
+        good += st == 1;
+        if (!st && !named) { fa_set_error("%s: display frame %u: %s", who, i, cause); named = 1; }
     }
-    for (i = first; i < first + count; i++)
-        if (wanted_k[s->coded_of[i]] && failed[s->coded_of[i]]) { fa_set_error("%s: display frame %u: %s", who, i, cause[s->coded_of[i]]); break; }
-out:
-    for (k = 0; images && k < n; k++) fa_image_free(images[k]);
-    free(need); free(isref); free(failed); free(wanted_k); free(last_use); free(images); free(cause); free(jobs); free(batch); free(disp); free(bw);
+    fa_cursor_close(c);
     return good;
 }
 
